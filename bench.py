@@ -34,8 +34,12 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
                 one-row walk of the sweep (gclm_set_row_pairs(h, 0)) -- the row-pair walk's effect on THIS box.
   overlap:      N=1, independent intrinsics: the same batch solved as two halves on two side streams
                 (LMOptimizer.overlap_streams = 2, the library's default for large batches); `value` stays the one-stream run.
-The timed region (exactly --steps steps between barrier + synchronize) is run --repeats times; `value` and
-`ms_per_step` are the MEDIAN region (a 0.2-0.4 s window has a few % of run-to-run variance), all regions are listed.
+The timed region is exactly --steps steps between barrier + synchronize: by default the only one, so --steps K runs K
+timed steps and `ms_per_step` is the time of one of them.  --repeats R runs R such regions (R x K timed steps); `value` and
+`ms_per_step` are then the MEDIAN region (a 0.2-0.4 s window has a few % of run-to-run variance), all regions are listed.
+--dump-outputs DIR: after the timed regions, rank 0 writes what the timed path returned in its last step as DIR/<name>.npy
+(float32 / float64); the inputs are a function of the arguments alone (device generator keyed by --seed and image index),
+so two builds run with the same arguments can be compared output for output.
 `value`, `ms_per_step` and `roofline` are measured on every rank's FIRST allocation of its input fields; at N = 1
 `placement.best_of_n` carries, beside them, the same measurement on the fastest-streaming of --placement-tries allocations
 (a serving loop may choose where its persistent field buffers live; the line of record does not).
@@ -72,7 +76,7 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of --steps steps each; the median is reported")
     ap.add_argument("--batch", type=int, default=1024, help="images per GPU")
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
@@ -106,6 +110,9 @@ def parse():
                          "2 frames of each of batch/2 groups) -- configs[4]'s partition at shape on fewer GPUs")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend; gloo (+ ranks sharing GPUs) only to exercise the N>1 path on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0: write the result of the timed path's last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the images beyond that)")
     return ap.parse_args()
 
 
@@ -398,6 +405,37 @@ def quick_case(lib, LMOptimizer, synth_fields, dev, model, B, H, W, lm_steps, se
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, max_bytes=DUMP_MAX_BYTES):
+    """What a caller of the timed path receives, as DIR/<name>.npy: `camera` / `gravity` are the (n, 8) / (n, 3) records of
+    the wrappers, every other tensor of the result dict is written as returned; float32 and float64 keep their type, other
+    dtypes become float64 (exact for the integer counts).  Beyond `max_bytes` in all, the same seeded sample of images is
+    written for every per-image output, and `dump_rows.npy` names the images.  Returns a summary."""
+    import numpy as np
+    arrays = {}
+    for name, v in out.items():
+        t = v._data if hasattr(v, "_data") else v
+        if torch.is_tensor(t):
+            a = t.detach().cpu().numpy()
+            arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    n = max(a.shape[0] if a.ndim else 1 for a in arrays.values())
+    per_image = [k for k, a in arrays.items() if a.ndim and a.shape[0] == n]
+    rows = None
+    if sum(a.nbytes for a in arrays.values()) > max_bytes:
+        fixed = sum(a.nbytes for k, a in arrays.items() if k not in per_image)
+        row_bytes = sum(arrays[k].nbytes // n for k in per_image) + 8          # (+ its entry in dump_rows)
+        rows = np.sort(np.random.default_rng(2024).choice(n, size=max(1, (max_bytes - fixed) // row_bytes), replace=False))
+        arrays.update({k: arrays[k][rows] for k in per_image}, dump_rows=rows.astype(np.float64))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+    return {"dir": os.path.abspath(directory), "arrays": sorted(arrays), "images": n,
+            "sampled_images": None if rows is None else int(rows.size),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def rccl_versions(lib):
     """NCCL_VERSION_CODE libgeocalib_hip.so was compiled against, ncclGetVersion() of the librccl this process bound
     (inside a torch process: torch's own librccl.so, loaded first, same soname), and torch's view of the same."""
@@ -647,6 +685,7 @@ def main():
         per_rank_sweep_ms = [x[2].item() for x in allr]     # every rank's own mean sweep launch (its own HIP events)
         per_rank_rc = [x[3].item() for x in allr]           # ... and its own allocation's pure-read ceiling
     elapsed = sorted(regions)[len(regions) // 2]
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # sanity: the solve must have recovered the synthetic ground truth (a fast wrong answer is no answer)
     cam = out["camera"]._data
@@ -810,6 +849,8 @@ def main():
                           "(geocalib_amd.fields.fastest_placement, DESIGN.md 9.1; candidate 0 = the first allocation)"},
         }
         result.update(extras)
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         if distributed:
             result["multi_gpu"] = {
                 "ranks_seen": ranks_seen, "per_rank_ms": per_rank_ms,

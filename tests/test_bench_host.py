@@ -3,8 +3,9 @@
 (1) without a HIP device `bench.py` (and `bench.py --gpus N`, which would start its own ranks) answers with ONE JSON line
     carrying `error` and a non-zero exit code -- never a traceback, never a CPU fallback of the product path;
 (2) `cpu_baseline()` has two branches: the reference's own PyTorch path timed on THIS box when the checkout is there
-    ($GEOCALIB_REFERENCE / /root/reference: the build container), otherwise the C port alone with
-    `reference_on_this_box: false`.  Both keep the keys the driver parses (value, unit, cores, kind)."""
+    ($GEOCALIB_REFERENCE / /root/reference: the build container; a stub checkout here), otherwise the C port alone with
+    `reference_on_this_box: false`.  Both keep the keys the driver parses (value, unit, cores, kind);
+(3) `dump_outputs()` (--dump-outputs DIR) writes the timed path's result as .npy files, sampled beyond its size cap."""
 import json
 import os
 import subprocess
@@ -63,19 +64,64 @@ def test_cpu_baseline_without_the_reference_is_the_port(monkeypatch):
     assert full is None or (full["kind"] == "reference" and "build container" in full["measured_on"])
 
 
-def test_cpu_baseline_times_the_reference_where_it_exists():
-    from oracle import ref_import
-    if not ref_import.available():
-        pytest.skip("no reference checkout on this box")
+STUB_LM_OPTIMIZER = '''
+import torch
+
+CALLS = []
+
+
+class LMOptimizer(torch.nn.Module):
+    """Stands in for the reference's LMOptimizer: records how it is driven, returns the shapes a caller reads."""
+
+    def __init__(self, conf):
+        super().__init__()
+        self.conf = dict(conf)
+
+    def forward(self, data):
+        n = data["latitude_field"].shape[0]
+        CALLS.append({"conf": self.conf, "training": self.training, "grad": torch.is_grad_enabled(), "images": n,
+                      "threads": torch.get_num_threads(), "keys": sorted(data)})
+        return {"camera": torch.zeros(n, 8), "gravity": torch.zeros(n, 3)}
+'''
+
+
+def test_cpu_baseline_times_the_reference_where_it_exists(monkeypatch, tmp_path):
+    """A checkout at $GEOCALIB_REFERENCE (here a stub package with the modules ref_import loads): its LMOptimizer is timed
+    as the baseline of record, in eval mode without autograd, on the host's granted cores, after a one-image warm-up,
+    with the port beside it."""
+    pkg = tmp_path / "geocalib"
+    pkg.mkdir()
+    for name in ("__init__", "perspective_fields", "camera", "gravity", "misc", "utils"):
+        (pkg / f"{name}.py").write_text("")
+    (pkg / "lm_optimizer.py").write_text(STUB_LM_OPTIMIZER)
     bench = _bench()
-    data = _sample(3)
-    out = bench.cpu_baseline(_args(), 3, data)
+    from oracle import lm_oracle, ref_import
+    real_root = ref_import.REFERENCE_ROOT
+    monkeypatch.setattr(ref_import, "REFERENCE_ROOT", str(tmp_path))
+    monkeypatch.setattr(sys, "path", [q for q in sys.path if q != real_root])     # (ref_import.load prepends the stub's root)
+    assert ref_import.available()
+    saved = {k: sys.modules.pop(k) for k in list(sys.modules) if k == "geocalib" or k.startswith("geocalib.")}
+    threads = torch.get_num_threads()
+    try:
+        out = bench.cpu_baseline(_args(), 3, _sample(3))
+        calls = sys.modules["geocalib.lm_optimizer"].CALLS
+    finally:
+        for k in [k for k in sys.modules if k == "geocalib" or k.startswith("geocalib.")]:
+            del sys.modules[k]
+        sys.modules.update(saved)
     assert out["kind"] == "reference" and out["measured_on"] == "this box" and out["reference_on_this_box"] is True
     assert out["value"] > 0 and out["unit"] == "images/sec" and out["cores"] >= 1
     assert "lm_optimizer.py:141" in out["code"] and "the first 3 images" in out["sample"]
     assert out["port"]["kind"] == "port" and out["port"]["value"] > 0
+    # one-image warm-up, then the timed call on the whole sample; the conf of the line, eval mode, no autograd, all cores
+    assert [c["images"] for c in calls] == [1, 3]
+    cores = lm_oracle.effective_cpus()
+    for c in calls:
+        assert c["conf"] == {"camera_model": "pinhole", "num_steps": 5, "early_stop": False, "shared_intrinsics": False}
+        assert c["training"] is False and c["grad"] is False and c["threads"] == cores
+        assert c["keys"] == ["latitude_confidence", "latitude_field", "up_confidence", "up_field"]
     # the thread count of the process is restored
-    assert torch.get_num_threads() >= 1
+    assert torch.get_num_threads() == threads
 
 
 def test_cpu_baseline_survives_a_broken_reference_checkout(monkeypatch, tmp_path):
@@ -135,3 +181,34 @@ def test_vs_oracle_record_and_the_kept_oracle_result(monkeypatch):
     assert kept_g["camera"][0, 3] != kept_g["camera"][3, 3]          # ... and not the same for both
     direct = bench.oracle_solve("pinhole", 5, {k: v[:3] for k, v in data.items()}, 3, 2)
     assert np.array_equal(direct["camera"], kept_g["camera"][:3])
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """--dump-outputs: every tensor of the result dict as DIR/<name>.npy (the camera / gravity records of the wrappers),
+    float32 kept, other dtypes as float64; beyond the size cap one seeded sample of images, the same for every output."""
+    import numpy as np
+    bench = _bench()
+    n = 40
+    rec = types.SimpleNamespace
+    out = {"camera": rec(_data=torch.arange(n * 8, dtype=torch.float32).reshape(n, 8)),
+           "gravity": rec(_data=torch.arange(n * 3, dtype=torch.float32).reshape(n, 3)),
+           "covariance": torch.arange(n * 9, dtype=torch.float32).reshape(n, 3, 3),
+           "final_cost": torch.linspace(0, 1, n, dtype=torch.float64), "stop_at": torch.full((n,), 7, dtype=torch.int32),
+           "note": "not an array"}
+    info = bench.dump_outputs(out, str(tmp_path / "all"))
+    assert info["images"] == n and info["sampled_images"] is None and info["arrays"] == sorted(k for k in out if k != "note")
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in info["arrays"]}
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(f"{k}.npy" for k in info["arrays"])
+    assert got["camera"].dtype == np.float32 and np.array_equal(got["camera"], out["camera"]._data.numpy())
+    assert got["covariance"].shape == (n, 3, 3) and got["final_cost"].dtype == np.float64
+    assert got["stop_at"].dtype == np.float64 and (got["stop_at"] == 7).all()
+    assert info["bytes"] == sum(a.nbytes for a in got.values())
+    # a cap of ~half the bytes: the same images of every output, named by dump_rows, within the cap, the same on every call
+    cap = info["bytes"] // 2
+    small = bench.dump_outputs(out, str(tmp_path / "s1"), max_bytes=cap)
+    again = bench.dump_outputs(out, str(tmp_path / "s2"), max_bytes=cap)
+    assert 0 < small["sampled_images"] < n and small["bytes"] <= cap and small == {**again, "dir": small["dir"]}
+    rows = np.load(tmp_path / "s1" / "dump_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "dump_rows.npy")) and np.all(np.diff(rows) > 0)
+    for k in info["arrays"]:
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), got[k][rows]), k

@@ -1344,7 +1344,7 @@ def test_bench_multi_rank_path_on_one_gpu(dev, extra):
     port = 29500 + (os.getpid() % 400)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--batch", "64", "--steps", "2", "--warmup", "1", "--cpu-sample", "0"] + extra
+           "--batch", "64", "--steps", "2", "--warmup", "1", "--repeats", "3", "--cpu-sample", "0"] + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
