@@ -734,7 +734,10 @@ static void invert(int n, const double *A, double *inv) {
  *  0 stop_at, 1 initial_up_cost, 2 initial_latitude_cost, 3 initial_cost,
  *  4 final_up_cost, 5 final_latitude_cost, 6 final_cost,
  *  7 roll_unc, 8 pitch_unc, 9 gravity_unc, 10 focal_unc, 11 vfov_unc, 12 n_params,
- *  13 final lambda, 16.. covariance (P x P row-major)
+ *  13 final lambda, 16.. covariance (P x P),
+ *  14 failed steps of this image: a damped system that is not positive definite (lm_oracle_solve_from also counts a
+ *     non-finite step).  Under lm_oracle_solve's reference rule (:129-133) one image's failure zeroes the step of the
+ *     WHOLE batch, yet only the failing image is counted; with shared intrinsics a failure counts for every frame.
  */
 int lm_oracle_info_stride(void) { return INFO_STRIDE; }
 int lm_oracle_real_bytes(void) { return (int)sizeof(real); }
@@ -752,9 +755,11 @@ static double total_cost(const oracle_data *d, const sys_t *s) {
 #define TRACE_STRIDE 48
 int lm_oracle_trace_stride(void) { return TRACE_STRIDE; }
 
-int lm_oracle_solve(const oracle_conf *cf, const oracle_data *d, float *cam_out /*B x 8*/,
-                    float *grav_out /*B x 3*/, float *info /*B x INFO_STRIDE*/,
-                    double *trace /* num_steps x B x TRACE_STRIDE or NULL */) {
+/* The loop of lm_oracle_solve, started from an optional state: init_cam (B x 8), init_grav (B x 3), init_lam (B), each
+ * NULL for get_trivial_estimation's value / lambda0.  contain != 0: a failed damped Cholesky (or a non-finite step) zeroes
+ * the step of ITS image only, as the HIP update does, instead of the whole batch (:129-133). */
+static int solve_impl(const oracle_conf *cf, const oracle_data *d, const float *init_cam, const float *init_grav,
+                      const float *init_lam, int contain, float *cam_out, float *grav_out, float *info, double *trace) {
     const int B = d->B;
     plan_t pl;
     make_plan(cf, d, &pl);
@@ -772,7 +777,17 @@ int lm_oracle_solve(const oracle_conf *cf, const oracle_data *d, float *cam_out 
     real *new_cost = (real *)malloc(sizeof(real) * B);
     real *delta = (real *)calloc((size_t)B * MAXP, sizeof(real));
     memset(info, 0, sizeof(float) * (size_t)B * INFO_STRIDE);
-    for (int b = 0; b < B; ++b) { oracle_init(cf, d, b, &cam[b], &grav[b]); lamb[b] = (real)cf->lambda0; }
+    float *fails = (float *)calloc(B, sizeof(float));
+    for (int b = 0; b < B; ++b) {
+        oracle_init(cf, d, b, &cam[b], &grav[b]);
+        lamb[b] = init_lam ? (real)init_lam[b] : (real)cf->lambda0;
+        if (init_cam) {
+            const float *c8 = init_cam + (size_t)b * 8;
+            cam_t c = {c8[0], c8[1], c8[2], c8[3], c8[4], c8[5], c8[6], c8[7]};
+            cam[b] = c;
+        }
+        if (init_grav) { vec3 g = {init_grav[b * 3], init_grav[b * 3 + 1], init_grav[b * 3 + 2]}; grav[b] = g; }
+    }
 
     int stop_at = cf->num_steps;
     /* pass at theta_0 */
@@ -791,9 +806,15 @@ int lm_oracle_solve(const oracle_conf *cf, const oracle_data *d, float *cam_out 
             for (int b = 0; b < B; ++b) {
                 real Hm[MAXP * MAXP], G[MAXP];
                 for (int k = 0; k < P; ++k) { G[k] = (real)sys[b].G[k]; for (int l = 0; l < P; ++l) Hm[k * P + l] = (real)sys[b].Hm[k][l]; }
-                if (!lm_step(P, Hm, G, lamb[b], &delta[b * MAXP])) any_fail = 1;
+                int ok = lm_step(P, Hm, G, lamb[b], &delta[b * MAXP]);
+                if (contain) for (int k = 0; k < P; ++k) ok = ok && isfinite(delta[b * MAXP + k]);
+                if (!ok) {
+                    any_fail = 1;
+                    fails[b] += 1;
+                    if (contain) memset(&delta[b * MAXP], 0, sizeof(real) * MAXP);
+                }
             }
-            if (any_fail) memset(delta, 0, sizeof(real) * (size_t)B * MAXP);  /* :129-133 */
+            if (any_fail && !contain) memset(delta, 0, sizeof(real) * (size_t)B * MAXP);  /* :129-133 */
         } else {
             /* arrow-head system (:350-383): [2B gravity dims | n_intrinsic] */
             const int ni = pl.n_intrinsic, n = 2 * B + ni;
@@ -814,7 +835,12 @@ int lm_oracle_solve(const oracle_conf *cf, const oracle_data *d, float *cam_out 
                     for (int j = 0; j < ni; ++j) A[(2 * B + i) * n + 2 * B + j] += (real)sys[b].Hm[2 + i][2 + j];
                 }
             }
-            if (!lm_step(n, A, g, lamb[0], dl)) memset(dl, 0, sizeof(real) * n);
+            int ok = lm_step(n, A, g, lamb[0], dl);
+            if (contain) for (int k = 0; k < n; ++k) ok = ok && isfinite(dl[k]);
+            if (!ok) {
+                memset(dl, 0, sizeof(real) * n);
+                for (int b = 0; b < B; ++b) fails[b] += 1;
+            }
             for (int b = 0; b < B; ++b) {   /* :599-603 */
                 delta[b * MAXP + 0] = dl[2 * b]; delta[b * MAXP + 1] = dl[2 * b + 1];
                 for (int j = 0; j < ni; ++j) delta[b * MAXP + 2 + j] = dl[2 * B + j];
@@ -871,6 +897,7 @@ int lm_oracle_solve(const oracle_conf *cf, const oracle_data *d, float *cam_out 
         o[4] = (float)sys[b].cost_up; o[5] = (float)sys[b].cost_lat; o[6] = (float)total_cost(d, &sys[b]);
         o[12] = (float)P;
         o[13] = (float)lamb[cf->shared_intrinsics ? 0 : b];
+        o[14] = fails[b];
         if (!cf->training) {
             double Hd[MAXP * MAXP], Cov[MAXP * MAXP];
             for (int k = 0; k < P; ++k) for (int l = 0; l < P; ++l) Hd[k * P + l] = (double)(real)sys[b].Hm[k][l];
@@ -896,8 +923,24 @@ int lm_oracle_solve(const oracle_conf *cf, const oracle_data *d, float *cam_out 
         co[4] = (float)cam[b].cx; co[5] = (float)cam[b].cy; co[6] = (float)cam[b].k1; co[7] = (float)cam[b].k2;
         grav_out[b * 3] = (float)grav[b].x; grav_out[b * 3 + 1] = (float)grav[b].y; grav_out[b * 3 + 2] = (float)grav[b].z;
     }
-    free(cam); free(grav); free(sys); free(lamb); free(prev_cost); free(new_cost); free(delta);
+    free(cam); free(grav); free(sys); free(lamb); free(prev_cost); free(new_cost); free(delta); free(fails);
     return 0;
+}
+
+int lm_oracle_solve(const oracle_conf *cf, const oracle_data *d, float *cam_out /*B x 8*/,
+                    float *grav_out /*B x 3*/, float *info /*B x INFO_STRIDE*/,
+                    double *trace /* num_steps x B x TRACE_STRIDE or NULL */) {
+    return solve_impl(cf, d, NULL, NULL, NULL, 0, cam_out, grav_out, info, trace);
+}
+
+/* lm_oracle_solve from a given state (test infrastructure for per-step checks: one step from a kernel's own state).
+ * init_cam (B x 8), init_grav (B x 3, taken as given), init_lam (B; image 0's for shared intrinsics): NULL = the usual
+ * initialisation.  Departure from the reference, for this entry only: a failed Cholesky zeroes the step of its own image
+ * (the HIP update's rule), not the whole batch's (:129-133), and info[14] counts each image's failed steps.
+ * num_steps = 0 returns the final costs and the covariance at the given state. */
+int lm_oracle_solve_from(const oracle_conf *cf, const oracle_data *d, const float *init_cam, const float *init_grav,
+                         const float *init_lam, float *cam_out, float *grav_out, float *info, double *trace) {
+    return solve_impl(cf, d, init_cam, init_grav, init_lam, 1, cam_out, grav_out, info, trace);
 }
 
 /* Render the perspective field of a camera (perspective_fields.py:278-320): up (2,H,W), lat (1,H,W). */

@@ -61,6 +61,7 @@ def _lib(precision: str):
             build()
         lib = C.CDLL(path)
         lib.lm_oracle_solve.restype = C.c_int
+        lib.lm_oracle_solve_from.restype = C.c_int
         lib.lm_oracle_system.restype = C.c_int
         lib.lm_oracle_jacobians.restype = C.c_int
         _libs[precision] = lib
@@ -120,12 +121,17 @@ def _pack(conf, data, training=False, num_threads=0):
 
 
 def solve(data: dict, conf: dict = None, precision: str = "f32", training: bool = False,
-          num_threads: int = 0, trace: bool = False) -> dict:
+          num_threads: int = 0, trace: bool = False, init=None) -> dict:
     """Run the restated LMOptimizer.forward (lm_optimizer.py:646-664) on numpy inputs.
 
     data keys follow the reference: up_field (B,2,H,W), latitude_field (B,1,H,W), up_confidence,
     latitude_confidence (B,H,W), scales (2,), prior_focal (B,), prior_gravity (B,3), prior_dist (B,nd).
     Returns numpy arrays keyed like the reference's output dict (camera -> (B,8), gravity -> (B,3)).
+
+    init = (camera (B,8), gravity (B,3), lambda (B,)), any of them None: start the loop from that state
+    (lm_oracle_solve_from).  That entry contains a failed Cholesky to its own image, as the HIP update does,
+    instead of zeroing the whole batch's step like the reference; `step_failures` counts them per image.
+    With num_steps = 0 it returns the final costs and the covariance at the given state.
     """
     lib = _lib(precision)
     cf, c, d, keep, (B, H, W) = _pack(conf, data, training, num_threads)
@@ -136,8 +142,15 @@ def solve(data: dict, conf: dict = None, precision: str = "f32", training: bool 
     tr = None
     if trace:
         tr = np.zeros((cf["num_steps"], B, lib.lm_oracle_trace_stride()), np.float64)
-    rc = lib.lm_oracle_solve(C.byref(c), C.byref(d), _ptr(cam), _ptr(grav), _ptr(info),
-                             tr.ctypes.data_as(C.POINTER(C.c_double)) if trace else None)
+    trp = tr.ctypes.data_as(C.POINTER(C.c_double)) if trace else None
+    if init is None:
+        rc = lib.lm_oracle_solve(C.byref(c), C.byref(d), _ptr(cam), _ptr(grav), _ptr(info), trp)
+    else:
+        icam, igrav, ilam = (_f32(a) for a in init)
+        for a, shape in ((icam, (B, 8)), (igrav, (B, 3)), (ilam, (B,))):
+            assert a is None or a.shape == shape, (a.shape, shape)
+        rc = lib.lm_oracle_solve_from(C.byref(c), C.byref(d), _ptr(icam), _ptr(igrav), _ptr(ilam), _ptr(cam),
+                                      _ptr(grav), _ptr(info), trp)
     if rc != 0:
         raise RuntimeError(f"lm_oracle_solve failed: {rc}")
     P = int(info[0, 12])
@@ -145,7 +158,7 @@ def solve(data: dict, conf: dict = None, precision: str = "f32", training: bool 
            "initial_up_cost": info[:, 1].copy(), "initial_latitude_cost": info[:, 2].copy(),
            "initial_cost": info[:, 3].copy(), "final_up_cost": info[:, 4].copy(),
            "final_latitude_cost": info[:, 5].copy(), "final_cost": info[:, 6].copy(),
-           "lambda": info[:, 13].copy()}
+           "lambda": info[:, 13].copy(), "step_failures": info[:, 14].copy()}
     if not training:
         out.update({"covariance": info[:, 16:16 + P * P].reshape(B, P, P).copy(),
                     "roll_uncertainty": info[:, 7].copy(), "pitch_uncertainty": info[:, 8].copy(),
