@@ -1409,7 +1409,11 @@ __global__ __launch_bounds__(kBlock) void residual_kernel(const float* up, const
 
 // calculate_costs (lm_optimizer.py:276-315) on residual rows of `dim` components (dim = 0: the input already holds
 // |r|^2, as scaled_loss / huber_loss take it): Huber cost and weight at scale a, both times the confidence -- the
-// sweep's own branch-free form -- and optionally the second derivative of the scaled loss (:87, / a^2 of :76).
+// sweep's own branch-free form -- and optionally the second derivative of the scaled loss (:87, / a^2 of :76), which
+// the confidence does not enter.  Unlike the sweep's residuals, these inputs are arbitrary (huber_loss takes any x), so
+// the reference's floor isx = max(eps, 1/sqrt(y + 1e-8)) (:82) is kept: it moves the weight and the second derivative
+// beyond y = 1/eps^2 (~7.04e13) only, and y = +inf gives the reference's (inf, eps, -0) instead of cost = inf * 0.
+constexpr float kHuberEps = 1.1920928955078125e-07f;        // torch.finfo(torch.float).eps
 __global__ void huber_costs_kernel(const float* residual, size_t n, int dim, float a, const float* conf, float* cost,
                                    float* weight, float* second) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1418,14 +1422,14 @@ __global__ void huber_costs_kernel(const float* residual, size_t n, int dim, flo
     for (int d = 0; d < dim; ++d) x2 = fmaf(residual[i * dim + d], residual[i * dim + d], x2);
     const float c = conf ? conf[i] : 1.0f;
     float acc = 0.f;
-    const float a2 = a * a;
-    const float wc = huber_accumulate(x2, 1.0f / a2, c, acc);
-    if (cost) cost[i] = acc * a2;
-    if (weight) weight[i] = wc;
-    if (second) {
-        const float y = x2 / a2;
-        second[i] = y <= 1.0f ? 0.f : -wc / (2.0f * y * a2);
-    }
+    const float a2 = a * a, inv_a2 = 1.0f / a2;
+    huber_accumulate(x2, inv_a2, c, acc);
+    const float y = x2 * inv_a2;                              // huber_accumulate's y
+    const float w = vrsq_min1(y);                             // huber_accumulate's weight
+    const float isx = w < kHuberEps ? kHuberEps : w;          // (not fmaxf: a NaN stays NaN, as in torch.max)
+    if (cost) cost[i] = y == __builtin_inff() ? y * c : acc * a2;
+    if (weight) weight[i] = isx * c;
+    if (second) second[i] = y <= 1.0f ? 0.f : -isx / (2.0f * y * a2);
 }
 
 template <int MODEL, int VEC>

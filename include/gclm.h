@@ -262,7 +262,9 @@ int gclm_residual_fields(int camera_model, const float* d_up, const float* d_lat
 /*
  * LMOptimizer.calculate_costs (geocalib/lm_optimizer.py:276-315) for one residual tensor: n rows of `dim`
  * components (dim = 0: the n inputs already are |r|^2) -> scaled Huber cost and weight at `scale` (scaled_loss
- * :61-76, huber_loss :79-87), both multiplied by d_conf (n) when given, and the loss's second derivative.
+ * :61-76, huber_loss :79-87), both multiplied by d_conf (n) when given, and the scaled loss's second derivative,
+ * which is NOT multiplied by d_conf (scaled_loss's d2 carries no confidence).  The weight is floored at FLT_EPSILON
+ * as the reference's is (y = |r|^2 / scale^2 beyond 1/eps^2); y = +inf gives cost inf, weight eps, second -0.
  * d_cost / d_weight / d_second (n) may each be NULL.
  */
 int gclm_huber_costs(const float* d_residual, size_t n, int dim, float scale, const float* d_conf, float* d_cost,

@@ -1684,7 +1684,7 @@ def test_residuals_and_costs_match_reference(dev, model):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("model", HIP_MODELS)
+@pytest.mark.parametrize("model", HIP_MODELS + ("radial",))
 def test_one_lm_step_composed_from_the_public_stages(dev, model):
     """The reference's loop body written with the public pieces -- system (residuals + costs + Jacobians +
     reductions), optimizer_step (damped Cholesky on the device), update_estimate -- reproduces what ONE step of the
@@ -1722,7 +1722,7 @@ def test_one_lm_step_composed_from_the_public_stages(dev, model):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("model", HIP_MODELS)
+@pytest.mark.parametrize("model", HIP_MODELS + ("radial",))
 def test_reference_stage_methods_agree_with_the_fused_path(dev, model):
     """calculate_residuals -> calculate_costs -> setup_system (materialised Jacobians + device contraction) gives the
     Hessian / gradient of the fused sweep; estimate_uncertainty on them gives forward's covariance and sigmas; the
@@ -1734,11 +1734,25 @@ def test_reference_stage_methods_agree_with_the_fused_path(dev, model):
     cam, grav = out["camera"], out["gravity"]
     res = opt.calculate_residuals(cam, grav, data)
     costs, weights = opt.calculate_costs(res, data)
+    from geocalib_amd import perspective_fields as pf
+    from test_stage_oracle import U, contraction_bounds, contraction_ref
     for as_rpf in (False, True):
         G, H = opt.setup_system(cam, grav, res, weights, as_rpf=as_rpf)
         s = opt.system(data, cam, grav, as_rpf=as_rpf)
         scale = s["H"].abs().amax((1, 2), keepdim=True)
         assert ((H - s["H"]).abs() / scale).max() < 2e-5
+        # and per entry against the float64 contraction of the same float32 Jacobians, residuals and weights
+        # (tests/test_stage_oracle.py: contraction gate, plus one float32 rounding for the up + latitude sum)
+        J_up, J_lat = (t.cpu().numpy() for t in pf.J_perspective_field(
+            cam, grav, spherical=opt.conf.use_spherical_manifold and not as_rpf, log_focal=opt.conf.use_log_focal and not as_rpf))
+        B, cols = J_up.shape[0], opt._column_dims()
+        parts = [(J_up.reshape(B, -1, 2, J_up.shape[-1])[..., cols], res["up_residual"].cpu().numpy(), weights["up_weights"].cpu().numpy()),
+                 (J_lat.reshape(B, -1, 1, J_lat.shape[-1])[..., cols], res["latitude_residual"].cpu().numpy(),
+                  weights["latitude_weights"].cpu().numpy())]
+        G64, H64 = (sum(contraction_ref(*p)[i] for p in parts) for i in (0, 1))
+        gG = sum(contraction_bounds(*p)[0] for p in parts) + U * np.abs(G64)
+        gH = sum(contraction_bounds(*p)[1] for p in parts) + U * np.abs(H64)
+        assert (np.abs(G.cpu().numpy() - G64) <= gG).all() and (np.abs(H.cpu().numpy() - H64) <= gH).all()
         assert ((G - s["G"]).abs() / s["H"].abs().amax((1, 2)).sqrt()[:, None]).max() < 1e-3     # G ~ 0 at the optimum
     unc = opt.estimate_uncertainty(cam, grav, res, weights)
     assert torch.allclose(unc["covariance"], out["covariance"], rtol=2e-3, atol=1e-9)
