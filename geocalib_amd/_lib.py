@@ -67,8 +67,12 @@ _SIGNATURES = {
     "gclm_workspace_bytes": (C.c_size_t, [_P]),
     "gclm_solve": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gclm_calibrate": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "gclm_solve_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "gclm_calibrate_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P,
+                                    _P]),
     "gclm_system": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
     "gclm_shared_begin": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "gclm_shared_begin_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
     "gclm_shared_reduce": (C.c_int, [_P, C.c_int, _P, _P]),
     "gclm_shared_apply": (C.c_int, [_P, C.c_int, _P, _P]),
     "gclm_shared_finish": (C.c_int, [_P, _P, _P]),
@@ -81,6 +85,7 @@ _SIGNATURES = {
     "gclm_huber_costs": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
     "gclm_jacobian_fields": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gclm_pack_fields": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "gclm_pack_fields_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gclm_synth_fields": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,
                                     _P, _P, _P, _P, _P, _P, _P]),
     "gclm_synth_fields_grouped": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,

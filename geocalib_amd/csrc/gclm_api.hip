@@ -49,6 +49,7 @@ struct gclm_handle {
         float *cam_io = nullptr, *grav_io = nullptr;
         Geometry geo{};
         bool slat_ready = false;    // the scratch plane holds sin(latitude) of this session's fields
+        const float* given = nullptr;   // the caller's plane of sin(latitude) these sweeps read (handed_slat), or null
     } sh;
     // The sin(latitude) scratch plane is an allocation of its own, of exactly the size asked for (no headroom), and the only
     // part of the workspace a solve can do without: see ensure_slat.
@@ -223,8 +224,28 @@ bool slat_wanted(const gclm_handle* h, const float* up, const float* upc, const 
     return sweep_has_slat_plane(h->cfg.camera_model);
 }
 
-// The sweep arguments of the next sweep of a solve that keeps the scratch plane: the first one fills it, the others read it
-void apply_slat(const gclm_handle* h, SweepArgs& a, bool& ready) {
+// The plane of sin(latitude_field) a caller handed (gclm_solve_ex, gclm_calibrate_ex, gclm_shared_begin_ex) that this
+// solve's sweeps read in place of `lat`, from the first sweep on -- or null: they read the radians, as without the plane.
+// Read by the five-plane float4 sweeps of the distortion models (one-row and row-pair walks) and by the five-plane
+// one-launch-per-step kernel of every model; ignored by pinhole's batch sweeps (memory-bound: the review keeps that kernel
+// as it is), the scalar path, four-plane and latitude-only sweeps, and a plane whose 16-byte alignment differs from the
+// other planes' (include/gclm.h says so).  Such a solve never wants the library's own plane.
+const float* handed_slat(const gclm_handle* h, const float* sl, const float* up, const float* upc, const float* latc,
+                         const Geometry& g, bool fused) {
+    if (!sl || g.vec != 4 || !is_aligned16(sl) || !up || !upc || !latc) return nullptr;
+    if (!fused && h->cfg.camera_model == GCLM_PINHOLE) return nullptr;
+    return sl;
+}
+
+// The sweep arguments of the next sweep of a solve that reads the caller's plane (every sweep: SLAT = 2), or that keeps the
+// scratch plane: the first one fills it, the others read it
+void apply_slat(const gclm_handle* h, SweepArgs& a, bool& ready, const float* given) {
+    if (given) {
+        a.slat = const_cast<float*>(given);     // (slat_mode 2 never writes through it)
+        a.lat = given;
+        a.slat_mode = 2;
+        return;
+    }
     if (!h->slat) return;
     a.slat = h->slat;
     if (ready) { a.slat_mode = 2; a.lat = h->slat; }
@@ -603,7 +624,7 @@ int gclm_last_pass_timing(gclm_handle* h, int* n_launches, float* total_ms) {
 
 static int run_solve(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
                      const float* d_lat_conf, int B, int H, int W, const InitArgs& ia, float* d_cam_out,
-                     float* d_grav_out, float* d_info_out, void* stream) {
+                     float* d_grav_out, float* d_info_out, const float* d_sin_lat, void* stream) {
     if (int rc = check_shapes(h, d_lat, B, H, W)) return rc;
     if (B > 0 && (!d_cam_out || !d_grav_out || !d_info_out)) return fail(h, -3, "null output pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -636,7 +657,8 @@ static int run_solve(gclm_handle* h, const float* d_up, const float* d_lat, cons
     if (int rc = setup_groups(h, B)) return rc;
     const bool es = h->cfg.early_stop != 0;
     const bool fused_path = !geo.mirror && use_fused(h, B, geo);      // (plan_sweeps only pairs rows where the step is not one launch)
-    const bool keep_slat = slat_wanted(h, d_up, d_up_conf, d_lat_conf, geo, fused_path);
+    const float* given = handed_slat(h, d_sin_lat, d_up, d_up_conf, d_lat_conf, geo, fused_path);
+    const bool keep_slat = !given && slat_wanted(h, d_up, d_up_conf, d_lat_conf, geo, fused_path);
     if (int rc = ensure_workspace(h, B, geo.nchunks, c.n_groups)) return rc;
     ensure_slat(h, keep_slat ? (size_t)B * H * W : 0);
     h->sh.active = false;
@@ -683,6 +705,7 @@ static int run_solve(gclm_handle* h, const float* d_up, const float* d_lat, cons
             }
             if (stop_seen && !fin) continue;       // the final launch finds the stop in the counters, as it always does
             SweepArgs a = sweep_args(h, d_up, d_lat, d_up_conf, d_lat_conf, c.pb[0], geo, !fin, 0);
+            apply_slat(h, a, slat_ready, given);        // (never the library's plane here: slat_wanted)
             a.partials = part[step & 1];
             FusedArgs f;
             f.c = c;
@@ -702,7 +725,7 @@ static int run_solve(gclm_handle* h, const float* d_up, const float* d_lat, cons
     }
     for (int step = 0; step < h->cfg.num_steps; ++step) {
         SweepArgs a = sweep_args(h, d_up, d_lat, d_up_conf, d_lat_conf, c.pb[step & 1], geo, true, es ? step : 0);
-        apply_slat(h, a, slat_ready);
+        apply_slat(h, a, slat_ready, given);
         if (int rc = timed_sweep(h, a, s)) return rc;
         if (!h->cfg.shared_intrinsics) {
             GCLM_HIP(h, launch_update(c, step, s));
@@ -717,27 +740,34 @@ static int run_solve(gclm_handle* h, const float* d_up, const float* d_lat, cons
     }
     GCLM_HIP(h, launch_prep_final(c, s));
     SweepArgs a = sweep_args(h, d_up, d_lat, d_up_conf, d_lat_conf, c.pb_final, geo, false, 0);
-    apply_slat(h, a, slat_ready);
+    apply_slat(h, a, slat_ready, given);
     if (int rc = timed_sweep(h, a, s)) return rc;
     GCLM_HIP(h, launch_finalize(c, d_cam_out, d_grav_out, d_info_out, s));
     return 0;
 }
 
-int gclm_solve(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
-               const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
-               float* d_info_out, void* stream) {
+int gclm_solve_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                  const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
+                  float* d_info_out, const float* d_sin_lat, void* stream) {
     if (!h) return -1;
     InitArgs ia{};
     ia.cam = d_cam_io;
     ia.grav = d_grav_io;
     if (B != 0 && (!d_cam_io || !d_grav_io)) return fail(h, -3, "gclm_solve: null camera / gravity pointer");
-    return run_solve(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, ia, d_cam_io, d_grav_io, d_info_out, stream);
+    return run_solve(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, ia, d_cam_io, d_grav_io, d_info_out, d_sin_lat, stream);
 }
 
-int gclm_calibrate(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
-                   const float* d_lat_conf, int B, int H, int W, const float* d_scales,
-                   const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
-                   int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out, void* stream) {
+int gclm_solve(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+               const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
+               float* d_info_out, void* stream) {
+    return gclm_solve_ex(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_cam_io, d_grav_io, d_info_out, nullptr, stream);
+}
+
+int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                      const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                      const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                      int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
+                      const float* d_sin_lat, void* stream) {
     if (!h) return -1;
     if (d_prior_dist && (prior_dist_cols < 1 || prior_dist_cols > 2)) return fail(h, -3, "gclm_calibrate: prior_dist_cols must be 1 or 2");
     // the free-parameter flags must agree with the priors (setup_optimization_and_priors, :204-221); an empty batch has
@@ -753,7 +783,16 @@ int gclm_calibrate(gclm_handle* h, const float* d_up, const float* d_lat, const 
     ia.up = d_up;
     ia.lat = d_lat;
     if (h->cfg.heuristic_init && !d_up && B != 0) return fail(h, -3, "gclm_calibrate: heuristic_init needs the up field");
-    return run_solve(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, stream);
+    // (the initial estimate -- the heuristic one reads `lat` -- always reads the radians: ia.lat)
+    return run_solve(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, d_sin_lat, stream);
+}
+
+int gclm_calibrate(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                   const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                   const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                   int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out, void* stream) {
+    return gclm_calibrate_ex(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_scales, d_prior_focal, d_prior_gravity,
+                             d_prior_dist, prior_dist_cols, d_cam_out, d_grav_out, d_info_out, nullptr, stream);
 }
 
 int gclm_system(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
@@ -782,9 +821,10 @@ int gclm_system(gclm_handle* h, const float* d_up, const float* d_lat, const flo
     return 0;
 }
 
-int gclm_shared_begin(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
-                      const float* d_lat_conf, int B_local, int H, int W, float* d_cam_io,
-                      float* d_grav_io, const int32_t* d_group_of_frame, int num_groups, void* stream) {
+int gclm_shared_begin_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                         const float* d_lat_conf, int B_local, int H, int W, float* d_cam_io,
+                         float* d_grav_io, const int32_t* d_group_of_frame, int num_groups, const float* d_sin_lat,
+                         void* stream) {
     if (!h) return -1;
     if (!h->cfg.shared_intrinsics) return fail(h, -2, "gclm_shared_begin: handle is not configured for shared_intrinsics");
     if (h->cfg.early_stop) return fail(h, -2, "gclm_shared_begin: early_stop needs a global decision; run with early_stop=0");
@@ -800,10 +840,12 @@ int gclm_shared_begin(gclm_handle* h, const float* d_up, const float* d_lat, con
     c.cfg = h->cfg;
     c.B = B_local; c.H = H; c.W = W; c.nchunks = h->sh.geo.nchunks;
     c.n_groups = num_groups; c.group_size = 1; c.group_of_frame = d_group_of_frame; c.iso_final = 0;
-    const bool keep_slat = B_local > 0 && slat_wanted(h, d_up, d_up_conf, d_lat_conf, h->sh.geo, false);
+    const float* given = B_local > 0 ? handed_slat(h, d_sin_lat, d_up, d_up_conf, d_lat_conf, h->sh.geo, false) : nullptr;
+    const bool keep_slat = B_local > 0 && !given && slat_wanted(h, d_up, d_up_conf, d_lat_conf, h->sh.geo, false);
     if (int rc = ensure_workspace(h, Bp, h->sh.geo.nchunks, num_groups)) return rc;
     ensure_slat(h, keep_slat ? (size_t)B_local * H * W : 0);
     h->sh.slat_ready = false;
+    h->sh.given = given;
     h->sh.up = d_up; h->sh.lat = d_lat; h->sh.upc = d_up_conf; h->sh.latc = d_lat_conf;
     h->sh.cam_io = d_cam_io; h->sh.grav_io = d_grav_io;
     h->sh.active = true;
@@ -812,6 +854,13 @@ int gclm_shared_begin(gclm_handle* h, const float* d_up, const float* d_lat, con
     ia.grav = d_grav_io;
     GCLM_HIP(h, launch_init(c, ia, s));
     return 0;
+}
+
+int gclm_shared_begin(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                      const float* d_lat_conf, int B_local, int H, int W, float* d_cam_io,
+                      float* d_grav_io, const int32_t* d_group_of_frame, int num_groups, void* stream) {
+    return gclm_shared_begin_ex(h, d_up, d_lat, d_up_conf, d_lat_conf, B_local, H, W, d_cam_io, d_grav_io, d_group_of_frame,
+                                num_groups, nullptr, stream);
 }
 
 int gclm_shared_reduce(gclm_handle* h, int step, float* d_partials, void* stream) {
@@ -824,7 +873,7 @@ int gclm_shared_reduce(gclm_handle* h, int step, float* d_partials, void* stream
     SolveCtx& c = h->ctx;
     if (c.B > 0) {
         SweepArgs a = sweep_args(h, h->sh.up, h->sh.lat, h->sh.upc, h->sh.latc, c.pb[step & 1], h->sh.geo, true, 0);
-        apply_slat(h, a, h->sh.slat_ready);
+        apply_slat(h, a, h->sh.slat_ready, h->sh.given);
         if (int rc = timed_sweep(h, a, s)) return rc;
     }
     GCLM_HIP(h, launch_shared_reduce(c, step, d_partials, s));
@@ -854,7 +903,7 @@ int gclm_shared_finish(gclm_handle* h, float* d_info_out, void* stream) {
     if (c.B == 0) return 0;
     GCLM_HIP(h, launch_prep_final(c, s));
     SweepArgs a = sweep_args(h, h->sh.up, h->sh.lat, h->sh.upc, h->sh.latc, c.pb_final, h->sh.geo, false, 0);
-    apply_slat(h, a, h->sh.slat_ready);
+    apply_slat(h, a, h->sh.slat_ready, h->sh.given);
     if (int rc = timed_sweep(h, a, s)) return rc;
     GCLM_HIP(h, launch_finalize(c, h->sh.cam_io, h->sh.grav_io, d_info_out, s));
     return 0;
@@ -924,17 +973,35 @@ int gclm_upsample_fields_multi(const float* const* d_srcs, float* const* d_dsts,
     return launch_upsample_multi(m, h, w, H, W, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -10;
 }
 
+int gclm_pack_fields_ex(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
+                        const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
+                        float* d_lat_conf, float* d_sin_lat, void* stream) {
+    if (!d_up_raw || !d_lat_raw || !d_up || !d_lat || B < 0 || H <= 0 || W <= 0) return -3;
+    if ((d_up_logconf && !d_up_conf) || (d_lat_logconf && !d_lat_conf)) return -3;
+    if (d_sin_lat) {
+        // the sixth plane is written from registers but must not land on a plane the pass still reads or writes
+        const size_t plane = (size_t)B * H * W * sizeof(float);
+        auto hits = [&](const void* p, size_t bytes) {
+            const char *a = reinterpret_cast<const char*>(d_sin_lat), *q = static_cast<const char*>(p);
+            return p && a < q + bytes && q < a + plane;
+        };
+        if (hits(d_up_raw, 2 * plane) || hits(d_up_logconf, plane) || hits(d_lat_raw, plane) || hits(d_lat_logconf, plane) ||
+            hits(d_up, 2 * plane) || hits(d_up_conf, plane) || hits(d_lat, plane) || hits(d_lat_conf, plane))
+            return -3;
+    }
+    const bool vec4 = ((size_t)H * W) % 4 == 0 && is_aligned16(d_up_raw) && is_aligned16(d_up_logconf) &&
+                      is_aligned16(d_lat_raw) && is_aligned16(d_lat_logconf) && is_aligned16(d_up) &&
+                      is_aligned16(d_up_conf) && is_aligned16(d_lat) && is_aligned16(d_lat_conf) && is_aligned16(d_sin_lat);
+    hipError_t e = launch_pack_fields(d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, vec4, d_up, d_up_conf,
+                                      d_lat, d_lat_conf, d_sin_lat, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : -10;
+}
+
 int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
                      const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
                      float* d_lat_conf, void* stream) {
-    if (!d_up_raw || !d_lat_raw || !d_up || !d_lat || B < 0 || H <= 0 || W <= 0) return -3;
-    if ((d_up_logconf && !d_up_conf) || (d_lat_logconf && !d_lat_conf)) return -3;
-    const bool vec4 = ((size_t)H * W) % 4 == 0 && is_aligned16(d_up_raw) && is_aligned16(d_up_logconf) &&
-                      is_aligned16(d_lat_raw) && is_aligned16(d_lat_logconf) && is_aligned16(d_up) &&
-                      is_aligned16(d_up_conf) && is_aligned16(d_lat) && is_aligned16(d_lat_conf);
-    hipError_t e = launch_pack_fields(d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, vec4, d_up, d_up_conf,
-                                      d_lat, d_lat_conf, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
+    return gclm_pack_fields_ex(d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, d_up, d_up_conf, d_lat, d_lat_conf,
+                               nullptr, stream);
 }
 
 int gclm_read_probe(const float* const* d_planes, int n_planes, size_t floats, void* stream) {

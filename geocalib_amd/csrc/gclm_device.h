@@ -435,6 +435,22 @@ __device__ inline void reduce_image_partials(const float* image_partials, int nc
     reduce_image_partials(image_partials, nchunks, nacc, acc, [] {});
 }
 
+// sin(x) for |x| <= pi/2 (odd minimax polynomial, |err| < 1.2e-7 in fp32): the sweep's sin(latitude_field)
+// (gclm_pass.hip: row_slat) and the sixth plane of the head epilogue (gclm_update.hip: pack_fields_kernel), one function
+// for both so that a plane written by the epilogue holds the very floats a sweep would compute.  F = float or a 2-wide
+// vector of floats (pixel pairs): written with explicit fmas and multiplies only, so v_fma_f32 per float and v_pk_fma_f32
+// per pair round alike.  t = x * x.
+template <typename F>
+__device__ __forceinline__ F sin_halfpi(F x, F t) {
+    F p = F(2.6000457182817627e-06f);
+    p = __builtin_elementwise_fma(p, t, F(-0.00019806611817330122f));
+    p = __builtin_elementwise_fma(p, t, F(0.008333017118275166f));
+    p = __builtin_elementwise_fma(p, t, F(-0.16666656732559204f));
+    return __builtin_elementwise_fma(x * t, p, x);
+}
+template <typename F>
+__device__ __forceinline__ F sin_halfpi(F x) { return sin_halfpi(x, x * x); }
+
 #pragma clang fp contract(fast)
 
 }  // namespace dev

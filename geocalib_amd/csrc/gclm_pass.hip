@@ -151,7 +151,7 @@ __device__ __forceinline__ f2 vsplat(f2, float s) { return f2{s, s}; }
 __device__ __forceinline__ float hsum(float a) { return a; }
 __device__ __forceinline__ float hsum(f2 a) { return a.x + a.y; }
 
-// sin(x) for |x| <= pi/2 (odd minimax polynomial, |err| < 1.2e-7 in fp32).  Latitudes are
+// sin(x) for |x| <= pi/2: sin_halfpi (gclm_device.h).  Latitudes are
 // asin(clamp(tanh)) outputs of the CNN head (geocalib.py:73-75) and therefore in range; the reference takes
 // torch.sin of whatever the caller passes (lm_optimizer.py:262,270), so anything outside is FOLDED into the
 // range first (fold_halfpi) -- behind a wave-uniform branch in the sweep that in-range data never takes.
@@ -167,16 +167,7 @@ __device__ __forceinline__ float fold_halfpi(float x) {
 __device__ __forceinline__ bool beyond_halfpi(float a) { return fabsf(a) > kHalfPi; }
 // the sweep tests t = x^2 (which the polynomial needs anyway) against a threshold a hair beyond (pi/2)^2
 constexpr float kHalfPiSq = 2.4675f;
-template <typename F>
-__device__ __forceinline__ F sin_halfpi(F x, F t) {          // t = x * x
-    F p = vsplat(x, 2.6000457182817627e-06f);
-    p = vfma(p, t, vsplat(x, -0.00019806611817330122f));
-    p = vfma(p, t, vsplat(x, 0.008333017118275166f));
-    p = vfma(p, t, vsplat(x, -0.16666656732559204f));
-    return vfma(x * t, p, x);
-}
-template <typename F>
-__device__ __forceinline__ F sin_halfpi(F x) { return sin_halfpi(x, x * x); }
+using dev::sin_halfpi;                                        // (gclm_device.h: shared with the head epilogue)
 
 // Scaled Huber on the squared residual x2 (lm_optimizer.py:61-87), in units of a^2 (the a^2 factor of the cost
 // is applied once per workgroup): adds confidence * cost / a^2 to `cost_acc` and returns confidence * weight.
@@ -898,7 +889,9 @@ __device__ __forceinline__ void row_slat(const RowData<VEC>& r, typename Lane<VE
 // handle's workspace; the boundary is unchanged: the caller still hands radians):
 //   SLAT = 0  compute, keep in registers (pinhole; the one-launch-per-step kernel; the stand-alone stages)
 //   SLAT = 1  compute as above AND store the plane (the first sweep of a solve; `slat_out` + `off`)
-//   SLAT = 2  the `lat` plane of this launch IS that scratch plane: the loaded value is sin(latitude) (every later sweep)
+//   SLAT = 2  the `lat` plane of this launch IS that scratch plane: the loaded value is sin(latitude) (every later sweep) --
+//             or a plane the CALLER handed (gclm_solve_ex ...: written by the head epilogue, gclm_pack_fields_ex, with the
+//             same sin_halfpi), read by every sweep of the solve from the first, also by the one-launch-per-step kernel
 // Same polynomial, same bits: a float stored and loaded is the float that was computed.
 template <int MODEL, bool HAS_UP, bool LOGF, int VEC, int SLAT = 0>
 __device__ __forceinline__ void row_math(const PBlock& P, const HuberK& hk, const typename Lane<VEC>::F (&col_u)[Lane<VEC>::kPairs],
@@ -1014,6 +1007,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const PBlock& P, 
                                            [[maybe_unused]] const LaneJob<VEC>* pj = nullptr,
                                            [[maybe_unused]] const RowData<VEC>* pre = nullptr) {
     constexpr int NACC = Layout<MODEL>::NACC;
+    static_assert(PRE == 0 || SLAT != 1, "the prefetched iterations of the one-launch-per-step kernel store no plane");
     const int tid = threadIdx.x;
     HuberK hk;
     hk.a2u = a.up_scale * a.up_scale;
@@ -1062,7 +1056,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const PBlock& P, 
 #pragma unroll
             for (int it = 0; it < PRE; ++it) {
                 if (y < y_end) {
-                    row_math<MODEL, HAS_UP, LOGF, VEC>(P, hk, col_u, col_px, y, pre[it], acc, col_zero, div_k_tiny);
+                    row_math<MODEL, HAS_UP, LOGF, VEC, SLAT>(P, hk, col_u, col_px, y, pre[it], acc, col_zero, div_k_tiny);
                     y += a.rpi;
                     off += off_step;
                 }
@@ -1147,12 +1141,15 @@ __global__ __launch_bounds__(kBlock, MIRROR ? (MODEL == GCLM_RADIAL && LOGF ? GC
 // committed, nobody sweeps, and every later launch returns at its first instruction pair.
 // The final launch (is_final) does the same with the last update, then builds the (roll, pitch, focal) block of the
 // uncertainty sweep (prep_final_kernel's job) and sweeps with it.
-template <int MODEL, bool HAS_UP, bool HAS_UPC, bool HAS_LATC, bool LOGF>
+// SLAT (row_math): 0, or 2 when the caller handed a plane of sin(latitude_field) (gclm_solve_ex / gclm_calibrate_ex): `a.lat`
+// is then that plane, prefetched and read by every launch of the solve in place of the radians (five planes only).
+template <int MODEL, bool HAS_UP, bool HAS_UPC, bool HAS_LATC, bool LOGF, int SLAT = 0>
 __global__ __launch_bounds__(kBlock) void fused_step_kernel(const SweepArgs a, const FusedArgs f) {
     using namespace dev;
     constexpr int PM = Layout<MODEL>::PM, NACC = Layout<MODEL>::NACC;
     const SolveCtx& c = f.c;
     const gclm_config& cfg = c.cfg;
+    static_assert(SLAT == 0 || (SLAT == 2 && HAS_UP && HAS_UPC && HAS_LATC), "a handed plane: five-plane launches only");
     const int b = blockIdx.y, chunk = blockIdx.x, step = f.step;      // this launch sweeps theta_step (final: theta_final)
     GCLM_T(step, 0);
     __shared__ PBlock Ps;
@@ -1186,7 +1183,7 @@ __global__ __launch_bounds__(kBlock) void fused_step_kernel(const SweepArgs a, c
         const size_t N = (size_t)a.H * a.W;
         const float* upx = HAS_UP ? a.up + (size_t)b * 2 * N : nullptr;
         const float* upy = HAS_UP ? upx + N : nullptr;
-        const float* lat = a.lat + (size_t)b * N;
+        const float* lat = a.lat + (size_t)b * N;                      // (SLAT == 2: the plane of sin(latitude))
         const float* upc = HAS_UPC ? a.upc + (size_t)b * N : nullptr;
         const float* latc = HAS_LATC ? a.latc + (size_t)b * N : nullptr;
 #pragma unroll
@@ -1331,7 +1328,7 @@ __global__ __launch_bounds__(kBlock) void fused_step_kernel(const SweepArgs a, c
         P.T20 = uni(Ps.T20); P.T21 = uni(Ps.T21); P.wfx = uni(Ps.wfx); P.wfy = uni(Ps.wfy);
         P.k2 = uni(Ps.k2); P.pad0 = P.pad1 = P.pad2 = 0.f;
     }
-    sweep_body<MODEL, HAS_UP, HAS_UPC, HAS_LATC, LOGF, 4, kFusedPre>(a, P, b, chunk, &pj, pre);
+    sweep_body<MODEL, HAS_UP, HAS_UPC, HAS_LATC, LOGF, 4, kFusedPre, SLAT>(a, P, b, chunk, &pj, pre);
     GCLM_T(step, 6);
 }
 
@@ -1495,6 +1492,13 @@ hipError_t dispatch_fused(const SweepArgs& a, const FusedArgs& f, hipStream_t s)
     const dim3 grid(a.nchunks, a.B), block(kBlock);
     const bool up = a.up != nullptr, upc = up && a.upc != nullptr, latc = a.latc != nullptr;
     const bool logf = a.log_focal != 0;
+    // a plane of sin(latitude) handed by the caller (gclm_api.hip: handed_slat): the five-plane launches read it as `lat`
+    if (a.slat_mode != 0) {
+        if (a.slat_mode != 2 || !(up && upc && latc) || a.slat == nullptr || a.lat != a.slat) return hipErrorInvalidValue;
+        if (logf) hipLaunchKernelGGL((fused_step_kernel<MODEL, true, true, true, true, 2>), grid, block, 0, s, a, f);
+        else hipLaunchKernelGGL((fused_step_kernel<MODEL, true, true, true, false, 2>), grid, block, 0, s, a, f);
+        return hipGetLastError();
+    }
 #define GCLM_LAUNCH(U, UC, LC)                                                                               \
     do {                                                                                                     \
         if (logf) hipLaunchKernelGGL((fused_step_kernel<MODEL, U, UC, LC, true>), grid, block, 0, s, a, f);  \

@@ -579,11 +579,15 @@ __global__ void synth_kernel(int model, uint64_t seed, int64_t first, int B, int
 // UpDecoder / LatitudeDecoder epilogues (geocalib.py:57,73-75) fused into ONE pass that writes the five
 // planes the sweep reads: up = normalize(raw, dim=1), latitude = asin(clamp(tanh(raw), +-(1-1e-5))),
 // confidences = sigmoid(log-confidence).  Eager PyTorch runs 8 elementwise kernels and ~18 plane passes.
+// slat (gclm_pack_fields_ex; NULL: not written): a sixth plane, sin of the latitude just written, by the sweep's own
+// polynomial (dev::sin_halfpi) -- the floats a sweep would compute from `lat`, so a solve that reads this plane in place of
+// the radians gives the same bits.  The packed latitude lies within +-asin(1 - 1e-5) < pi/2: the range fold the sweep keeps
+// for a caller's own radians (gclm_pass.hip: row_slat) never fires on it and is not needed here.
 template <int VEC>
 __global__ void pack_fields_kernel(const float* __restrict__ up_raw, const float* __restrict__ up_lc,
                                    const float* __restrict__ lat_raw, const float* __restrict__ lat_lc, int B,
                                    size_t N, float* __restrict__ up, float* __restrict__ upc,
-                                   float* __restrict__ lat, float* __restrict__ latc) {
+                                   float* __restrict__ lat, float* __restrict__ latc, float* __restrict__ slat) {
     const size_t units = N / VEC;
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
         const float* ux = up_raw + (size_t)b * 2 * N;
@@ -591,7 +595,7 @@ __global__ void pack_fields_kernel(const float* __restrict__ up_raw, const float
         float* ox = up + (size_t)b * 2 * N;
         float* oy = ox + N;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < units; i += (size_t)gridDim.x * blockDim.x) {
-            float vx[VEC], vy[VEC], vl[VEC], c1[VEC], c2[VEC];
+            float vx[VEC], vy[VEC], vl[VEC], c1[VEC], c2[VEC], sl[VEC];
             if constexpr (VEC == 4) {
                 // every byte is read once and written once: non-temporal both ways (+4 ... 8 % over plain float4 accesses,
                 // profiles/archive/r05_pack_bench.log)
@@ -613,6 +617,7 @@ __global__ void pack_fields_kernel(const float* __restrict__ up_raw, const float
                 const float n = fmaxf(sqrtf(vx[k] * vx[k] + vy[k] * vy[k]), 1e-12f);     // F.normalize eps
                 vx[k] /= n; vy[k] /= n;
                 vl[k] = asinf(fminf(fmaxf(tanhf(vl[k]), -1.0f + 1e-5f), 1.0f - 1e-5f));
+                if (slat) sl[k] = dev::sin_halfpi(vl[k]);
                 if (up_lc) c1[k] = 1.0f / (1.0f + expf(-c1[k]));
                 if (lat_lc) c2[k] = 1.0f / (1.0f + expf(-c2[k]));
             }
@@ -624,10 +629,12 @@ __global__ void pack_fields_kernel(const float* __restrict__ up_raw, const float
                 st4(ox, i, vx); st4(oy, i, vy); st4(lat + (size_t)b * N, i, vl);
                 if (up_lc) st4(upc + (size_t)b * N, i, c1);
                 if (lat_lc) st4(latc + (size_t)b * N, i, c2);
+                if (slat) st4(slat + (size_t)b * N, i, sl);
             } else {
                 ox[i] = vx[0]; oy[i] = vy[0]; lat[(size_t)b * N + i] = vl[0];
                 if (up_lc) upc[(size_t)b * N + i] = c1[0];
                 if (lat_lc) latc[(size_t)b * N + i] = c2[0];
+                if (slat) slat[(size_t)b * N + i] = sl[0];
             }
         }
     }
@@ -1184,15 +1191,15 @@ hipError_t launch_upsample(const float* src, int planes, int h, int w, int H, in
 
 hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const float* lat_raw, const float* lat_lc,
                               int B, int H, int W, bool vec4, float* up, float* upc, float* lat, float* latc,
-                              hipStream_t s) {
+                              float* slat, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     const size_t N = (size_t)H * W;
     const size_t units = vec4 ? N / 4 : N;
     // one unit per thread and image where the image allows (one pass: +3 % over 128 blocks walking a grid-stride loop)
     const int bx = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
     const dim3 grid(bx, B < 4096 ? B : 4096), block(256);
-    if (vec4) hipLaunchKernelGGL(pack_fields_kernel<4>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc);
-    else hipLaunchKernelGGL(pack_fields_kernel<1>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc);
+    if (vec4) hipLaunchKernelGGL(pack_fields_kernel<4>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc, slat);
+    else hipLaunchKernelGGL(pack_fields_kernel<1>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc, slat);
     return hipGetLastError();
 }
 

@@ -7,7 +7,8 @@ Replaces the tail of the reference's UpDecoder / LatitudeDecoder (geocalib/geoca
     latitude_field      = asin(clamp(tanh(lat_raw), -1 + 1e-5, 1 - 1e-5))
     latitude_confidence = sigmoid(lat_log_confidence)
 
-and writes the five planes in the layout LMOptimizer reads (eager PyTorch: 8 kernels, ~18 plane passes)."""
+and writes the five planes in the layout LMOptimizer reads (eager PyTorch: 8 kernels, ~18 plane passes) -- and, on request,
+a sixth: sin(latitude_field), which the LM solve reads in place of the radians (gclm_pack_fields_ex)."""
 from typing import Dict, Optional
 
 import torch
@@ -35,9 +36,15 @@ def _on_device(device):
 
 
 def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: Optional[torch.Tensor] = None,
-                lat_log_confidence: Optional[torch.Tensor] = None, inplace: bool = False) -> Dict[str, torch.Tensor]:
+                lat_log_confidence: Optional[torch.Tensor] = None, inplace: bool = False,
+                sin_latitude: bool = False) -> Dict[str, torch.Tensor]:
     """up_raw (B,2,H,W), lat_raw (B,1,H,W), log-confidences (B,H,W) or (B,1,H,W): raw head outputs on a HIP device.
-    Returns the dict `LMOptimizer.forward` consumes."""
+    Returns the dict `LMOptimizer.forward` consumes.
+
+    `sin_latitude`: the dict also holds "sin_latitude" (B,1,H,W), sin of "latitude_field" written by the same launch with
+    the solve's own polynomial.  LMOptimizer reads it in place of the radians where its sweeps can (include/gclm.h:
+    gclm_solve_ex) -- same results bit for bit, no per-sweep sin and no library-owned scratch plane.  The key names no
+    field / confidence / uncertainty, so GeoCalib._post_process neither resizes nor returns it."""
     for t in (up_raw, lat_raw):
         if not t.is_cuda:
             raise RuntimeError("geocalib_amd.pack_fields needs HIP device tensors (no CPU fallback)")
@@ -54,17 +61,20 @@ def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: 
     up, lat = out_like(up_raw), out_like(lat_raw)
     upc = None if ulc is None else out_like(ulc).view(B, H, W)
     latc = None if llc is None else out_like(llc).view(B, H, W)
+    slat = torch.empty_like(lat_raw) if sin_latitude else None       # (never in place: a plane of its own)
     p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(lat_raw.device):
-        rc = _lib.load().gclm_pack_fields(p(up_raw), p(ulc), p(lat_raw), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc),
-                                          torch.cuda.current_stream(lat_raw.device).cuda_stream)
+        rc = _lib.load().gclm_pack_fields_ex(p(up_raw), p(ulc), p(lat_raw), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc),
+                                             p(slat), torch.cuda.current_stream(lat_raw.device).cuda_stream)
     if rc != 0:
-        raise _lib.GclmError(f"gclm_pack_fields failed ({rc})")
+        raise _lib.GclmError(f"gclm_pack_fields_ex failed ({rc})")
     out = {"up_field": up, "latitude_field": lat}
     if upc is not None:
         out["up_confidence"] = upc
     if latc is not None:
         out["latitude_confidence"] = latc
+    if slat is not None:
+        out["sin_latitude"] = slat
     return out
 
 

@@ -345,10 +345,23 @@ class LMOptimizer(nn.Module):
             assert c is None or c.numel() == B * H * W, c.shape
         return up, lat, upc, latc, (B, H, W)
 
+    @staticmethod
+    def _sin_lat(data, lat):
+        """data["sin_latitude"] (fields.pack_fields(..., sin_latitude=True)): sin(latitude_field), which the solve reads in
+        place of the radians where it can (include/gclm.h: gclm_solve_ex), or None."""
+        if "sin_latitude" not in data:
+            return None
+        t = _dev_f32(data["sin_latitude"], "sin_latitude")
+        if t.shape != lat.shape:
+            raise ValueError(f"geocalib_amd: `sin_latitude` {tuple(t.shape)} must have the shape of `latitude_field` "
+                             f"{tuple(lat.shape)}")
+        return t
+
     def optimize(self, data: Dict[str, torch.Tensor], camera_opt: BaseCamera,
                  gravity_opt: Gravity) -> Tuple[BaseCamera, Gravity, Dict[str, torch.Tensor]]:
         """All LM steps + final costs + uncertainty on the device (reference: lm_optimizer.py:551-644)."""
         up, lat, upc, latc, (B, H, W) = self._fields(data)
+        slat = self._sin_lat(data, lat)
         device = lat.device
         h = self._handle(device)
         cam = _dev_f32(camera_opt._data, "camera").clone()
@@ -356,9 +369,9 @@ class LMOptimizer(nn.Module):
         info = torch.empty((B, _lib.INFO_STRIDE), dtype=torch.float32, device=device)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            rc = _lib.load().gclm_solve(h.ptr, self._ptr(up), self._ptr(lat), self._ptr(upc), self._ptr(latc),
-                                        B, H, W, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), stream)
-        _lib.check(rc, h.ptr, "gclm_solve")
+            rc = _lib.load().gclm_solve_ex(h.ptr, self._ptr(up), self._ptr(lat), self._ptr(upc), self._ptr(latc),
+                                           B, H, W, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), self._ptr(slat), stream)
+        _lib.check(rc, h.ptr, "gclm_solve_ex")
         self._last_raw = (cam, grav, info)     # packed device results (parallel.calibrate_sharded)
         return camera_opt.__class__(cam), _unit_gravity(grav), self._unpack_info(info, up is not None)
 
@@ -436,7 +449,7 @@ class LMOptimizer(nn.Module):
             logger.warning("geocalib_amd.LMOptimizer: a batch of %d images is solved in slices of %d; with early_stop=True "
                            "the batch-global stop is evaluated per slice (pass early_stop=False for slice-independent "
                            "results)", B, self._MAX_CALL)
-        per_image = ("up_field", "latitude_field", "up_confidence", "latitude_confidence", "prior_focal",
+        per_image = ("up_field", "latitude_field", "up_confidence", "latitude_confidence", "sin_latitude", "prior_focal",
                      "prior_gravity", "prior_dist")
         cams, gravs, infos, raws = [], [], [], []
         for lo in range(0, B, self._MAX_CALL):
@@ -453,6 +466,7 @@ class LMOptimizer(nn.Module):
         up, lat, upc, latc, (B, H, W) = self._fields(data)
         if B > self._MAX_CALL:
             return self._calibrate_chunked(data, B)
+        slat = self._sin_lat(data, lat)
         device = lat.device
         stream = _raw_stream(device)      # looked up once: the handle's key and the launch stream
         h = self._handle(device, stream)
@@ -480,12 +494,13 @@ class LMOptimizer(nn.Module):
         P = self._ptr           # (the library switches to the handle's device itself: no torch.cuda.device() context)
         n_over = self._overlap_parts(B, H, W, h, lambda: all(t is None or t.data_ptr() % 16 == 0 for t in (up, lat, upc, latc)))
         if n_over > 1:
-            self._calibrate_overlapped(n_over, device, (up, lat, upc, latc), (B, H, W), scales, (pf, pg, pd), nd, (cam, grav, info))
+            self._calibrate_overlapped(n_over, device, (up, lat, upc, latc, slat), (B, H, W), scales, (pf, pg, pd), nd,
+                                       (cam, grav, info))
         else:
-            rc = _lib.load().gclm_calibrate(h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg),
-                                            P(pd), nd, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), stream)
+            rc = _lib.load().gclm_calibrate_ex(h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg),
+                                               P(pd), nd, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), stream)
             if rc != 0:
-                _lib.check(rc, h.ptr, "gclm_calibrate")
+                _lib.check(rc, h.ptr, "gclm_calibrate_ex")
         self._last_raw = (cam, grav, info)
         return self.camera_model(cam), _unit_gravity(grav), self._unpack_info(info, up is not None)
 
@@ -565,13 +580,13 @@ class LMOptimizer(nn.Module):
             s = streams[i]
             s.wait_event(fork)                              # the caller's stream produced the fields
             h = self._handle(device, s.cuda_stream)
-            up, lat, upc, latc = (part(t, lo, hi) for t in fields)
+            up, lat, upc, latc, slat = (part(t, lo, hi) for t in fields)
             pf, pg, pd = (part(t, lo, hi) for t in priors)
             cam, grav, info = (t[lo:hi] for t in outs)
-            rc = lib.gclm_calibrate(h.ptr, P(up), P(lat), P(upc), P(latc), hi - lo, H, W, P(scales), P(pf), P(pg), P(pd), nd,
-                                    cam.data_ptr(), grav.data_ptr(), info.data_ptr(), s.cuda_stream)
+            rc = lib.gclm_calibrate_ex(h.ptr, P(up), P(lat), P(upc), P(latc), hi - lo, H, W, P(scales), P(pf), P(pg), P(pd), nd,
+                                       cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), s.cuda_stream)
             if rc != 0:
-                _lib.check(rc, h.ptr, "gclm_calibrate")
+                _lib.check(rc, h.ptr, "gclm_calibrate_ex")
             handles.append(h)
             cur.wait_event(s.record_event())                # join: whatever follows on the caller's stream sees the results
         # infos["stop_at"] is ONE number for the whole batch (the first step after which every image's cost was close,

@@ -298,6 +298,7 @@ class SharedIntrinsicsSplit:
             cam0, grav0 = get_trivial_estimation(local_data, opt.camera_model)
             opt.setup_optimization_and_priors(local_data, shared_intrinsics=True)
             up, lat, upc, latc, (B, H, W) = opt._fields(local_data)
+            slat = opt._sin_lat(local_data, lat)
             dev = lat.device
             h = opt._handle(dev)
             cam = _dev_f32(cam0._data, "camera").clone()
@@ -322,9 +323,9 @@ class SharedIntrinsicsSplit:
             with torch.cuda.device(dev):
                 s = torch.cuda.current_stream(dev).cuda_stream
                 P = opt._ptr
-                _lib.check(lib.gclm_shared_begin(h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(),
-                                                 grav.data_ptr(), gof.data_ptr(), self.num_groups, s), h.ptr,
-                           "gclm_shared_begin")
+                _lib.check(lib.gclm_shared_begin_ex(h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(),
+                                                    grav.data_ptr(), gof.data_ptr(), self.num_groups, P(slat), s), h.ptr,
+                           "gclm_shared_begin_ex")
                 for step in range(opt.num_steps):
                     _lib.check(lib.gclm_shared_reduce(h.ptr, step, partials.data_ptr(), s), h.ptr, "gclm_shared_reduce")
                     if self.comm is not None or multi:

@@ -43,7 +43,9 @@ extern "C" {
  * empty batch (B = 0, NULL fields) is accepted by gclm_solve / gclm_calibrate; 500 = round 5: gclm_set_slat_plane and gclm_plan_cut added;
  * 600 = round 6: gclm_set_slat_plane_limit, gclm_slat_plane_bytes, gclm_release_workspace and gclm_read_probe added, the
  * scratch plane became an optional allocation of its own, gclm_merge_stop_at skips empty parts; 610 = round 6: gclm_set_row_pairs
- * added -- radial / simple_divisional batches walk row pairs by default, results equal the one-row walk's to summation order).  gclm_create refuses a gclm_config whose first two fields do not
+ * added -- radial / simple_divisional batches walk row pairs by default, results equal the one-row walk's to summation order;
+ * additive within 610: gclm_pack_fields_ex, gclm_solve_ex, gclm_calibrate_ex and gclm_shared_begin_ex added -- the head
+ * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -177,6 +179,33 @@ int gclm_calibrate(gclm_handle* h, const float* d_up, const float* d_lat, const 
                    int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out, void* stream);
 
 /*
+ * gclm_solve / gclm_calibrate with one more argument, d_sin_lat: (B,1,H,W) float32 holding sin(latitude_field), laid out
+ * like d_lat -- the sixth plane of gclm_pack_fields_ex, or the caller's own sin of d_lat -- or NULL (= gclm_solve /
+ * gclm_calibrate exactly; those two are these with NULL).  d_lat stays required: the plane is an optional accelerator.
+ * Each of the num_steps + 1 sweeps of a solve takes sin(latitude_field) again (lm_optimizer.py:262,270); with the plane
+ * handed, the sweeps that can read it do so IN PLACE OF d_lat, from the first sweep of the solve to the final uncertainty
+ * sweep, and the library holds no scratch plane for the solve (see gclm_set_slat_plane: none is allocated; one the handle
+ * already holds is kept, unused).  Where the plane is read:
+ *   - the five-plane (both confidences) 16-byte-aligned sweeps of simple_radial, radial and simple_divisional, on the
+ *     one-row walk and on row pairs (gclm_set_row_pairs);
+ *   - the same sweeps in a shared-intrinsics session (gclm_shared_begin_ex ... gclm_shared_finish);
+ *   - the five-plane one-launch-per-step path (gclm_set_fused_steps; single images), for all four camera models.
+ * Everywhere else the plane is ignored and d_lat is read as by gclm_solve: pinhole's batch sweeps (memory-bound), the scalar
+ * path (W % 4 != 0 or a field plane not 16-byte aligned), four-plane and latitude-only sweeps, and a d_sin_lat that is not
+ * 16-byte aligned while the other planes are.  The initial estimate (cfg.heuristic_init) always reads d_lat.
+ * The result of a solve that reads the plane is that of a solve from d_lat bit for bit when the plane holds the library's
+ * own sin of d_lat (gclm_pack_fields_ex); a caller's own sin (e.g. torch.sin) may differ in the last bit per pixel.
+ */
+int gclm_solve_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                  const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
+                  float* d_info_out, const float* d_sin_lat, void* stream);
+int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                      const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                      const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                      int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
+                      const float* d_sin_lat, void* stream);
+
+/*
  * One fused sweep at fixed parameters: calculate_residuals + calculate_costs + setup_system
  * (lm_optimizer.py:248-315,387-461).  as_rpf selects the (roll, pitch, focal) parametrisation used
  * by estimate_uncertainty (:481-483).  Outputs, per image: d_cost (B,2) mean up / latitude Huber cost,
@@ -200,6 +229,12 @@ int gclm_shared_begin(gclm_handle* h, const float* d_up, const float* d_lat, con
                       const float* d_lat_conf, int B_local, int H, int W, float* d_cam_io,
                       float* d_grav_io, const int32_t* d_group_of_frame /* (B_local), non-decreasing */,
                       int num_groups, void* stream);
+/* gclm_shared_begin with a plane of sin(latitude_field) (NULL = gclm_shared_begin), read by the session's sweeps under the
+ * rule of gclm_solve_ex.  Like the field pointers, d_sin_lat must stay valid until gclm_shared_finish. */
+int gclm_shared_begin_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                         const float* d_lat_conf, int B_local, int H, int W, float* d_cam_io,
+                         float* d_grav_io, const int32_t* d_group_of_frame /* (B_local), non-decreasing */,
+                         int num_groups, const float* d_sin_lat, void* stream);
 int gclm_shared_reduce(gclm_handle* h, int step, float* d_partials, void* stream);
 int gclm_shared_apply(gclm_handle* h, int step, const float* d_partials, void* stream);
 int gclm_shared_finish(gclm_handle* h, float* d_info_out, void* stream);
@@ -215,6 +250,14 @@ int gclm_shared_finish(gclm_handle* h, float* d_info_out, void* stream);
 int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
                      const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
                      float* d_lat_conf, void* stream);
+/* The same pass (the five planes bit-identical to gclm_pack_fields', which is this with NULL), writing, when d_sin_lat
+ * (B,1,H,W) is not NULL, a sixth plane in the same launch: sin of the latitude it has just written, by the polynomial the
+ * sweeps use -- the plane gclm_solve_ex / gclm_calibrate_ex / gclm_shared_begin_ex read in place of d_lat, with the results
+ * of a solve from d_lat bit for bit.  d_sin_lat must not overlap any other plane of the call (-3).  A d_sin_lat that is not
+ * 16-byte aligned sends the pass to its scalar path (as any other unaligned plane does). */
+int gclm_pack_fields_ex(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
+                        const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
+                        float* d_lat_conf, float* d_sin_lat /* (B,1,H,W) or NULL */, void* stream);
 
 /*
  * The step AFTER the path: GeoCalib._post_process (geocalib/extractor.py:51-69) resizes the fields and confidences
@@ -393,7 +436,8 @@ int gclm_plan_cut(const gclm_handle* h, int B, int H, int W, int aligned16, int*
  * large enough for -- gclm_release_workspace drops it).  A refused size is remembered until the limit or the mode is set again,
  * so a serving loop does not pay a failing allocation per call.  Only the core workspace failing to allocate is an error
  * (-10).  A batch solved as n parts by n handles (LMOptimizer.overlap_streams) holds n planes of B / n images each: one
- * plane's worth in total. */
+ * plane's worth in total.
+ * A solve handed the caller's plane (gclm_solve_ex ...) where its sweeps read it needs no scratch plane, in every mode. */
 int gclm_set_slat_plane(gclm_handle* h, int mode);
 int gclm_set_slat_plane_limit(gclm_handle* h, size_t max_bytes);
 
