@@ -5,6 +5,7 @@
 (1) `GeoCalib.optimizer` (geocalib/geocalib.py:106,119): any code that calls `optimizer(data) -> dict` with the CNN's fields.
 (2) `GeoCalib.calibrate(img, camera_model=..., priors=..., shared_intrinsics=...)` (geocalib/extractor.py:72-127) with a
     caller-supplied field network.
+(3) `camera.undistort_image(image)` (geocalib/camera.py:396-412), which the reference's Gradio app calls right after calibrate().
 
 The CNN is out of scope of this package, so a stand-in "network" renders the perspective fields of a known camera
 (gclm_synth_fields) at the resolution the reference's network would see; with the upstream package installed, pass its
@@ -45,3 +46,8 @@ print("calibrate()      : image size", cam.size[0].tolist(), " focal", round(cam
 print("                   roll / pitch [deg]", tuple(round(x, 2) for x in torch.rad2deg(grav.rp)[0].tolist()), " keys:", sorted(k for k in res if "uncertainty" in k))
 res = model.calibrate(img, camera_model="pinhole", priors={"focal": torch.tensor(900.0, device=dev)})
 print("with a focal prior: focal", round(res["camera"].f[0, 1].item(), 1))
+
+# (3) remove the lens distortion: calibrate with a distortion model, then resample the image on the device
+res = model.calibrate(img, camera_model="radial")
+rect = res["camera"].undistort_image(img[None])                   # (1, 3, H, W): one gclm_undistort_image launch
+print("undistort_image(): k1, k2", [round(v, 4) for v in res["camera"].dist[0].tolist()], " output", tuple(rect.shape))

@@ -6,7 +6,8 @@ SimpleRadial :565, Radial :663, SimpleDivisional :789, camera_models :945): a `(
 (un)distortion maps.  Every model here is *radial*: distort(p) = p * s(r2) and
 undistort(p) = p * t(r2) with r2 = |p|^2, so a model only supplies s, t and their derivatives
 and all Jacobians follow in closed form (the reference falls back to torch.func.jacfwd for the
-generic cases).  Host-side torch code: the per-pixel hot path is csrc/gclm_pass.hip.
+generic cases).  Host-side torch code: the per-pixel hot paths are csrc/gclm_pass.hip and, for undistort_image,
+csrc/gclm_image.hip.
 """
 from typing import Dict, Tuple, Union
 
@@ -314,6 +315,38 @@ class BaseCamera(TensorWrapper):
         if wrt == "f":
             return self.J_undistort(self.normalize(p2d), "pts") @ self.J_normalize(p2d, wrt)
         raise ValueError(f"Unknown wrt: {wrt}")
+
+    @autocast
+    def undistort_image(self, img: torch.Tensor) -> torch.Tensor:
+        """Remove the distortion from `img` (B, C, Hin, Win): (B, C, H, W) with (W, H) = self.size truncated, as the
+        reference's camera.py:396-412, which asserts B = 1.  Here the camera batch is 1 (shared by every image) or B (one
+        camera per image, all of one size).  Output pixel (x, y) samples the image bilinearly at
+        denormalize(distort(normalize(x, y))), scaled by (Win - 1) / (W - 1), (Hin - 1) / (H - 1), with zero padding
+        (F.grid_sample(bilinear, zeros, align_corners=True)).
+
+        A float32 image on a HIP device runs one gclm_undistort_image launch (not differentiable); a non-finite
+        coordinate gives 0 there.  Every other input (CPU, other dtypes) runs the reference's torch composition.  The two
+        differ for simple_divisional at small |k1 r2|: the torch path keeps the reference's cancelling float32 form of the
+        distort scale, the HIP path evaluates the identical 2 / (1 + sqrt(1 - 4 k1 r2)), held to float64."""
+        assert img.dim() == 4, f"expected a (B, C, H, W) image, got {tuple(img.shape)}"
+        data = self._data.reshape(-1, self._data.shape[-1])
+        n, B = data.shape[0], img.shape[0]
+        assert n in (1, B), f"camera batch {n} must be 1 or the image batch {B}"
+        if n > 1:
+            assert data[:, 0].unique().shape[0] == 1, "All images must have the same width."
+            assert data[:, 1].unique().shape[0] == 1, "All images must have the same height."
+        W, H = (int(v) for v in data[0, :2].int().tolist())
+        if img.is_cuda and img.dtype == torch.float32:
+            from .fields import undistort_image
+            return undistort_image(self.name(), data, img, (H, W))
+        cam = self.__class__(data)
+        x, y = torch.meshgrid(torch.arange(0, W), torch.arange(0, H), indexing="xy")
+        coords = torch.stack((x, y), dim=-1).reshape(-1, 2).to(device=self.device, dtype=self.dtype)
+        p3d, _ = cam.pinhole().image2world(coords.expand(n, -1, -1))
+        p2d, _ = cam.world2image(p3d)
+        grid = p2d.reshape(n, H, W, 2)
+        grid = 2.0 * grid / torch.tensor([W - 1, H - 1]).to(grid) - 1
+        return F.grid_sample(img, grid.expand(B, -1, -1, -1).to(img), align_corners=True)
 
     def __repr__(self):
         return f"{self.__class__.__name__} {self.shape} {self.dtype} {self.device}"

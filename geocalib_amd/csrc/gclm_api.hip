@@ -1004,6 +1004,21 @@ int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const flo
                                nullptr, stream);
 }
 
+int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin, int Win,
+                         int H, int W, float* d_dst, void* stream) {
+    // every check runs before the first HIP call
+    if (!d_cam || !d_src || !d_dst || B < 1 || C < 1 || Hin < 1 || Win < 1 || H < 2 || W < 2) return -3;
+    if ((cam_batch != 1 && cam_batch != B) || camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL || B > 65535)
+        return -3;
+    if ((int64_t)H * W > INT32_MAX) return -3;
+    const size_t in_bytes = (size_t)B * C * Hin * Win * sizeof(float), out_bytes = (size_t)B * C * H * W * sizeof(float);
+    const char *a = reinterpret_cast<const char*>(d_src), *o = reinterpret_cast<const char*>(d_dst);
+    if (o < a + in_bytes && a < o + out_bytes) return -3;
+    hipError_t e = launch_undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, d_dst,
+                                          static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : -10;
+}
+
 int gclm_read_probe(const float* const* d_planes, int n_planes, size_t floats, void* stream) {
     if (!d_planes || n_planes < 1 || n_planes > 8 || floats % 4 != 0) return -3;
     for (int k = 0; k < n_planes; ++k)

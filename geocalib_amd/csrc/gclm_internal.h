@@ -1,6 +1,6 @@
-// gclm_internal.h -- shared declarations of the three translation units of libgeocalib_hip.so
+// gclm_internal.h -- shared declarations of the translation units of libgeocalib_hip.so
 // (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update,
-//  gclm_api.hip: C ABI and launch sequence).  gfx950 only.
+//  gclm_api.hip: C ABI and launch sequence, gclm_image.hip: image undistortion).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -190,6 +190,8 @@ hipError_t launch_upsample_multi(const UpsampleMulti& m, int h, int w, int H, in
 hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const float* lat_raw, const float* lat_lc,
                               int B, int H, int W, bool vec4, float* up, float* upc, float* lat, float* latc,
                               float* slat /* or nullptr */, hipStream_t s);
+hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,
+                                  int Win, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_read_probe(const float* const* planes, int n, size_t floats, hipStream_t s);
 hipError_t launch_synth(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
                         float sigma, int group_size, int run, int run_stride, float* up, float* lat, float* upc, float* latc, float* gt_cam,

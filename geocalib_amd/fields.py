@@ -160,3 +160,28 @@ def fastest_placement(allocate, solve, tries: int = 3, keep_first: bool = False)
         times.append(best_ms)
     best = min(range(tries), key=times.__getitem__)
     return (cands[best], times, cands[0]) if keep_first else (cands[best], times)
+
+
+def undistort_image(camera_model: str, cam: torch.Tensor, img: torch.Tensor, size) -> torch.Tensor:
+    """gclm_undistort_image: `img` (B, C, Hin, Win) float32 on a HIP device, resampled to `size` = (H, W) at the distorted
+    position of every output pixel of `cam` ((1, 8) shared by the batch, or (B, 8)), in one launch per 65 535 images on
+    torch's current stream.  BaseCamera.undistort_image is the public entry; not differentiable."""
+    if not img.is_cuda or img.dtype != torch.float32:
+        raise RuntimeError("geocalib_amd.undistort_image needs a float32 HIP device tensor (no CPU fallback)")
+    H, W = int(size[0]), int(size[1])
+    src = img.detach().contiguous()
+    cam = cam.detach().to(device=src.device, dtype=torch.float32).reshape(-1, 8).contiguous()
+    B, C, Hin, Win = src.shape
+    dst = src.new_empty((B, C, H, W))
+    if dst.numel() == 0:
+        return dst
+    lib = _lib.load()
+    with _on_device(src.device):
+        for b0 in range(0, B, 65535):
+            n = min(65535, B - b0)
+            c = cam if cam.shape[0] == 1 else cam[b0:b0 + n]
+            rc = lib.gclm_undistort_image(_lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], src[b0].data_ptr(), n, C,
+                                          Hin, Win, H, W, dst[b0].data_ptr(), _raw_stream(src.device))
+            if rc != 0:
+                raise _lib.GclmError(f"gclm_undistort_image failed ({rc})")
+    return dst

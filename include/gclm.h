@@ -45,7 +45,8 @@ extern "C" {
  * scratch plane became an optional allocation of its own, gclm_merge_stop_at skips empty parts; 610 = round 6: gclm_set_row_pairs
  * added -- radial / simple_divisional batches walk row pairs by default, results equal the one-row walk's to summation order;
  * additive within 610: gclm_pack_fields_ex, gclm_solve_ex, gclm_calibrate_ex and gclm_shared_begin_ex added -- the head
- * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged).  gclm_create refuses a gclm_config whose first two fields do not
+ * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged; gclm_undistort_image
+ * added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -273,6 +274,29 @@ int gclm_upsample_fields(const float* d_src, int planes, int h, int w, int H, in
  * single-image calibrate() pays one launch instead of four). */
 int gclm_upsample_fields_multi(const float* const* d_srcs, float* const* d_dsts, const int* planes, int n_tensors, int h, int w,
                                int H, int W, void* stream);
+
+/*
+ * BaseCamera.undistort_image (geocalib/camera.py:396-412) for a batch, in one pass: d_dst (B, C, H, W) is d_src
+ * (B, C, Hin, Win) resampled at the distorted position of every output pixel, float32 NCHW.  d_cam is (cam_batch, 8)
+ * {w, h, fx, fy, cx, cy, k1, k2} in device memory (read by the kernel; the w, h entries are not read: H, W are the output
+ * size); cam_batch = 1 shares one camera over the batch, cam_batch = B gives each image its own.  For output pixel (x, y),
+ * integer pixel centres, no half-pixel offset:
+ *   u = (x - cx) / fx,  v = (y - cy) / fy,  r2 = u^2 + v^2,  s = the model's distort scale s(r2)
+ *   ix = ((x - cx) s + cx) (Win - 1) / (W - 1),   iy = ((y - cy) s + cy) (Hin - 1) / (H - 1)
+ * which is the reference's denormalize(distort(normalize(x))) then grid_sample's align_corners unnormalisation, in exact
+ * arithmetic.  s: pinhole 1; simple_radial 1 + k1 r2; radial 1 + k1 r2 + k2 r2^2; simple_divisional
+ * (1 - sqrt(max(0, 1 - 4 k1 r2))) / (2 k1 r2), 1 where k1 r2 = 0 -- evaluated as 2 / (1 + sqrt(t)) where t = 1 - 4 k1 r2 > 0
+ * and 1 / (2 k1 r2) elsewhere, which does not cancel in float32 (the reference's form, which the LM solve keeps on purpose,
+ * is off by 1.3 % at |k1 r2| = 1e-6).  Bilinear with zero padding, as F.grid_sample(bilinear, zeros, align_corners=True):
+ * each of the four taps contributes only if it lies in [0, Win) x [0, Hin).  A non-finite coordinate (a NaN or inf in
+ * the camera) contributes nothing: that output pixel is 0.  With s = 1, an exactly representable c and Win = W, H = Hin,
+ * the output is a bit-exact copy.
+ * Returns -3 (before any HIP call) for a NULL pointer, B, C, Hin or Win < 1, H or W < 2, H * W > 2^31 - 1,
+ * cam_batch not 1 or B, a camera_model outside 0..3, B > 65535, or a destination that overlaps the source; -10 if the
+ * launch fails.  Asynchronous on `stream`; no allocation.
+ */
+int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin,
+                         int Win, int H, int W, float* d_dst, void* stream);
 
 /*
  * LMOptimizer.calculate_gradient_and_hessian (geocalib/lm_optimizer.py:317-385) on materialised tensors:
