@@ -578,20 +578,38 @@ static void image_pass(const oracle_conf *cf, const oracle_data *d, const plan_t
     memcpy(out->Hm, Hm, sizeof(Hm));
 }
 
-/* Dense Cholesky solve (lower), n x n, row-major A (overwritten); returns 0 on failure. */
+/* Envelope (skyline) start of the factorisation's inner sums; lm_oracle_set_dense_cholesky(1) restores the dense loop.
+ * Row i of L is zero left of the first non-zero of row i of A (fill-in stays inside a row's envelope), so every term
+ * k < max(first[i], first[j]) of L_ik L_jk has an exact zero factor and a finite partner (a non-finite L_jk, j < i, has
+ * already failed column j's pivot test): skipping those terms changes no value, only the O(n^3) dense cost of the
+ * (2B + ni)^2 arrow-head system becomes O(n^2).  The triangular solves stay dense (O(n^2) either way), so a NaN in b
+ * spreads exactly as before. */
+static int g_dense_chol = 0;
+void lm_oracle_set_dense_cholesky(int on) { g_dense_chol = on; }
+
+/* Cholesky solve (lower), n x n, row-major A (overwritten); returns 0 on failure. */
 static int chol_solve(int n, real *A, real *b) {
+    int *first = (int *)malloc(sizeof(int) * (n > 0 ? n : 1));
+    for (int i = 0; i < n; ++i) {
+        int f = 0;
+        if (!g_dense_chol)
+            while (f < i && A[i * n + f] == 0) ++f;
+        first[i] = f;
+    }
     for (int j = 0; j < n; ++j) {
         real s = A[j * n + j];
-        for (int k = 0; k < j; ++k) s -= A[j * n + k] * A[j * n + k];
-        if (!(s > 0)) return 0;
+        for (int k = first[j]; k < j; ++k) s -= A[j * n + k] * A[j * n + k];
+        if (!(s > 0)) { free(first); return 0; }
         real l = rsqrt_(s);
         A[j * n + j] = l;
         for (int i = j + 1; i < n; ++i) {
             real t = A[i * n + j];
-            for (int k = 0; k < j; ++k) t -= A[i * n + k] * A[j * n + k];
+            const int k0 = first[i] > first[j] ? first[i] : first[j];
+            for (int k = k0; k < j; ++k) t -= A[i * n + k] * A[j * n + k];
             A[i * n + j] = t / l;
         }
     }
+    free(first);
     for (int i = 0; i < n; ++i) {
         real t = b[i];
         for (int k = 0; k < i; ++k) t -= A[i * n + k] * b[k];

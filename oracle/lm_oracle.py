@@ -171,6 +171,21 @@ def solve(data: dict, conf: dict = None, precision: str = "f32", training: bool 
     return out
 
 
+class dense_cholesky:
+    """Context: the oracle's Cholesky runs its dense inner loops instead of the envelope start (lm_oracle.c chol_solve).
+    The two give the same bits; tests/test_shared_gate.py holds them to that."""
+
+    def __enter__(self):
+        for p in ("f32", "f64"):
+            _lib(p).lm_oracle_set_dense_cholesky(1)
+        return self
+
+    def __exit__(self, *exc):
+        for p in ("f32", "f64"):
+            _lib(p).lm_oracle_set_dense_cholesky(0)
+        return False
+
+
 def system(data: dict, camera: np.ndarray, gravity: np.ndarray, conf: dict = None,
            as_rpf: bool = False, precision: str = "f32") -> dict:
     """One sweep at fixed parameters: mean Huber costs, J^T W r and J^T W J per image."""

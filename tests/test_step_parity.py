@@ -129,9 +129,11 @@ def _oracle_step(oracle, conf, data, start, lam, precision, steps=1, training=Tr
 
 
 def check_steps(dev, oracle, label, conf, data, knobs=None, ks=FIXED_K, adaptive_ks=ADAPTIVE_K, init=None, unaligned=False,
-                expect=None):
+                expect=None, gate_scale=None):
     """The step-ahead check of one configuration (fixed lambda at every k of `ks`, adaptive lambda at `adaptive_ks`), plus
-    the initial / final costs and the covariance at HIP's own final state.  `expect(run)` asserts the path was taken."""
+    the initial / final costs and the covariance at HIP's own final state.  `expect(run)` asserts the path was taken.
+    `gate_scale(start, lam)` -> (scale (B,), notes dict): a derived per-image factor on the gate (shared-intrinsics groups,
+    tests/shared_gate.py), its notes recorded with the step."""
     knobs = dict(knobs or {})
     model = conf["camera_model"]
     if model == "simple_divisional":
@@ -159,10 +161,14 @@ def check_steps(dev, oracle, label, conf, data, knobs=None, ks=FIXED_K, adaptive
             scale = 1.0
             if not fix:          # adaptive lambda: the bound on the step's amplification, (P + lambda) / lambda, scales the gate
                 scale = ((P + lam) / lam)[:, None]
+            notes = {}
+            if gate_scale is not None:
+                g, notes = gate_scale(start, lam)
+                scale = scale * g[:, None]
             ratio = step_gate(model, start, (r1["cam"], r1["grav"]), (ref64["camera"], ref64["gravity"]),
                               TAU_REL * scale, TAU_FLOOR * scale, extra)
             tag = f"step/{label}/{'fix' if fix else 'adaptive'}/k{k}"
-            MEASURED[tag] = {"worst_ratio": ratio.max(0).tolist(), "images": int(len(ratio))}
+            MEASURED[tag] = {"worst_ratio": ratio.max(0).tolist(), "images": int(len(ratio)), **notes}
             n_images[tag] = len(ratio)
             assert np.isfinite(ratio).all() and (ratio <= 1).all(), (tag, ratio.max(0), np.argwhere(ratio > 1)[:8])
             # images whose damped float64 system is not positive definite are exactly those whose HIP step failed
