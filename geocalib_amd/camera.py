@@ -6,8 +6,8 @@ SimpleRadial :565, Radial :663, SimpleDivisional :789, camera_models :945): a `(
 (un)distortion maps.  Every model here is *radial*: distort(p) = p * s(r2) and
 undistort(p) = p * t(r2) with r2 = |p|^2, so a model only supplies s, t and their derivatives
 and all Jacobians follow in closed form (the reference falls back to torch.func.jacfwd for the
-generic cases).  Host-side torch code: the per-pixel hot paths are csrc/gclm_pass.hip and, for undistort_image,
-csrc/gclm_image.hip.
+generic cases).  Host-side torch code: the per-pixel hot paths are csrc/gclm_pass.hip and, for undistort_image
+and get_img_from_pano, csrc/gclm_image.hip and csrc/gclm_pano.hip.
 """
 from typing import Dict, Tuple, Union
 
@@ -15,7 +15,7 @@ import torch
 from torch.nn import functional as F
 
 from .misc import TensorWrapper, autocast
-from .utils import deg2rad, focal2fov, fov2focal
+from .utils import deg2rad, focal2fov, fov2focal, rad2rotmat
 
 
 def _outer(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -347,6 +347,103 @@ class BaseCamera(TensorWrapper):
         grid = p2d.reshape(n, H, W, 2)
         grid = 2.0 * grid / torch.tensor([W - 1, H - 1]).to(grid) - 1
         return F.grid_sample(img, grid.expand(B, -1, -1, -1).to(img), align_corners=True)
+
+    def get_img_from_pano(self, pano_img: torch.Tensor, gravity, yaws=0.0, resize_factor=None) -> torch.Tensor:
+        """Render perspective images (n, C, h, w) from an equirectangular panorama, as the reference's camera.py:414-514:
+        image i looks along the rotation R_i = gravity.R[i] @ rad2rotmat(0, 0, yaws[i]), and its pixel (x, y) samples the
+        panorama bilinearly (zero padding, align_corners=True, no wrap at the +-pi seam) at
+            ix = (lon / pi + 1) / 2 (Ws - 1),   iy = (2 lat / pi + 1) / 2 (Hs - 1)
+        where (lon, lat) are the spherical angles of its undistorted bearing and Hs x Ws the panorama's size.
+
+        n = len(yaws) (a scalar yaw is a list of one); the camera and gravity batches broadcast against it and must each be 1
+        or the broadcast size.  As in the reference, n cameras with ONE yaw give one image, rendered from camera 0.
+        resize_factor (a scalar, or one per image) first resizes the panorama to int(Hp scale) x int(Wp scale) with
+        scale = pi / vfov_i * h / Hp * resize_factor[i] in the camera's dtype (bicubic if scale >= 1, else area, clamped to the
+        panorama's range); each distinct target shape is resized once.  `pano_img` is (C, Hp, Wp) or (1, C, Hp, Wp); as an
+        extension it may also be (n, C, Hp, Wp), one panorama per image.
+
+        A float32 panorama on a HIP device runs one gclm_render_from_pano launch per 192 images (not differentiable; a
+        non-finite coordinate gives 0).  Every other input (CPU, other dtypes, a resized side < 2) runs the reference's torch
+        composition.  The method reads the device once: the camera sizes, and with resize_factor the vfovs and factors, in
+        one .tolist()."""
+        assert isinstance(pano_img, torch.Tensor), "Panorama image must be a torch.Tensor."
+        data = self._data.reshape(-1, self._data.shape[-1])
+        if isinstance(yaws, (int, float)):
+            yaws = [yaws]
+        if isinstance(resize_factor, (int, float)):
+            resize_factor = [resize_factor]
+        yaws = yaws.to(self.dtype).to(self.device) if isinstance(yaws, torch.Tensor) else self.new_tensor(yaws)
+        yaws = yaws.reshape(-1)
+        if isinstance(resize_factor, torch.Tensor):
+            resize_factor = resize_factor.to(self.dtype).to(self.device).reshape(-1)
+        elif resize_factor is not None:
+            resize_factor = self.new_tensor(resize_factor).reshape(-1)
+        pano = pano_img if pano_img.dim() == 4 else pano_img.unsqueeze(0)
+        n, nc, ng = yaws.shape[0], data.shape[0], gravity._data.reshape(-1, 3).shape[0]
+        N = max(n, nc, ng)
+        if n < 1 or any(b not in (1, N) for b in (n, nc, ng)):
+            raise ValueError(f"camera batch {nc}, gravity batch {ng} and {n} yaws do not broadcast")
+        if pano.shape[0] not in (1, n):
+            raise ValueError(f"panorama batch {pano.shape[0]} must be 1 or the number of yaws {n}")
+        if resize_factor is not None and resize_factor.shape[0] not in (1, n):
+            raise ValueError(f"{resize_factor.shape[0]} resize factors for {n} yaws")
+
+        # the one device-to-host read: sizes (and vfovs, resize factors)
+        parts = [data[:, 0], data[:, 1]] + ([] if resize_factor is None else [self.vfov.reshape(-1), resize_factor])
+        host = torch.cat(parts).tolist()
+        ws, hs = host[:nc], host[nc:2 * nc]
+        assert len(set(ws)) == 1, "All images must have the same width."
+        assert len(set(hs)) == 1, "All images must have the same height."
+        w, h = int(round(ws[0])), int(round(hs[0]))
+
+        # per image: (panorama index, resized (H', W') or None, interpolation mode); each distinct one is resized once
+        Hp, Wp = pano.shape[-2:]
+        targets = []
+        for i in range(n):
+            p = i if pano.shape[0] > 1 else 0
+            if resize_factor is None:
+                targets.append((p, None, None))
+                continue
+            vfov, rf = host[2 * nc + (i if nc > 1 else 0)], host[3 * nc + (i if resize_factor.shape[0] > 1 else 0)]
+            scale = torch.pi / float(vfov) * float(h) / Hp * torch.tensor(rf, dtype=self.dtype)
+            shape = (int(Hp * scale), int(Wp * scale))
+            targets.append((p, shape, "bicubic" if scale >= 1 else "area"))
+        panos = {}
+        for key in targets:
+            if key not in panos:
+                p, shape, mode = key
+                src = pano[p:p + 1]
+                # clamp as bicubic interpolation can over- or under-shoot
+                panos[key] = src if shape is None else F.interpolate(src, size=shape, mode=mode).clamp(src.min(), src.max())
+
+        R_yaw = rad2rotmat(yaws.new_zeros(yaws.shape), yaws.new_zeros(yaws.shape), yaws)
+        if pano.is_cuda and pano.dtype == torch.float32 and all(min(v.shape[-2:]) >= 2 for v in panos.values()):
+            from .fields import render_from_pano
+            rot = (gravity.R.reshape(-1, 3, 3).to(R_yaw) @ R_yaw)[:n]
+            return render_from_pano(self.name(), data[:n] if nc > 1 else data[:1], rot, [panos[k][0] for k in targets],
+                                    (h, w))
+
+        # the reference's torch composition
+        cam = self.__class__(data)
+        uv1, _ = cam.image2world(cam.pixel_coordinates())
+        bearings = cam.pixel_bearing_many(uv1)
+        rotated_bearings = bearings @ gravity.R @ R_yaw
+        lon = torch.atan2(rotated_bearings[..., 0], rotated_bearings[..., 2])
+        lat = torch.atan2(rotated_bearings[..., 1], torch.norm(rotated_bearings[..., [0, 2]], dim=-1))
+        images = []
+        for idx, key in enumerate(targets):
+            resized_pano = panos[key]
+            pano_shape = key[1] if key[1] is not None else resized_pano.shape[-2:][::-1]
+            min_lon, max_lon = -torch.pi, torch.pi
+            min_lat, max_lat = -torch.pi / 2.0, torch.pi / 2.0
+            min_x, max_x = 0, pano_shape[0] - 1.0
+            min_y, max_y = 0, pano_shape[1] - 1.0
+            nx = (lon[idx] - min_lon) / (max_lon - min_lon) * (max_x - min_x) + min_x
+            ny = (lat[idx] - min_lat) / (max_lat - min_lat) * (max_y - min_y) + min_y
+            grid = torch.stack((nx.reshape((1, h, w)), ny.reshape((1, h, w))), dim=-1)
+            grid = 2.0 * grid / torch.tensor([pano_shape[-2] - 1, pano_shape[-1] - 1]).to(grid) - 1
+            images.append(F.grid_sample(resized_pano, grid.to(resized_pano), align_corners=True))
+        return torch.cat(images, 0)
 
     def __repr__(self):
         return f"{self.__class__.__name__} {self.shape} {self.dtype} {self.device}"

@@ -1,6 +1,7 @@
 // gclm_internal.h -- shared declarations of the translation units of libgeocalib_hip.so
 // (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update,
-//  gclm_api.hip: C ABI and launch sequence, gclm_image.hip: image undistortion).  gfx950 only.
+//  gclm_api.hip: C ABI and launch sequence, gclm_image.hip: image undistortion, gclm_pano.hip: panorama
+//  rendering).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -9,6 +9,7 @@ Replaces the tail of the reference's UpDecoder / LatitudeDecoder (geocalib/geoca
 
 and writes the five planes in the layout LMOptimizer reads (eager PyTorch: 8 kernels, ~18 plane passes) -- and, on request,
 a sixth: sin(latitude_field), which the LM solve reads in place of the radians (gclm_pack_fields_ex)."""
+import ctypes
 from typing import Dict, Optional
 
 import torch
@@ -184,4 +185,39 @@ def undistort_image(camera_model: str, cam: torch.Tensor, img: torch.Tensor, siz
                                           Hin, Win, H, W, dst[b0].data_ptr(), _raw_stream(src.device))
             if rc != 0:
                 raise _lib.GclmError(f"gclm_undistort_image failed ({rc})")
+    return dst
+
+
+def render_from_pano(camera_model: str, cam: torch.Tensor, rot: torch.Tensor, panos, size) -> torch.Tensor:
+    """gclm_render_from_pano: n images of `size` = (H, W) rendered from equirectangular panoramas, on torch's current stream.
+
+    `cam` is (1, 8) shared by the batch or (n, 8); `rot` is (n, 3, 3), R_i = gravity.R[i] @ rad2rotmat(0, 0, yaw_i); `panos`
+    is a sequence of n float32 (C, Hs, Ws) HIP device tensors, one per image (the same tensor may repeat).
+    BaseCamera.get_img_from_pano is the public entry; not differentiable."""
+    panos = [p.detach().contiguous() for p in panos]
+    n = len(panos)
+    if n == 0 or any(not p.is_cuda or p.dtype != torch.float32 or p.dim() != 3 for p in panos):
+        raise RuntimeError("geocalib_amd.render_from_pano needs float32 (C, H, W) HIP device tensors (no CPU fallback)")
+    dev, C = panos[0].device, panos[0].shape[0]
+    if any(p.device != dev or p.shape[0] != C for p in panos):
+        raise ValueError("every panorama must live on one device and carry the same number of channels")
+    H, W = int(size[0]), int(size[1])
+    cam = cam.detach().to(device=dev, dtype=torch.float32).reshape(-1, 8).contiguous()
+    rot = rot.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3, 3).contiguous()
+    if cam.shape[0] not in (1, n) or rot.shape[0] != n:
+        raise ValueError(f"camera batch {cam.shape[0]} must be 1 or {n}, rotations {rot.shape[0]} must be {n}")
+    dst = torch.empty((n, C, H, W), device=dev, dtype=torch.float32)
+    if dst.numel() == 0:
+        return dst
+    lib = _lib.load()
+    with _on_device(dev):
+        for i0 in range(0, n, 65535):
+            m = min(65535, n - i0)
+            c = cam if cam.shape[0] == 1 else cam[i0:i0 + m]
+            srcs = (ctypes.c_void_p * m)(*(p.data_ptr() for p in panos[i0:i0 + m]))
+            hw = (ctypes.c_int * (2 * m))(*(v for p in panos[i0:i0 + m] for v in p.shape[1:]))
+            rc = lib.gclm_render_from_pano(_lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], rot[i0].data_ptr(),
+                                           srcs, hw, m, C, H, W, dst[i0].data_ptr(), _raw_stream(dev))
+            if rc != 0:
+                raise _lib.GclmError(f"gclm_render_from_pano failed ({rc})")
     return dst

@@ -46,7 +46,7 @@ extern "C" {
  * added -- radial / simple_divisional batches walk row pairs by default, results equal the one-row walk's to summation order;
  * additive within 610: gclm_pack_fields_ex, gclm_solve_ex, gclm_calibrate_ex and gclm_shared_begin_ex added -- the head
  * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged; gclm_undistort_image
- * added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
+ * and gclm_render_from_pano added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -297,6 +297,30 @@ int gclm_upsample_fields_multi(const float* const* d_srcs, float* const* d_dsts,
  */
 int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin,
                          int Win, int H, int W, float* d_dst, void* stream);
+
+/*
+ * BaseCamera.get_img_from_pano (geocalib/camera.py:414-514) for n images, in one pass: d_dst (n, C, H, W) holds image i
+ * rendered from the equirectangular panorama srcs[i] (C, Hs, Ws) with Hs = src_hw[2 i], Ws = src_hw[2 i + 1], float32
+ * NCHW.  srcs and src_hw are HOST arrays of n device pointers and 2 n sizes (a pointer may repeat: n images of one
+ * panorama).  d_cam is (cam_batch, 8) {w, h, fx, fy, cx, cy, k1, k2} in device memory (the w, h entries are not read: H, W
+ * are the output size); cam_batch = 1 shares one camera over the batch, cam_batch = n gives each image its own.  d_rot is
+ * (n, 3, 3) row-major in device memory: R_i = gravity.R[i] @ rad2rotmat(0, 0, yaw_i).  For output pixel (x, y), integer
+ * pixel centres, no half-pixel offset:
+ *   u = (x - cx) / fx,  v = (y - cy) / fy,  r2 = u^2 + v^2,  t = the model's undistort scale t(r2)
+ *   q = (u t, v t, 1) R_i,  lon = atan2(q_x, q_z),  lat = atan2(q_y, hypot(q_x, q_z))
+ *   ix = (lon / pi + 1) / 2 (Ws - 1),   iy = (2 lat / pi + 1) / 2 (Hs - 1)
+ * t: pinhole 1; simple_radial 1 - k1 r2; radial 1 - k1 r2 + (3 k1^2 - k2) r2^2; simple_divisional 1 / (1 + k1 r2), with a
+ * zero denominator replaced by 1e6.  The reference normalises (u t, v t, 1) first; both angles are invariant to that scale.
+ * Bilinear with zero padding, as F.grid_sample(bilinear, zeros, align_corners=True): each of the four taps contributes
+ * only if it lies in [0, Ws) x [0, Hs); longitude does not wrap at +-pi.  A non-finite coordinate (a NaN or inf in the
+ * camera or the rotation) contributes nothing: that output pixel is 0.
+ * Returns -3 (before any HIP call) for a NULL pointer (srcs[i] included), n outside 1..65535, C < 1, H or W < 2,
+ * H * W > 2^31 - 1, any Hs or Ws < 2, cam_batch not 1 or n, a camera_model outside 0..3, or a destination that overlaps a
+ * source, the camera or the rotations; -10 if a launch fails.  Asynchronous on `stream` (one launch per 192 images); no
+ * allocation, no host-to-device copy: the panorama table travels in the kernel arguments.
+ */
+int gclm_render_from_pano(int camera_model, const float* d_cam, int cam_batch, const float* d_rot, const float* const* srcs,
+                          const int* src_hw, int n, int C, int H, int W, float* d_dst, void* stream);
 
 /*
  * LMOptimizer.calculate_gradient_and_hessian (geocalib/lm_optimizer.py:317-385) on materialised tensors:
