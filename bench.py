@@ -6,14 +6,20 @@ global batch is batch x N; BASELINE configs[1] at N=1, configs[2] = 8192 images 
 for N>1 by the single RCCL all-gather of the packed results.  Inputs are generated on the device
 before the timed region (counter-based generator keyed by (seed, global image index)).
 
-    python bench.py                      # N=1
+    python bench.py                      # N=1: the headline only
+    python bench.py --full               # N=1 with every record below (baselines, checks, other configurations)
     python bench.py --gpus N             # N>1 without a launcher: re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run does only what the headline needs: it sets up, warms up, times the --steps steps, writes --dump-outputs and
+prints ONE JSON line on rank 0 (contract in the task statement) with `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, the ground-truth check of the timed result, and
   roofline:     achieved = algorithmic bytes of one sweep launch / mean sweep duration measured with
                 HIP events on the launch stream inside the timed region; peak = 8 TB/s HBM3E.
+  multi_gpu:    N > 1 (below), without `parity`.
+Everything that takes runs of its own comes with --full (off by default): `roofline.read_ceiling_frac`, `check.vs_oracle`,
+`cpu_baseline`, `secondary`, `overlap`, `placement.best_of_n` and `multi_gpu.parity`, as described here.
   cpu_baseline: rank 0, at every N, after the last barrier, on a bounded sample of rank 0's timed batch, on THIS box's host
                 cores.  Where the reference
                 checkout exists on the box ($GEOCALIB_REFERENCE or /root/reference): the reference's OWN PyTorch CPU path
@@ -26,7 +32,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
                 that tests/test_oracle.py pins to reference-generated goldens; the solve the cpu_baseline leg times anyway):
                 max focal rel / max gravity abs / max final-cost rel distance next to north_star's 1e-4 gate.  The
                 ground-truth errors beside it are the noise floor of the synthetic data, not a parity figure.
-  secondary:    N=1 default run only: BASELINE configs[3] (simple_radial, B=1024) and configs[4]'s shape (shared intrinsics,
+  secondary:    N=1 pinhole run only: BASELINE configs[3] (simple_radial, B=1024) and configs[4]'s shape (shared intrinsics,
                 64 groups x 16 frames) at 5 steps after 2 warm-ups each, same event-based sweep timing, ground-truth check and
                 `check.vs_oracle` (64 images each); configs[3] also carries `slat_off`: the same solves on the same allocation
                 with the sin(latitude) scratch plane switched off (gclm_set_slat_plane(h, 0)) -- the plane's effect on THIS box;
@@ -41,11 +47,11 @@ timed steps and `ms_per_step` is the time of one of them.  --repeats R runs R su
 (float32 / float64); the inputs are a function of the arguments alone (device generator keyed by --seed and image index),
 so two builds run with the same arguments can be compared output for output.
 `value`, `ms_per_step` and `roofline` are measured on every rank's FIRST allocation of its input fields; at N = 1
-`placement.best_of_n` carries, beside them, the same measurement on the fastest-streaming of --placement-tries allocations
+(--full) `placement.best_of_n` carries, beside them, the same measurement on the fastest-streaming of --placement-tries allocations
 (a serving loop may choose where its persistent field buffers live; the line of record does not).
 `roofline.read_ceiling_frac`: what THIS allocation streams on THIS box with the sweep's own load and no arithmetic
 (gclm_read_probe over the five timed planes, 5 launches), as a fraction of the 8 TB/s peak; `frac_of_read_ceiling` = frac / that.
-For N > 1 the line also carries `multi_gpu.parity`: rank 0 re-generates the shard of ANOTHER rank from (seed, first index),
+For N > 1 --full adds `multi_gpu.parity`: rank 0 re-generates the shard of ANOTHER rank from (seed, first index),
 solves it alone and compares the gathered rows of that rank bit for bit (image / group sharding); for the frame split it solves
 whole groups alone and records the distance of the split result (gate 1e-4).
 For N > 1 the line also carries `multi_gpu`: ranks_seen (from the communicator), per_rank_ms (every rank's own
@@ -94,13 +100,17 @@ def parse():
                          "(LMOptimizer.overlap_streams): one part's update launches run under another part's sweep.  The "
                          "roofline block is then measured in a separate one-stream pass (overlapping launches have no "
                          "separable durations)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check what takes runs of its own: read ceiling, CPU baseline and "
+                         "oracle check, `secondary`, `overlap`, `placement.best_of_n`, `multi_gpu.parity` (off: the headline only)")
     ap.add_argument("--placement-tries", type=int, default=4,
-                    help="N = 1: allocations of the input fields tried for `placement.best_of_n`, AFTER the line of record (which "
-                         "is always measured on the first allocation); geocalib_amd.fields.fastest_placement; 1 = none")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="images for the CPU baseline (-1: auto, 0: skip)")
+                    help="--full, N = 1: allocations of the input fields tried for `placement.best_of_n`, AFTER the line of record "
+                         "(which is always measured on the first allocation); geocalib_amd.fields.fastest_placement; 1 = none")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: images for the CPU baseline (-1: auto, 0: skip)")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="N=1 pinhole run: skip the `secondary` records (configs[3] simple_radial, configs[4] shared-16 shape)")
-    ap.add_argument("--no-overlap", action="store_true", help="N=1: skip the `overlap` record (the batch as two halves on two streams)")
+                    help="--full, N=1 pinhole run: skip the `secondary` records (configs[3] simple_radial, configs[4] shared-16 shape)")
+    ap.add_argument("--no-overlap", action="store_true",
+                    help="--full, N=1: skip the `overlap` record (the batch as two halves on two streams)")
     ap.add_argument("--no-timing", action="store_true", help="skip the in-library HIP-event timing of the sweeps")
     ap.add_argument("--comm", default="torch", choices=["torch", "rccl"],
                     help="route of the two data-path collectives: torch.distributed (nccl = RCCL) or RCCL directly behind "
@@ -660,8 +670,8 @@ def main():
     algo_bytes_per_launch = B * H * W * PLANES * 4
     if not args.no_timing:
         lib.gclm_set_timing(handle.ptr, 0)
-    # the pure-read ceiling of THIS rank's allocation, right after the timed regions (same buffers, same clocks)
-    own_rc = read_ceiling(lib, data, dev)
+    # --full: the pure-read ceiling of THIS rank's allocation, right after the timed regions (same buffers, same clocks)
+    own_rc = read_ceiling(lib, data, dev) if args.full else None
     own_rc_frac = own_rc["frac"] if own_rc is not None else 0.0
 
     def algo_frac(avg_launch_ms):
@@ -708,7 +718,7 @@ def main():
         return sorted(rs)[len(rs) // 2]
 
     extras = {}
-    solo = world == 1 and not distributed and gs == 0 and not overlapped
+    solo = args.full and world == 1 and not distributed and gs == 0 and not overlapped
     if solo:
         if placement["tries"] > 1:
             # beside the line of record: what a serving loop that CHOOSES among allocations of its persistent field buffers
@@ -749,7 +759,7 @@ def main():
                                  "bit_identical": bool(same),
                                  "whole_job_frac": round(v2 * (args.lm_steps + 1) * H * W * PLANES * 4 / 1e9 / HBM_PEAK_GBS, 4)}
     host_sample = hip_sample = None
-    if rank == 0 and args.cpu_sample != 0:
+    if args.full and rank == 0 and args.cpu_sample != 0:
         from oracle.lm_oracle import effective_cpus
         n_cpu = min(B, args.cpu_sample if args.cpu_sample > 0 else max(8, 16 * effective_cpus()))   # ~7-10 s of CPU work
         if gs:
@@ -866,10 +876,11 @@ def main():
                 "launched_by": "bench.py itself (torch.distributed.run child)" if os.environ.get("GCLM_BENCH_SELF_LAUNCHED") == "1"
                                else "an external launcher",
                 "rccl": rccl_versions(lib)}
-            try:
-                result["multi_gpu"]["parity"] = gathered_parity() if gs == 0 or args.shared_by_group else split_parity()
-            except Exception as e:      # (a failing check is reported, it does not take the measurement down)
-                result["multi_gpu"]["parity"] = {"error": repr(e)}
+            if args.full:
+                try:
+                    result["multi_gpu"]["parity"] = gathered_parity() if gs == 0 or args.shared_by_group else split_parity()
+                except Exception as e:      # (a failing check is reported, it does not take the measurement down)
+                    result["multi_gpu"]["parity"] = {"error": repr(e)}
         if sweep_n and all(t > 0 for t in per_rank_sweep_ms):
             # every rank's own mean sweep launch; the line's `frac` / `achieved` are the SLOWEST rank's (N = 1: the only one)
             per_rank_frac = [round(algo_frac(t), 4) for t in per_rank_sweep_ms]

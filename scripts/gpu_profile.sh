@@ -14,7 +14,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "== bench $NAME ($EXTRA)"
-python $REPO/bench.py --steps 10 --warmup 2 --camera-model $MODEL $EXTRA > $OUT/bench_$NAME.json 2> $OUT/bench_$NAME.err
+python $REPO/bench.py --full --steps 10 --warmup 2 --camera-model $MODEL $EXTRA > $OUT/bench_$NAME.json 2> $OUT/bench_$NAME.err
 tail -c 2500 $OUT/bench_$NAME.json
 echo "== kernel trace $NAME"
 # the SAME command as the bench line (steps, warm-up, repeats), so that the two sweep averages are comparable: a short run

@@ -5,7 +5,8 @@
 (2) `cpu_baseline()` has two branches: the reference's own PyTorch path timed on THIS box when the checkout is there
     ($GEOCALIB_REFERENCE / /root/reference: the build container; a stub checkout here), otherwise the C port alone with
     `reference_on_this_box: false`.  Both keep the keys the driver parses (value, unit, cores, kind);
-(3) `dump_outputs()` (--dump-outputs DIR) writes the timed path's result as .npy files, sampled beyond its size cap."""
+(3) `dump_outputs()` (--dump-outputs DIR) writes the timed path's result as .npy files, sampled beyond its size cap;
+(4) `--full` is off by default: a plain run measures the headline only."""
 import json
 import os
 import subprocess
@@ -212,3 +213,15 @@ def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
     assert np.array_equal(rows, np.load(tmp_path / "s2" / "dump_rows.npy")) and np.all(np.diff(rows) > 0)
     for k in info["arrays"]:
         assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), got[k][rows]), k
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline only; --full adds the records that take runs
+    of their own (read ceiling, CPU baseline and oracle check, secondary, overlap, best of n allocations, N > 1 parity)."""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    plain = bench.parse()
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup) == (1, 20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    full = bench.parse()
+    assert full.full is True and vars(full) == {**vars(plain), "full": True}

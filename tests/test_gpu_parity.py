@@ -1344,7 +1344,7 @@ def test_bench_multi_rank_path_on_one_gpu(dev, extra):
     port = 29500 + (os.getpid() % 400)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--batch", "64", "--steps", "2", "--warmup", "1", "--repeats", "3", "--cpu-sample", "0"] + extra
+           "--batch", "64", "--steps", "2", "--warmup", "1", "--repeats", "3", "--cpu-sample", "0", "--full"] + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -1387,7 +1387,7 @@ def test_bench_starts_its_own_ranks(dev, extra):
     import sys
     from conftest import ROOT
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--batch", "64", "--steps", "2",
-           "--warmup", "1", "--cpu-sample", "2"] + extra
+           "--warmup", "1", "--cpu-sample", "2", "--full"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -1425,7 +1425,7 @@ def test_bench_starts_its_own_ranks(dev, extra):
 
 
 def test_bench_single_gpu_line_carries_secondary_overlap_and_best_of_n(dev):
-    """The N=1 line of record (small shapes here): `secondary` = configs[3] (simple_radial) and configs[4]'s shape
+    """The N=1 --full line (small shapes here): `secondary` = configs[3] (simple_radial) and configs[4]'s shape
     (shared-16) with their own roofline blocks, `overlap` = the same batch as two halves on two streams (bit-identical),
     `value` / `roofline` from the FIRST allocation with `placement.best_of_n` (the fastest of three allocations) beside them,
     `cpu_baseline` from this box (the port; the reference checkout does not exist on the GPU box)."""
@@ -1435,7 +1435,7 @@ def test_bench_single_gpu_line_carries_secondary_overlap_and_best_of_n(dev):
     from conftest import ROOT
     # 832 images of 640x480: halves of 416 images are cut into workgroups exactly like the whole batch (bit-identity regime)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "832", "--steps", "2", "--warmup", "1", "--cpu-sample", "4",
-           "--placement-tries", "3"]
+           "--placement-tries", "3", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -1493,6 +1493,33 @@ def test_bench_single_gpu_line_carries_secondary_overlap_and_best_of_n(dev):
     assert "first_allocation" not in pl and out["roofline"]["per_rank_frac"] == [out["roofline"]["frac"]]
     cb = out["cpu_baseline"]
     assert cb["value"] > 0 and cb["kind"] in ("port", "reference") and cb["reference_on_this_box"] == (cb["kind"] == "reference")
+
+
+def test_bench_plain_line_is_the_headline_only(dev, tmp_path):
+    """Without --full the N=1 line is the headline and what the timed steps measured themselves (roofline from their own
+    HIP events, ground-truth check of their result, --dump-outputs); nothing that takes runs of its own."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "64", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "dump")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["metric"] == "images/sec LM calibration (640x480, 20 iters)" and out["unit"] == "images/sec"
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1
+    assert abs(out["value"] - 64 * 1e3 / out["ms_per_step"]) <= 1e-3 * out["value"]
+    assert out["check"]["median_focal_rel_err_vs_gt"] < 5e-3 and "vs_oracle" not in out["check"]
+    rf = out["roofline"]
+    assert rf["launches_timed"] == 2 * 21 and 0 < rf["frac"] < 1 and "read_ceiling_frac" not in rf
+    for key in ("cpu_baseline", "secondary", "overlap", "multi_gpu"):
+        assert key not in out, key
+    assert out["placement"]["tries"] == 1 and "best_of_n" not in out["placement"]
+    assert out["dump_outputs"]["images"] == 64 and os.path.exists(tmp_path / "dump" / "camera.npy")
 
 
 @pytest.mark.gpu
@@ -1603,7 +1630,7 @@ def test_bench_collectives_through_rccl_with_one_rank(dev, extra):
     port = 29900 + (os.getpid() % 90)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl",
-           "--batch", "64", "--steps", "2", "--warmup", "1", "--cpu-sample", "0"] + extra
+           "--batch", "64", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--full"] + extra
     env = dict(os.environ, GCLM_FORCE_COLLECTIVES="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("NCCL_DEBUG", None)
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
