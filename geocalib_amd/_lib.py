@@ -87,6 +87,7 @@ _SIGNATURES = {
     "gclm_undistort_image": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "gclm_render_from_pano": (C.c_int, [C.c_int, _P, C.c_int, _P, C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                         C.c_int, _P, _P]),
+    "gclm_perspective_fields": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gclm_pack_fields": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "gclm_pack_fields_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gclm_synth_fields": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,

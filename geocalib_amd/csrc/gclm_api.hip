@@ -1019,6 +1019,29 @@ int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, co
     return e == hipSuccess ? 0 : -10;
 }
 
+int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,
+                            float* d_up, float* d_lat, void* stream) {
+    // every check runs before the first HIP call
+    if (!d_cam || !d_grav || (!d_up && !d_lat) || B < 1 || B > 65535 || H < 1 || W < 1) return -3;
+    if (camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL || (normalize_up != 0 && normalize_up != 1)) return -3;
+    if ((int64_t)H * W > INT32_MAX || (int64_t)((W + 63) / 64) * ((H + 3) / 4) * 256 > UINT32_MAX) return -3;
+    if (reinterpret_cast<uintptr_t>(d_up) % 8 || reinterpret_cast<uintptr_t>(d_lat) % 4) return -3;
+    const size_t px = (size_t)B * H * W;
+    auto overlaps = [](const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+        const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+        return pa && pb && pa < pb + b_bytes && pb < pa + a_bytes;
+    };
+    const size_t cam_bytes = (size_t)B * 8 * sizeof(float), grav_bytes = (size_t)B * 3 * sizeof(float);
+    const size_t up_bytes = px * 2 * sizeof(float), lat_bytes = px * sizeof(float);
+    if (overlaps(d_up, up_bytes, d_lat, lat_bytes) || overlaps(d_up, up_bytes, d_cam, cam_bytes) ||
+        overlaps(d_up, up_bytes, d_grav, grav_bytes) || overlaps(d_lat, lat_bytes, d_cam, cam_bytes) ||
+        overlaps(d_lat, lat_bytes, d_grav, grav_bytes))
+        return -3;
+    hipError_t e = launch_perspective_fields(camera_model, d_cam, d_grav, B, H, W, normalize_up, d_up, d_lat,
+                                             static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : -10;
+}
+
 int gclm_read_probe(const float* const* d_planes, int n_planes, size_t floats, void* stream) {
     if (!d_planes || n_planes < 1 || n_planes > 8 || floats % 4 != 0) return -3;
     for (int k = 0; k < n_planes; ++k)

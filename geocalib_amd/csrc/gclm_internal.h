@@ -1,7 +1,7 @@
 // gclm_internal.h -- shared declarations of the translation units of libgeocalib_hip.so
 // (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update,
 //  gclm_api.hip: C ABI and launch sequence, gclm_image.hip: image undistortion, gclm_pano.hip: panorama
-//  rendering).  gfx950 only.
+//  rendering, gclm_persp.hip: perspective fields).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -193,6 +193,8 @@ hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const flo
                               float* slat /* or nullptr */, hipStream_t s);
 hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,
                                   int Win, int H, int W, float* dst, hipStream_t s);
+hipError_t launch_perspective_fields(int camera_model, const float* cam, const float* grav, int B, int H, int W, int normalize,
+                                     float* up /* or nullptr */, float* lat /* or nullptr */, hipStream_t s);
 hipError_t launch_read_probe(const float* const* planes, int n, size_t floats, hipStream_t s);
 hipError_t launch_synth(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
                         float sigma, int group_size, int run, int run_stride, float* up, float* lat, float* upc, float* latc, float* gt_cam,

@@ -221,3 +221,35 @@ def render_from_pano(camera_model: str, cam: torch.Tensor, rot: torch.Tensor, pa
             if rc != 0:
                 raise _lib.GclmError(f"gclm_render_from_pano failed ({rc})")
     return dst
+
+
+def perspective_fields(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, size, up: bool = True, latitude: bool = True,
+                       normalize: bool = True):
+    """gclm_perspective_fields: the up field (B, H, W, 2) and the latitude field (B, H, W, 1) of `size` = (H, W) for cameras
+    `cam` (B, 8) and gravities `grav` (B, 3), float32 on one HIP device, in one launch per 65 535 images on torch's current
+    stream.  A field not asked for is returned as None.  get_perspective_field and friends are the public entries; not
+    differentiable.  simple_divisional's distort scale and its derivative take the forms that do not cancel in float32
+    (include/gclm.h), where the torch composition keeps the reference's."""
+    assert up or latitude, "at least one of up or latitude must be True"
+    cam, grav = cam.detach().reshape(-1, 8), grav.detach().reshape(-1, 3)
+    if not (cam.is_cuda and cam.dtype == grav.dtype == torch.float32 and grav.device == cam.device):
+        raise RuntimeError("geocalib_amd.perspective_fields needs float32 cameras and gravities on one HIP device "
+                           "(no CPU fallback)")
+    if cam.shape[0] != grav.shape[0]:
+        raise ValueError(f"camera batch {cam.shape[0]} and gravity batch {grav.shape[0]} must be equal")
+    cam, grav = cam.contiguous(), grav.contiguous()
+    B, H, W = cam.shape[0], int(size[0]), int(size[1])
+    u = cam.new_empty((B, H, W, 2)) if up else None
+    lat = cam.new_empty((B, H, W, 1)) if latitude else None
+    if B * H * W == 0:
+        return u, lat
+    lib = _lib.load()
+    with _on_device(cam.device):
+        for b0 in range(0, B, 65535):
+            n = min(65535, B - b0)
+            rc = lib.gclm_perspective_fields(_lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n,
+                                             H, W, int(normalize), None if u is None else u[b0].data_ptr(),
+                                             None if lat is None else lat[b0].data_ptr(), _raw_stream(cam.device))
+            if rc != 0:
+                raise _lib.GclmError(f"gclm_perspective_fields failed ({rc})")
+    return u, lat

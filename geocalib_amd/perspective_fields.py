@@ -5,6 +5,12 @@ Forward model of the reference's geocalib/perspective_fields.py (get_up_field :4
 geocalib_amd.camera.  Used to render ground-truth fields; the optimiser does NOT
 call this module -- residuals and Jacobians are evaluated per pixel in csrc/gclm_pass.hip.
 
+float32 cameras and gravities on one HIP device that do not require grad render through the HIP extension
+(gclm_perspective_fields: both fields in one launch); anything else (CPU, float64, autograd) runs the torch composition,
+which stays the differentiable path.  The one deliberate difference: the HIP path evaluates simple_divisional's distort
+scale and its derivative in forms that do not cancel in float32 (held to float64), the torch path keeps the reference's
+float32 forms, which do (1.3 % off at |k1 r2| = 1e-6).
+
 J_up_field / J_latitude_field / J_perspective_field (:84, :214, :323) return the per-pixel Jacobian fields
 from the same HIP pixel code through gclm_jacobian_fields (device tensors only, no CPU fallback).
 """
@@ -13,7 +19,7 @@ from typing import Tuple
 import torch
 from torch.nn import functional as F
 
-from . import _lib
+from . import _lib, fields
 from .camera import BaseCamera
 from .gravity import Gravity
 
@@ -38,10 +44,19 @@ def get_horizon_line(camera: BaseCamera, gravity: Gravity, relative: bool = True
     return ends / camera.size[0, 1] if relative else ends
 
 
-def get_up_field(camera: BaseCamera, gravity: Gravity, normalize: bool = True) -> torch.Tensor:
-    """Projected up direction per pixel, (..., h, w, 2): p = (a, b) - c (u, v), pushed through the
-    distortion differential  s p + (ds/duv . ... ) i.e. q = s p + (off . uv-weighted p)."""
-    camera, gravity, h, w = _batched(camera, gravity)
+def _on_hip(camera: BaseCamera, gravity: Gravity) -> bool:
+    """Whether these batched inputs take gclm_perspective_fields: float32 (B, 8) / (B, 3) data on one HIP device, the
+    batches equal, no grad."""
+    cam, grav = camera._data, gravity._data
+    return (cam.is_cuda and cam.dtype == grav.dtype == torch.float32 and grav.device == cam.device and
+            not (cam.requires_grad or grav.requires_grad) and cam.dim() == grav.dim() == 2 and cam.shape[0] == grav.shape[0])
+
+
+def _hip_fields(camera: BaseCamera, gravity: Gravity, h: int, w: int, up: bool, latitude: bool, normalize: bool = True):
+    return fields.perspective_fields(camera.name(), camera._data, gravity._data, (h, w), up, latitude, normalize)
+
+
+def _up_field_torch(camera: BaseCamera, gravity: Gravity, h: int, w: int, normalize: bool) -> torch.Tensor:
     uv = camera.normalize(camera.pixel_coordinates())
     abc = gravity.vec3d
     up = abc[..., None, :2] - abc[..., 2, None, None] * uv
@@ -54,23 +69,46 @@ def get_up_field(camera: BaseCamera, gravity: Gravity, normalize: bool = True) -
     return up.reshape(camera.shape[0], h, w, 2)
 
 
-def get_latitude_field(camera: BaseCamera, gravity: Gravity) -> torch.Tensor:
-    """Latitude (radians) of every pixel's viewing ray wrt the gravity direction, (..., h, w, 1)."""
-    camera, gravity, h, w = _batched(camera, gravity)
+def _latitude_field_torch(camera: BaseCamera, gravity: Gravity, h: int, w: int) -> torch.Tensor:
     rays = camera.pixel_bearing_many(camera.image2world(camera.pixel_coordinates())[0])
     s = (rays * gravity.vec3d[..., None, :]).sum(-1)
     eps = 1e-6
     return torch.asin(s.clamp(min=-1 + eps, max=1 - eps)).reshape(camera.shape[0], h, w, 1)
 
 
+def get_up_field(camera: BaseCamera, gravity: Gravity, normalize: bool = True) -> torch.Tensor:
+    """Projected up direction per pixel, (..., h, w, 2): p = (a, b) - c (u, v), pushed through the
+    distortion differential  s p + (ds/duv . ... ) i.e. q = s p + (off . uv-weighted p).
+    float32 device inputs without grad: one HIP launch, contiguous (B, h, w, 2) (module docstring)."""
+    camera, gravity, h, w = _batched(camera, gravity)
+    if _on_hip(camera, gravity):
+        return _hip_fields(camera, gravity, h, w, True, False, normalize)[0]
+    return _up_field_torch(camera, gravity, h, w, normalize)
+
+
+def get_latitude_field(camera: BaseCamera, gravity: Gravity) -> torch.Tensor:
+    """Latitude (radians) of every pixel's viewing ray wrt the gravity direction, (..., h, w, 1).
+    float32 device inputs without grad: one HIP launch, contiguous (B, h, w, 1) (module docstring)."""
+    camera, gravity, h, w = _batched(camera, gravity)
+    if _on_hip(camera, gravity):
+        return _hip_fields(camera, gravity, h, w, False, True)[1]
+    return _latitude_field_torch(camera, gravity, h, w)
+
+
 def get_perspective_field(camera: BaseCamera, gravity: Gravity, use_up: bool = True,
                           use_latitude: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(up (..., 2, h, w), latitude (..., 1, h, w)); a disabled field is returned as zeros."""
+    """(up (..., 2, h, w), latitude (..., 1, h, w)); a disabled field is returned as zeros.
+    float32 device inputs without grad: both fields from ONE HIP launch, the same views as the torch path's."""
     assert use_up or use_latitude, "At least one of use_up or use_latitude must be True."
     camera, gravity, h, w = _batched(camera, gravity)
     B = camera.shape[0]
-    up = get_up_field(camera, gravity).permute(0, 3, 1, 2) if use_up else camera.new_zeros((B, 2, h, w))
-    lat = get_latitude_field(camera, gravity).permute(0, 3, 1, 2) if use_latitude else camera.new_zeros((B, 1, h, w))
+    if _on_hip(camera, gravity):
+        up, lat = _hip_fields(camera, gravity, h, w, use_up, use_latitude)
+    else:
+        up = _up_field_torch(camera, gravity, h, w, True) if use_up else None
+        lat = _latitude_field_torch(camera, gravity, h, w) if use_latitude else None
+    up = up.permute(0, 3, 1, 2) if use_up else camera.new_zeros((B, 2, h, w))
+    lat = lat.permute(0, 3, 1, 2) if use_latitude else camera.new_zeros((B, 1, h, w))
     return up, lat
 
 

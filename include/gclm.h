@@ -45,8 +45,8 @@ extern "C" {
  * scratch plane became an optional allocation of its own, gclm_merge_stop_at skips empty parts; 610 = round 6: gclm_set_row_pairs
  * added -- radial / simple_divisional batches walk row pairs by default, results equal the one-row walk's to summation order;
  * additive within 610: gclm_pack_fields_ex, gclm_solve_ex, gclm_calibrate_ex and gclm_shared_begin_ex added -- the head
- * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged; gclm_undistort_image
- * and gclm_render_from_pano added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
+ * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged; gclm_undistort_image,
+ * gclm_render_from_pano and gclm_perspective_fields added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -297,6 +297,31 @@ int gclm_upsample_fields_multi(const float* const* d_srcs, float* const* d_dsts,
  */
 int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin,
                          int Win, int H, int W, float* d_dst, void* stream);
+
+/*
+ * get_up_field / get_latitude_field / get_perspective_field (geocalib/perspective_fields.py:47-74, 185-211, 278-320) for a
+ * batch, in one pass that writes both fields: d_up (B, H, W, 2) interleaved and d_lat (B, H, W, 1) (the memory of
+ * (B, 1, H, W)), float32; either may be NULL, not both.  d_cam is (B, 8) {w, h, fx, fy, cx, cy, k1, k2} and d_grav (B, 3)
+ * {a, b, c} in device memory, one camera and one gravity per image (the w, h entries are not read: H, W are the size;
+ * gravity is used as stored, not renormalised).  For pixel (x, y), integer pixel centres, no half-pixel offset:
+ *   u = (x - cx) / fx,  v = (y - cy) / fy,  r2 = u^2 + v^2
+ *   up:  p = (a - c u, b - c v),  q = s(r2) p + 2 s'(r2) (u, v) (u p_x + v p_y)      (pinhole: q = p)
+ *        normalize_up = 1: up = q / max(|q|, 1e-12) (F.normalize);  normalize_up = 0: up = q
+ *   lat: t = t(r2),  ray = (u t, v t, 1) / |(u t, v t, 1)|,  lat = asin(clamp(ray . (a, b, c), -1 + 1e-6, 1 - 1e-6))
+ * s = the distort scale, s' = ds/dr2, t = the undistort scale: pinhole s = t = 1; simple_radial s = 1 + k1 r2, s' = k1,
+ * t = 1 - k1 r2; radial s = 1 + k1 r2 + k2 r2^2, s' = k1 + 2 k2 r2, t = 1 - k1 r2 + (3 k1^2 - k2) r2^2; simple_divisional
+ * t = 1 / (1 + k1 r2) (a zero denominator replaced by 1e6) and, with tau = 1 - 4 k1 r2, s = (1 - sqrt(max(0, tau))) /
+ * (2 k1 r2), s' its derivative with sqrt(tau) clamped at 1e-3, both 1 and 0 where k1 r2 = 0 -- evaluated as s = 2 / (1 +
+ * sqrt(tau)) (tau > 0) or 1 / (2 k1 r2) (tau <= 0) and s' = 4 k1 / (sqrt(tau) (1 + sqrt(tau))^2) (tau >= 1e-6), which do
+ * not cancel in float32 (the reference's own evaluation does; below tau = 1e-6 its expression is used as written).
+ * A NaN or inf in the camera or gravity gives NaN in the pixels where the reference's composition does.
+ * Returns -3 (before any HIP call) for a NULL d_cam or d_grav, both outputs NULL, B outside 1..65535, H or W < 1,
+ * H * W > 2^31 - 1 (or a grid of (W / 64) x (H / 4) tiles over 2^32 threads), a camera_model outside 0..3, normalize_up
+ * not 0 or 1, a d_up not 8-byte or d_lat not 4-byte aligned, or an output that overlaps the other output, the camera or
+ * the gravity; -10 if the launch fails.  Asynchronous on `stream`; no allocation.
+ */
+int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W,
+                            int normalize_up, float* d_up, float* d_lat, void* stream);
 
 /*
  * BaseCamera.get_img_from_pano (geocalib/camera.py:414-514) for n images, in one pass: d_dst (n, C, H, W) holds image i
