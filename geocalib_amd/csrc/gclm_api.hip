@@ -140,6 +140,12 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 bool is_aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A null pointer names no range.
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+    return pa && pb && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
 // Carve the core workspace for B images / nchunks partial records per image / G groups.  Growing it frees and re-allocates
 // (hipFree synchronises the device ONCE, on the first call of a larger shape than any before; every later call finds the
 // workspace in place -- include/gclm.h says so).  A failure here is the only allocation failure a solve reports (-10).
@@ -981,10 +987,7 @@ int gclm_pack_fields_ex(const float* d_up_raw, const float* d_up_logconf, const 
     if (d_sin_lat) {
         // the sixth plane is written from registers but must not land on a plane the pass still reads or writes
         const size_t plane = (size_t)B * H * W * sizeof(float);
-        auto hits = [&](const void* p, size_t bytes) {
-            const char *a = reinterpret_cast<const char*>(d_sin_lat), *q = static_cast<const char*>(p);
-            return p && a < q + bytes && q < a + plane;
-        };
+        auto hits = [&](const void* p, size_t bytes) { return ranges_overlap(d_sin_lat, plane, p, bytes); };
         if (hits(d_up_raw, 2 * plane) || hits(d_up_logconf, plane) || hits(d_lat_raw, plane) || hits(d_lat_logconf, plane) ||
             hits(d_up, 2 * plane) || hits(d_up_conf, plane) || hits(d_lat, plane) || hits(d_lat_conf, plane))
             return -3;
@@ -1012,8 +1015,7 @@ int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, co
         return -3;
     if ((int64_t)H * W > INT32_MAX) return -3;
     const size_t in_bytes = (size_t)B * C * Hin * Win * sizeof(float), out_bytes = (size_t)B * C * H * W * sizeof(float);
-    const char *a = reinterpret_cast<const char*>(d_src), *o = reinterpret_cast<const char*>(d_dst);
-    if (o < a + in_bytes && a < o + out_bytes) return -3;
+    if (ranges_overlap(d_dst, out_bytes, d_src, in_bytes)) return -3;
     hipError_t e = launch_undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, d_dst,
                                           static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : -10;
@@ -1027,18 +1029,34 @@ int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d
     if ((int64_t)H * W > INT32_MAX || (int64_t)((W + 63) / 64) * ((H + 3) / 4) * 256 > UINT32_MAX) return -3;
     if (reinterpret_cast<uintptr_t>(d_up) % 8 || reinterpret_cast<uintptr_t>(d_lat) % 4) return -3;
     const size_t px = (size_t)B * H * W;
-    auto overlaps = [](const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-        const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-        return pa && pb && pa < pb + b_bytes && pb < pa + a_bytes;
-    };
     const size_t cam_bytes = (size_t)B * 8 * sizeof(float), grav_bytes = (size_t)B * 3 * sizeof(float);
     const size_t up_bytes = px * 2 * sizeof(float), lat_bytes = px * sizeof(float);
-    if (overlaps(d_up, up_bytes, d_lat, lat_bytes) || overlaps(d_up, up_bytes, d_cam, cam_bytes) ||
-        overlaps(d_up, up_bytes, d_grav, grav_bytes) || overlaps(d_lat, lat_bytes, d_cam, cam_bytes) ||
-        overlaps(d_lat, lat_bytes, d_grav, grav_bytes))
+    if (ranges_overlap(d_up, up_bytes, d_lat, lat_bytes) || ranges_overlap(d_up, up_bytes, d_cam, cam_bytes) ||
+        ranges_overlap(d_up, up_bytes, d_grav, grav_bytes) || ranges_overlap(d_lat, lat_bytes, d_cam, cam_bytes) ||
+        ranges_overlap(d_lat, lat_bytes, d_grav, grav_bytes))
         return -3;
     hipError_t e = launch_perspective_fields(camera_model, d_cam, d_grav, B, H, W, normalize_up, d_up, d_lat,
                                              static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : -10;
+}
+
+int gclm_render_from_pano(int camera_model, const float* d_cam, int cam_batch, const float* d_rot, const float* const* srcs,
+                          const int* src_hw, int n, int C, int H, int W, float* d_dst, void* stream) {
+    // every check runs before the first HIP call
+    if (!d_cam || !d_rot || !srcs || !src_hw || !d_dst || n < 1 || n > 65535 || C < 1 || H < 2 || W < 2) return -3;
+    if ((cam_batch != 1 && cam_batch != n) || camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL) return -3;
+    if ((int64_t)H * W > INT32_MAX) return -3;
+    const size_t out_bytes = (size_t)n * C * H * W * sizeof(float);
+    if (ranges_overlap(d_dst, out_bytes, d_cam, (size_t)cam_batch * 8 * sizeof(float)) ||
+        ranges_overlap(d_dst, out_bytes, d_rot, (size_t)n * 9 * sizeof(float)))
+        return -3;
+    for (int i = 0; i < n; ++i) {
+        const int Hs = src_hw[2 * i], Ws = src_hw[2 * i + 1];
+        if (!srcs[i] || Hs < 2 || Ws < 2) return -3;
+        if (ranges_overlap(d_dst, out_bytes, srcs[i], (size_t)C * Hs * Ws * sizeof(float))) return -3;
+    }
+    hipError_t e = launch_render_from_pano(camera_model, d_cam, cam_batch, d_rot, srcs, src_hw, n, C, H, W, d_dst,
+                                           static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : -10;
 }
 

@@ -1,10 +1,13 @@
 // gclm_internal.h -- shared declarations of the translation units of libgeocalib_hip.so
 // (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update,
-//  gclm_api.hip: C ABI and launch sequence, gclm_image.hip: image undistortion, gclm_pano.hip: panorama
-//  rendering, gclm_persp.hip: perspective fields).  gfx950 only.
+//  gclm_api.hip: C ABI (the entry points of the solve, the stage kernels and the three render kernels) and launch
+//  sequence, gclm_comm.hip: the communicator and its entry points; the render kernels over gclm_render.h --
+//  gclm_image.hip: image undistortion, gclm_pano.hip: panorama rendering, gclm_persp.hip: perspective fields).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/gclm.h"
 
@@ -32,6 +35,19 @@ __host__ __device__ constexpr int acc_h(int pm, int i, int j) {   // i <= j
 }
 __host__ __device__ constexpr int num_dist_params(int camera_model) {
     return camera_model == GCLM_PINHOLE ? 0 : (camera_model == GCLM_RADIAL ? 2 : 1);
+}
+
+// The one place a runtime camera_model becomes a template argument: calls f(std::integral_constant<int, MODEL>{}), so a
+// generic lambda reads the model as decltype(m)::value.  Host code.
+template <typename F>
+hipError_t with_camera_model(int camera_model, F&& f) {
+    switch (camera_model) {
+        case GCLM_PINHOLE: return f(std::integral_constant<int, GCLM_PINHOLE>{});
+        case GCLM_SIMPLE_RADIAL: return f(std::integral_constant<int, GCLM_SIMPLE_RADIAL>{});
+        case GCLM_RADIAL: return f(std::integral_constant<int, GCLM_RADIAL>{});
+        case GCLM_SIMPLE_DIVISIONAL: return f(std::integral_constant<int, GCLM_SIMPLE_DIVISIONAL>{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // Per-image constants consumed by the sweep (written by the update kernels).
@@ -193,6 +209,8 @@ hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const flo
                               float* slat /* or nullptr */, hipStream_t s);
 hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,
                                   int Win, int H, int W, float* dst, hipStream_t s);
+hipError_t launch_render_from_pano(int camera_model, const float* cam, int cam_batch, const float* rot, const float* const* srcs,
+                                   const int* src_hw, int n, int C, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_perspective_fields(int camera_model, const float* cam, const float* grav, int B, int H, int W, int normalize,
                                      float* up /* or nullptr */, float* lat /* or nullptr */, hipStream_t s);
 hipError_t launch_read_probe(const float* const* planes, int n, size_t floats, hipStream_t s);

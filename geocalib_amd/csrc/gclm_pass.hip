@@ -1523,13 +1523,7 @@ hipError_t dispatch_model(const SweepArgs& a, hipStream_t s) {
 
 hipError_t launch_sweep(int camera_model, const SweepArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    switch (camera_model) {
-        case GCLM_PINHOLE: return dispatch_model<GCLM_PINHOLE>(a, s);
-        case GCLM_SIMPLE_RADIAL: return dispatch_model<GCLM_SIMPLE_RADIAL>(a, s);
-        case GCLM_RADIAL: return dispatch_model<GCLM_RADIAL>(a, s);
-        case GCLM_SIMPLE_DIVISIONAL: return dispatch_model<GCLM_SIMPLE_DIVISIONAL>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return with_camera_model(camera_model, [&](auto m) { return dispatch_model<decltype(m)::value>(a, s); });
 }
 
 bool sweep_has_mirror(int camera_model) { return camera_model == GCLM_RADIAL || camera_model == GCLM_SIMPLE_DIVISIONAL; }
@@ -1542,30 +1536,17 @@ bool sweep_has_slat_plane(int camera_model) {
 hipError_t launch_fused_step(int camera_model, const SweepArgs& a, const FusedArgs& f, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     if (a.vec != 4) return hipErrorInvalidValue;          // the caller only fuses the float4 path
-    switch (camera_model) {
-        case GCLM_PINHOLE: return dispatch_fused<GCLM_PINHOLE>(a, f, s);
-        case GCLM_SIMPLE_RADIAL: return dispatch_fused<GCLM_SIMPLE_RADIAL>(a, f, s);
-        case GCLM_RADIAL: return dispatch_fused<GCLM_RADIAL>(a, f, s);
-        case GCLM_SIMPLE_DIVISIONAL: return dispatch_fused<GCLM_SIMPLE_DIVISIONAL>(a, f, s);
-        default: return hipErrorInvalidValue;
-    }
+    return with_camera_model(camera_model, [&](auto m) { return dispatch_fused<decltype(m)::value>(a, f, s); });
 }
 
 hipError_t launch_residual_fields(int camera_model, const float* d_up, const float* d_lat, const float* d_cam,
                                   const float* d_grav, int B, int H, int W, float* d_r_up, float* d_r_lat, hipStream_t s) {
     if (B <= 0 || H <= 0 || W <= 0) return hipSuccess;
     const dim3 grid((unsigned)(((size_t)H * W + kBlock - 1) / kBlock), B), block(kBlock);
-    switch (camera_model) {
-#define GCLM_RES(M) \
-    case M: hipLaunchKernelGGL(residual_kernel<M>, grid, block, 0, s, d_up, d_lat, d_cam, d_grav, H, W, d_r_up, d_r_lat); break
-        GCLM_RES(GCLM_PINHOLE);
-        GCLM_RES(GCLM_SIMPLE_RADIAL);
-        GCLM_RES(GCLM_RADIAL);
-        GCLM_RES(GCLM_SIMPLE_DIVISIONAL);
-#undef GCLM_RES
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_camera_model(camera_model, [&](auto m) {
+        hipLaunchKernelGGL(residual_kernel<decltype(m)::value>, grid, block, 0, s, d_up, d_lat, d_cam, d_grav, H, W, d_r_up, d_r_lat);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_huber_costs(const float* d_residual, size_t n, int dim, float scale, const float* d_conf,
@@ -1580,17 +1561,11 @@ hipError_t launch_jacobian_fields(int camera_model, const float* d_cam, const fl
                                   int spherical, int log_focal, float* d_J_up, float* d_J_lat, hipStream_t s) {
     if (B <= 0 || H <= 0 || W <= 0) return hipSuccess;
     const dim3 grid((unsigned)(((size_t)H * W + kBlock - 1) / kBlock), B), block(kBlock);
-    switch (camera_model) {
-#define GCLM_JAC(M) \
-    case M: hipLaunchKernelGGL(jacobian_kernel<M>, grid, block, 0, s, d_cam, d_grav, H, W, spherical, log_focal, d_J_up, d_J_lat); break
-        GCLM_JAC(GCLM_PINHOLE);
-        GCLM_JAC(GCLM_SIMPLE_RADIAL);
-        GCLM_JAC(GCLM_RADIAL);
-        GCLM_JAC(GCLM_SIMPLE_DIVISIONAL);
-#undef GCLM_JAC
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_camera_model(camera_model, [&](auto m) {
+        hipLaunchKernelGGL(jacobian_kernel<decltype(m)::value>, grid, block, 0, s, d_cam, d_grav, H, W, spherical, log_focal, d_J_up,
+                           d_J_lat);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace gclm

@@ -1,0 +1,120 @@
+// gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_persp.hip; device
+// code, included by those three only): the camera models' undistort and distort scales, the zero-padded bilinear sampler,
+// the nontemporal store and the tile geometry.  Each kernel keeps its own coordinate formula.
+//
+// Nothing here is shared with the LM sweep (gclm_pass.hip) or with synth_kernel (gclm_update.hip), on purpose: the sweep
+// keeps the reference's float32 forms so that the solve rounds like the reference, and the synthetic fields' bits define
+// the benchmark's inputs.
+#pragma once
+#include "gclm_internal.h"
+
+namespace gclm {
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));     // (HIP's float2 / float4 are structs: no nontemporal store)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Tile geometry: one wave walks 64 PX adjacent output pixels of a row (PX pixels per lane), a block of 4 waves covers 4 rows,
+// grid = (tiles of one image, images).  No LDS, no barrier.
+constexpr int kTileRows = kBlock / 64;                        // rows per block: one per wave
+constexpr int tile_columns(int W, int px = 1) { return (W + 64 * px - 1) / (64 * px); }
+constexpr int tile_count(int H, int W, int px = 1) { return tile_columns(W, px) * ((H + kTileRows - 1) / kTileRows); }
+
+// This lane's first pixel (x, y); false where it lies outside the image.
+template <int PX = 1>
+__device__ __forceinline__ bool tile_pixel(int tiles_x, int H, int W, int& x, int& y) {
+    const int t = blockIdx.x, ty = t / tiles_x, tx = t - ty * tiles_x;
+    y = ty * kTileRows + (threadIdx.x >> 6);
+    x = (tx * 64 + (threadIdx.x & 63)) * PX;
+    return y < H && x < W;
+}
+
+// Nontemporal stores of the outputs, which the kernels never read back (measured against plain stores).
+template <typename T>
+__device__ __forceinline__ void store_nt(T v, T* p) {
+    __builtin_nontemporal_store(v, p);
+}
+
+// t(r2), the undistort scale of image2world (camera.py's _undistort_scale): pinhole 1; simple_radial 1 - k1 r2; radial
+// 1 - k1 r2 + (3 k1^2 - k2) r2^2; simple_divisional 1 / (1 + k1 r2), a zero denominator replaced by 1e6 (the reference's
+// masked_fill).
+template <int MODEL>
+__device__ __forceinline__ float undistort_scale(float r2, float k1, float k2) {
+    if constexpr (MODEL == GCLM_PINHOLE) {
+        return 1.f;
+    } else if constexpr (MODEL == GCLM_SIMPLE_RADIAL) {
+        return 1.f - k1 * r2;
+    } else if constexpr (MODEL == GCLM_RADIAL) {
+        return 1.f - k1 * r2 + (3.f * k1 * k1 - k2) * (r2 * r2);
+    } else {
+        const float den = 1.f + k1 * r2;
+        return 1.f / (den == 0.f ? 1e6f : den);
+    }
+}
+
+// s(r2) and s' = ds/dr2, the distort scale (camera.py's _distort_scale, _distort_scale_dr2): pinhole s = 1, s' = 0;
+// simple_radial s = 1 + k1 r2, s' = k1; radial s = 1 + k1 r2 + k2 r2^2, s' = k1 + 2 k2 r2; simple_divisional, with
+// tau = 1 - 4 k1 r2, s = 2 / (1 + sqrt(tau)) (tau > 0), 1 / (2 k1 r2) (tau <= 0: what the reference's clamp leaves),
+// 1 (k1 r2 = 0); s' = 4 k1 / (sqrt(tau) (1 + sqrt(tau))^2) (tau >= 1e-6), the reference's expression with sqrt(tau) clamped
+// at 1e-3 (tau < 1e-6), 0 (k1 r2 = 0).  A caller that needs s alone ignores s'.
+// Those are the reference's definitions; its float32 evaluation, (1 - sqrt(1 - 4 k1 r2)) / (2 k1 r2), cancels (s 1.3 % off
+// at |k1 r2| = 1e-6, 13 px at 1000 px from the centre), the forms above do not.  The LM sweep (gclm_pass.hip) keeps the
+// cancelling form on purpose, to match the reference's float32 rounding inside the solve; a renderer has no such reason
+// and is held to float64 (tests/undistort_gate.py, tests/perspective_gate.py).
+template <int MODEL>
+__device__ __forceinline__ void distort_scale(float r2, float k1, float k2, float& s, float& sp) {
+    if constexpr (MODEL == GCLM_PINHOLE) {
+        s = 1.f;
+        sp = 0.f;
+    } else if constexpr (MODEL == GCLM_SIMPLE_RADIAL) {
+        s = 1.f + k1 * r2;
+        sp = k1;
+    } else if constexpr (MODEL == GCLM_RADIAL) {
+        s = 1.f + (k1 + k2 * r2) * r2;
+        sp = k1 + 2.f * k2 * r2;
+    } else {
+        const float kr = k1 * r2, tau = 1.f - 4.f * kr;
+        const float rt = sqrtf(tau > 0.f ? tau : 0.f), d = 1.f + rt;
+        s = tau > 0.f ? 2.f / d : 1.f / (2.f * kr);
+        if (tau >= 1e-6f) {
+            sp = 4.f * k1 / (rt * d * d);
+        } else {                // the reference's expression at its clamp sqrt(max(tau, 1e-6)): no cancellation here
+            const float tt = sqrtf(1e-6f), den = 2.f * k1 * (r2 * r2) * tt;
+            sp = (2.f * k1 * r2 - (1.f - tt) * tt) / (den == 0.f ? 1e6f : den);
+        }
+        if (kr == 0.f) s = 1.f, sp = 0.f;
+    }
+}
+
+// Bilinear sampling with zero padding, as F.grid_sample(bilinear, zeros, align_corners=True): each tap contributes only if
+// it lies in [0, Win) x [0, Hin), and is not read otherwise.  A non-finite coordinate contributes nothing: the sample is 0.
+// One pixel's taps: 64-bit offset of the top-left tap, bilinear weights, which taps lie inside the source.
+struct Taps {
+    int64_t o;
+    float w00, w01, w10, w11;
+    bool m00, m01, m10, m11;
+};
+
+__device__ __forceinline__ Taps bilinear_taps(float ix, float iy, int Hin, int Win) {
+    // NaN -> -2, +-inf and overflows -> just outside the source: every tap then lies outside and the sample is 0
+    ix = ix == ix ? fminf(fmaxf(ix, -2.f), (float)Win + 1.f) : -2.f;
+    iy = iy == iy ? fminf(fmaxf(iy, -2.f), (float)Hin + 1.f) : -2.f;
+    const float x0 = floorf(ix), y0 = floorf(iy);
+    const int xi = (int)x0, yi = (int)y0;
+    const float ax = ix - x0, ay = iy - y0, bx = 1.f - ax, by = 1.f - ay;
+    const bool mx0 = (unsigned)xi < (unsigned)Win, mx1 = (unsigned)(xi + 1) < (unsigned)Win;
+    const bool my0 = (unsigned)yi < (unsigned)Hin, my1 = (unsigned)(yi + 1) < (unsigned)Hin;
+    Taps t;
+    t.o = (int64_t)yi * Win + xi;
+    t.w00 = bx * by; t.w01 = ax * by; t.w10 = bx * ay; t.w11 = ax * ay;     // grid_sample's nw, ne, sw, se
+    t.m00 = mx0 && my0; t.m01 = mx1 && my0; t.m10 = mx0 && my1; t.m11 = mx1 && my1;
+    return t;
+}
+
+// One channel's sample: p is the channel's plane, Win its row stride.
+__device__ __forceinline__ float bilinear_sample(const float* __restrict__ p, const Taps& t, int Win) {
+    const float v00 = t.m00 ? p[t.o] : 0.f, v01 = t.m01 ? p[t.o + 1] : 0.f;
+    const float v10 = t.m10 ? p[t.o + Win] : 0.f, v11 = t.m11 ? p[t.o + Win + 1] : 0.f;
+    return v00 * t.w00 + v01 * t.w01 + v10 * t.w10 + v11 * t.w11;
+}
+
+}  // namespace gclm
