@@ -14,26 +14,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib
-from .lm_optimizer import _raw_stream
-
-
-class _NoSwitch:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_SWITCH = _NoSwitch()
-
-
-def _on_device(device):
-    """These entry points take no handle, so the launch goes to HIP's CURRENT device: switch only when the tensors live on
-    another one (one process per GPU: never; the context manager costs 3-4 us of a 10 us single-image call)."""
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    return _NO_SWITCH if index == torch.cuda.current_device() else torch.cuda.device(device)
+from . import _call, _lib
 
 
 def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: Optional[torch.Tensor] = None,
@@ -46,16 +27,11 @@ def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: 
     the solve's own polynomial.  LMOptimizer reads it in place of the radians where its sweeps can (include/gclm.h:
     gclm_solve_ex) -- same results bit for bit, no per-sweep sin and no library-owned scratch plane.  The key names no
     field / confidence / uncertainty, so GeoCalib._post_process neither resizes nor returns it."""
-    for t in (up_raw, lat_raw):
-        if not t.is_cuda:
-            raise RuntimeError("geocalib_amd.pack_fields needs HIP device tensors (no CPU fallback)")
+    up_raw, lat_raw = _call.dev_f32(up_raw, "up_raw"), _call.dev_f32(lat_raw, "lat_raw")
     B, _, H, W = lat_raw.shape
     assert up_raw.shape == (B, 2, H, W), up_raw.shape
-
-    def prep(t):
-        return None if t is None else t.detach().to(torch.float32).contiguous()
-
-    up_raw, lat_raw, ulc, llc = prep(up_raw), prep(lat_raw), prep(up_log_confidence), prep(lat_log_confidence)
+    ulc = None if up_log_confidence is None else _call.dev_f32(up_log_confidence, "up_log_confidence")
+    llc = None if lat_log_confidence is None else _call.dev_f32(lat_log_confidence, "lat_log_confidence")
     for c in (ulc, llc):
         assert c is None or c.numel() == B * H * W, c.shape
     out_like = (lambda t: t) if inplace else torch.empty_like
@@ -63,12 +39,9 @@ def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: 
     upc = None if ulc is None else out_like(ulc).view(B, H, W)
     latc = None if llc is None else out_like(llc).view(B, H, W)
     slat = torch.empty_like(lat_raw) if sin_latitude else None       # (never in place: a plane of its own)
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    with torch.cuda.device(lat_raw.device):
-        rc = _lib.load().gclm_pack_fields_ex(p(up_raw), p(ulc), p(lat_raw), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc),
-                                             p(slat), torch.cuda.current_stream(lat_raw.device).cuda_stream)
-    if rc != 0:
-        raise _lib.GclmError(f"gclm_pack_fields_ex failed ({rc})")
+    p = _call.ptr
+    _call.call("gclm_pack_fields_ex", p(up_raw), p(ulc), p(lat_raw), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc), p(slat),
+               _call.raw_stream(lat_raw.device), device=lat_raw.device)
     out = {"up_field": up, "latitude_field": lat}
     if upc is not None:
         out["up_confidence"] = upc
@@ -82,17 +55,13 @@ def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: 
 def upsample_fields(t: torch.Tensor, size) -> torch.Tensor:
     """Bilinear resize of the trailing (h, w) planes of `t` to `size` = (H, W), matching
     `torch.nn.functional.interpolate(t, size, mode="bilinear", align_corners=False)` (extractor.py:60-63)."""
-    if not t.is_cuda:
-        raise RuntimeError("geocalib_amd.upsample_fields needs a HIP device tensor (no CPU fallback)")
     H, W = int(size[0]), int(size[1])
-    src = t.detach().to(torch.float32).contiguous()
+    src = _call.dev_f32(t, "t")
     h, w = src.shape[-2:]
     dst = src.new_empty(src.shape[:-2] + (H, W))
     planes = src.numel() // (h * w)
-    with _on_device(src.device):
-        rc = _lib.load().gclm_upsample_fields(src.data_ptr(), planes, h, w, H, W, dst.data_ptr(), _raw_stream(src.device))
-    if rc != 0:
-        raise _lib.GclmError(f"gclm_upsample_fields failed ({rc})")
+    _call.call("gclm_upsample_fields", src.data_ptr(), planes, h, w, H, W, dst.data_ptr(), _call.raw_stream(src.device),
+               device=src.device)
     return dst
 
 
@@ -100,11 +69,7 @@ def upsample_fields_multi(tensors, size):
     """`upsample_fields` for several tensors of equal (h, w) in ONE launch (gclm_upsample_fields_multi): the outputs are views
     of one allocation, each contiguous, with the leading shape of its source."""
     H, W = int(size[0]), int(size[1])
-    srcs = []
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("geocalib_amd.upsample_fields_multi needs HIP device tensors (no CPU fallback)")
-        srcs.append(t.detach().to(torch.float32).contiguous())
+    srcs = [_call.dev_f32(t, "tensors") for t in tensors]
     h, w = srcs[0].shape[-2:]
     assert all(t.shape[-2:] == (h, w) and t.device == srcs[0].device for t in srcs) and 1 <= len(srcs) <= 8
     planes = [t.numel() // (h * w) for t in srcs]
@@ -115,12 +80,9 @@ def upsample_fields_multi(tensors, size):
         lo += n
     C = _lib.C
     n = len(srcs)
-    with _on_device(srcs[0].device):
-        rc = _lib.load().gclm_upsample_fields_multi((C.c_void_p * n)(*[t.data_ptr() for t in srcs]),
-                                                     (C.c_void_p * n)(*[o.data_ptr() for o in outs]), (C.c_int * n)(*planes), n, h, w,
-                                                     H, W, _raw_stream(srcs[0].device))
-    if rc != 0:
-        raise _lib.GclmError(f"gclm_upsample_fields_multi failed ({rc})")
+    _call.call("gclm_upsample_fields_multi", (C.c_void_p * n)(*[t.data_ptr() for t in srcs]),
+               (C.c_void_p * n)(*[o.data_ptr() for o in outs]), (C.c_int * n)(*planes), n, h, w, H, W,
+               _call.raw_stream(srcs[0].device), device=srcs[0].device)
     return outs
 
 
@@ -167,24 +129,19 @@ def undistort_image(camera_model: str, cam: torch.Tensor, img: torch.Tensor, siz
     """gclm_undistort_image: `img` (B, C, Hin, Win) float32 on a HIP device, resampled to `size` = (H, W) at the distorted
     position of every output pixel of `cam` ((1, 8) shared by the batch, or (B, 8)), in one launch per 65 535 images on
     torch's current stream.  BaseCamera.undistort_image is the public entry; not differentiable."""
-    if not img.is_cuda or img.dtype != torch.float32:
-        raise RuntimeError("geocalib_amd.undistort_image needs a float32 HIP device tensor (no CPU fallback)")
+    if img.dtype != torch.float32:
+        raise RuntimeError("geocalib_amd.undistort_image needs a float32 image")
     H, W = int(size[0]), int(size[1])
-    src = img.detach().contiguous()
+    src = _call.dev_f32(img, "img")
     cam = cam.detach().to(device=src.device, dtype=torch.float32).reshape(-1, 8).contiguous()
     B, C, Hin, Win = src.shape
     dst = src.new_empty((B, C, H, W))
     if dst.numel() == 0:
         return dst
-    lib = _lib.load()
-    with _on_device(src.device):
-        for b0 in range(0, B, 65535):
-            n = min(65535, B - b0)
-            c = cam if cam.shape[0] == 1 else cam[b0:b0 + n]
-            rc = lib.gclm_undistort_image(_lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], src[b0].data_ptr(), n, C,
-                                          Hin, Win, H, W, dst[b0].data_ptr(), _raw_stream(src.device))
-            if rc != 0:
-                raise _lib.GclmError(f"gclm_undistort_image failed ({rc})")
+    for b0, n in _call.slices(B):
+        c = cam if cam.shape[0] == 1 else cam[b0:b0 + n]
+        _call.call("gclm_undistort_image", _lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], src[b0].data_ptr(), n, C,
+                   Hin, Win, H, W, dst[b0].data_ptr(), _call.raw_stream(src.device), device=src.device)
     return dst
 
 
@@ -194,10 +151,10 @@ def render_from_pano(camera_model: str, cam: torch.Tensor, rot: torch.Tensor, pa
     `cam` is (1, 8) shared by the batch or (n, 8); `rot` is (n, 3, 3), R_i = gravity.R[i] @ rad2rotmat(0, 0, yaw_i); `panos`
     is a sequence of n float32 (C, Hs, Ws) HIP device tensors, one per image (the same tensor may repeat).
     BaseCamera.get_img_from_pano is the public entry; not differentiable."""
-    panos = [p.detach().contiguous() for p in panos]
     n = len(panos)
-    if n == 0 or any(not p.is_cuda or p.dtype != torch.float32 or p.dim() != 3 for p in panos):
-        raise RuntimeError("geocalib_amd.render_from_pano needs float32 (C, H, W) HIP device tensors (no CPU fallback)")
+    if n == 0 or any(p.dtype != torch.float32 or p.dim() != 3 for p in panos):
+        raise RuntimeError("geocalib_amd.render_from_pano needs float32 (C, H, W) panoramas")
+    panos = [_call.dev_f32(p, "panos") for p in panos]
     dev, C = panos[0].device, panos[0].shape[0]
     if any(p.device != dev or p.shape[0] != C for p in panos):
         raise ValueError("every panorama must live on one device and carry the same number of channels")
@@ -209,17 +166,12 @@ def render_from_pano(camera_model: str, cam: torch.Tensor, rot: torch.Tensor, pa
     dst = torch.empty((n, C, H, W), device=dev, dtype=torch.float32)
     if dst.numel() == 0:
         return dst
-    lib = _lib.load()
-    with _on_device(dev):
-        for i0 in range(0, n, 65535):
-            m = min(65535, n - i0)
-            c = cam if cam.shape[0] == 1 else cam[i0:i0 + m]
-            srcs = (ctypes.c_void_p * m)(*(p.data_ptr() for p in panos[i0:i0 + m]))
-            hw = (ctypes.c_int * (2 * m))(*(v for p in panos[i0:i0 + m] for v in p.shape[1:]))
-            rc = lib.gclm_render_from_pano(_lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], rot[i0].data_ptr(),
-                                           srcs, hw, m, C, H, W, dst[i0].data_ptr(), _raw_stream(dev))
-            if rc != 0:
-                raise _lib.GclmError(f"gclm_render_from_pano failed ({rc})")
+    for i0, m in _call.slices(n):
+        c = cam if cam.shape[0] == 1 else cam[i0:i0 + m]
+        srcs = (ctypes.c_void_p * m)(*(p.data_ptr() for p in panos[i0:i0 + m]))
+        hw = (ctypes.c_int * (2 * m))(*(v for p in panos[i0:i0 + m] for v in p.shape[1:]))
+        _call.call("gclm_render_from_pano", _lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], rot[i0].data_ptr(),
+                   srcs, hw, m, C, H, W, dst[i0].data_ptr(), _call.raw_stream(dev), device=dev)
     return dst
 
 
@@ -231,25 +183,18 @@ def perspective_fields(camera_model: str, cam: torch.Tensor, grav: torch.Tensor,
     differentiable.  simple_divisional's distort scale and its derivative take the forms that do not cancel in float32
     (include/gclm.h), where the torch composition keeps the reference's."""
     assert up or latitude, "at least one of up or latitude must be True"
-    cam, grav = cam.detach().reshape(-1, 8), grav.detach().reshape(-1, 3)
-    if not (cam.is_cuda and cam.dtype == grav.dtype == torch.float32 and grav.device == cam.device):
-        raise RuntimeError("geocalib_amd.perspective_fields needs float32 cameras and gravities on one HIP device "
-                           "(no CPU fallback)")
+    if not (cam.dtype == grav.dtype == torch.float32 and grav.device == cam.device):
+        raise RuntimeError("geocalib_amd.perspective_fields needs float32 cameras and gravities on one device")
+    cam, grav = _call.dev_f32(cam, "cam").reshape(-1, 8), _call.dev_f32(grav, "grav").reshape(-1, 3)
     if cam.shape[0] != grav.shape[0]:
         raise ValueError(f"camera batch {cam.shape[0]} and gravity batch {grav.shape[0]} must be equal")
-    cam, grav = cam.contiguous(), grav.contiguous()
     B, H, W = cam.shape[0], int(size[0]), int(size[1])
     u = cam.new_empty((B, H, W, 2)) if up else None
     lat = cam.new_empty((B, H, W, 1)) if latitude else None
     if B * H * W == 0:
         return u, lat
-    lib = _lib.load()
-    with _on_device(cam.device):
-        for b0 in range(0, B, 65535):
-            n = min(65535, B - b0)
-            rc = lib.gclm_perspective_fields(_lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n,
-                                             H, W, int(normalize), None if u is None else u[b0].data_ptr(),
-                                             None if lat is None else lat[b0].data_ptr(), _raw_stream(cam.device))
-            if rc != 0:
-                raise _lib.GclmError(f"gclm_perspective_fields failed ({rc})")
+    for b0, n in _call.slices(B):
+        _call.call("gclm_perspective_fields", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, H, W,
+                   int(normalize), None if u is None else u[b0].data_ptr(), None if lat is None else lat[b0].data_ptr(),
+                   _call.raw_stream(cam.device), device=cam.device)
     return u, lat

@@ -10,13 +10,14 @@ device memory and the stream, nothing else.  There is NO CPU fallback: CPU tenso
 libgeocalib_hip.so raise.
 """
 import logging
+import math
 from types import SimpleNamespace
 from typing import Any, Dict, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _call, _lib
 from .camera import BaseCamera, camera_models
 from .gravity import Gravity
 from .utils import focal2fov
@@ -52,11 +53,9 @@ class _Handle:
     blocks, partial records, early-stop counters), so two streams must never share one (include/gclm.h)."""
 
     def __init__(self, cfg: _lib.GclmConfig, device: torch.device):
-        lib = _lib.load()
         self.ptr = _lib.C.c_void_p()
         assert cfg.device == (device.index or 0)
-        rc = lib.gclm_create(_lib.C.byref(self.ptr), _lib.C.byref(cfg))
-        _lib.check(rc, None, "gclm_create")
+        _call.call("gclm_create", _lib.C.byref(self.ptr), _lib.C.byref(cfg))
         self.key = cfg.key()
         self.device = cfg.device
         self.paced = 0
@@ -65,12 +64,12 @@ class _Handle:
 
     def set_paced(self, depth: int):
         if depth != self.paced:
-            _lib.check(_lib.load().gclm_set_paced_launches(self.ptr, int(depth)), self.ptr, "gclm_set_paced_launches")
+            _call.call("gclm_set_paced_launches", self.ptr, int(depth), handle=self.ptr)
             self.paced = depth
 
     def set_row_pairs(self, mode: int):
         if mode != self.row_pairs:
-            _lib.check(_lib.load().gclm_set_row_pairs(self.ptr, int(mode)), self.ptr, "gclm_set_row_pairs")
+            _call.call("gclm_set_row_pairs", self.ptr, int(mode), handle=self.ptr)
             self.row_pairs = mode
 
     def destroy(self):
@@ -80,13 +79,12 @@ class _Handle:
 
     def configure(self, cfg: _lib.GclmConfig):
         if cfg.key() != self.key:
-            _lib.check(_lib.load().gclm_configure(self.ptr, _lib.C.byref(cfg)), self.ptr, "gclm_configure")
+            _call.call("gclm_configure", self.ptr, _lib.C.byref(cfg), handle=self.ptr)
             self.key = cfg.key()
 
     def __del__(self):
         try:
-            if self.ptr:
-                _lib.load().gclm_destroy(self.ptr)
+            self.destroy()
         except Exception:
             pass
 
@@ -98,37 +96,13 @@ def _unit_gravity(data: torch.Tensor) -> Gravity:
     return g
 
 
-def _raw_stream(device: torch.device) -> int:
-    """The current HIP stream of `device` as the integer the C ABI takes (torch.cuda.current_stream(...).cuda_stream builds a
-    Stream object first: 4.5 us per call on the single-image path)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    try:
-        return torch._C._cuda_getCurrentRawStream(idx)
-    except AttributeError:            # a torch without the private accessor
-        return torch.cuda.current_stream(device).cuda_stream
-
-
-def _dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError(f"geocalib_amd: `{name}` must live on a HIP device (got {t.device}); "
-                           "the MI355X path has no CPU fallback")
-    if t.dtype is torch.float32 and t.is_contiguous() and not t.requires_grad:
-        return t                                   # the common case: nothing to convert (saves three dispatcher trips)
-    return t.detach().to(torch.float32).contiguous()
-
-
 def huber_loss(x: torch.Tensor):
     """Huber loss of an already squared residual `x`: (loss, first derivative = IRLS weight, second derivative)
     (reference: lm_optimizer.py:79-87), evaluated by gclm_huber_costs in the sweep's branch-free form."""
-    if not x.is_cuda:
-        raise RuntimeError("geocalib_amd.huber_loss needs a HIP device tensor (no CPU fallback)")
-    xs = x.detach().to(torch.float32).contiguous()
+    xs = _call.dev_f32(x, "x")
     loss, d1, d2 = torch.empty_like(xs), torch.empty_like(xs), torch.empty_like(xs)
-    with torch.cuda.device(xs.device):
-        rc = _lib.load().gclm_huber_costs(xs.data_ptr(), xs.numel(), 0, 1.0, None, loss.data_ptr(), d1.data_ptr(),
-                                          d2.data_ptr(), torch.cuda.current_stream(xs.device).cuda_stream)
-    if rc != 0:
-        raise _lib.GclmError(f"gclm_huber_costs failed ({rc})")
+    _call.call("gclm_huber_costs", xs.data_ptr(), xs.numel(), 0, 1.0, None, loss.data_ptr(), d1.data_ptr(), d2.data_ptr(),
+               _call.raw_stream(xs.device), device=xs.device)
     return loss, d1, d2
 
 
@@ -157,21 +131,16 @@ def optimizer_step(G: torch.Tensor, H: torch.Tensor, lambda_: torch.Tensor, eps:
     device (gclm_optimizer_step; the reference copies H and G to the CPU, lm_optimizer.py:109-137).  G (..., N),
     H (..., N, N), lambda_ a scalar tensor or one value per system; N <= 5.  A system that is not positive definite
     gets a zero step (the reference zeroes the whole batch)."""
-    if not (G.is_cuda and H.is_cuda):
-        raise RuntimeError("geocalib_amd.optimizer_step needs HIP device tensors (no CPU fallback)")
+    g, h = _call.dev_f32(G, "G"), _call.dev_f32(H, "H")
     N = G.shape[-1]
     assert H.shape[-2:] == (N, N) and H.shape[:-2] == G.shape[:-1], (G.shape, H.shape)
-    g = G.detach().to(torch.float32).reshape(-1, N).contiguous()
-    h = H.detach().to(torch.float32).reshape(-1, N, N).contiguous()
+    g, h = g.reshape(-1, N), h.reshape(-1, N, N)
     B = g.shape[0]
     lam = torch.as_tensor(lambda_, dtype=torch.float32, device=g.device).reshape(-1).contiguous()
     assert lam.numel() in (1, B), f"lambda_ must hold 1 or {B} values"
     delta = torch.empty_like(g)
-    with torch.cuda.device(g.device):
-        rc = _lib.load().gclm_optimizer_step(g.data_ptr(), h.data_ptr(), lam.data_ptr(), int(lam.numel() == 1), float(eps),
-                                             B, N, delta.data_ptr(), None, torch.cuda.current_stream(g.device).cuda_stream)
-    if rc != 0:
-        raise _lib.GclmError(f"gclm_optimizer_step failed ({rc})")
+    _call.call("gclm_optimizer_step", g.data_ptr(), h.data_ptr(), lam.data_ptr(), int(lam.numel() == 1), float(eps), B, N,
+               delta.data_ptr(), None, _call.raw_stream(g.device), device=g.device)
     return delta.reshape(G.shape)
 
 
@@ -224,6 +193,11 @@ class LMOptimizer(nn.Module):
         self.camera_model = camera_models[camera_model]
         self.camera_has_distortion = hasattr(self.camera_model, "dist")
 
+    @property
+    def num_dist(self) -> int:
+        """Distortion parameters of the camera model (0 for pinhole)."""
+        return self.camera_model.num_dist_params() if self.camera_has_distortion else 0
+
     def setup_optimization_and_priors(self, data: Dict[str, torch.Tensor] = None,
                                       shared_intrinsics: bool = False) -> None:
         """Which parameters are free given the priors in `data` (reference: lm_optimizer.py:189-246)."""
@@ -234,7 +208,7 @@ class LMOptimizer(nn.Module):
         gravity_delta_dims = (0, 1) if estimate_gravity else (-1,)
         focal_delta_dims = (max(gravity_delta_dims) + 1,) if estimate_focal else (-1,)
         dist_delta_dims = None
-        nd = self.camera_model.num_dist_params() if self.camera_has_distortion else 0
+        nd = self.num_dist
         if estimate_dist:
             first = focal_delta_dims[-1] + 1
             dist_delta_dims = tuple(range(first, first + nd))
@@ -253,7 +227,12 @@ class LMOptimizer(nn.Module):
         return (device_index, self.camera_model, self.shared_intrinsics, self.num_steps, self.estimate_gravity,
                 self.estimate_focal, self.estimate_dist, self.training, c.group_size, c.lambda_, c.fix_lambda, c.early_stop,
                 c.atol, c.rtol, c.use_spherical_manifold, c.use_log_focal, c.loss_fn, c.up_loss_fn_scale,
-                c.lat_loss_fn_scale, c.init_conf["name"] if isinstance(c.init_conf, dict) else getattr(c.init_conf, "name", "trivial"))
+                c.lat_loss_fn_scale, self._init_name)
+
+    @property
+    def _init_name(self) -> str:
+        c = self.conf.init_conf
+        return c["name"] if isinstance(c, dict) else getattr(c, "name", "trivial")
 
     def _config(self, device_index: int = 0) -> _lib.GclmConfig:
         c = self.conf
@@ -276,9 +255,8 @@ class LMOptimizer(nn.Module):
         squared = c.loss_fn == "squared_loss"
         cfg.up_loss_fn_scale = self._SQUARED_LOSS_SCALE if squared else float(c.up_loss_fn_scale)
         cfg.lat_loss_fn_scale = self._SQUARED_LOSS_SCALE if squared else float(c.lat_loss_fn_scale)
-        init_name = c.init_conf["name"] if isinstance(c.init_conf, dict) else getattr(c.init_conf, "name", "trivial")
-        assert init_name in ("trivial", "heuristic"), f"Unknown initialisation: {init_name}"
-        cfg.heuristic_init = int(init_name == "heuristic")
+        assert self._init_name in ("trivial", "heuristic"), f"Unknown initialisation: {self._init_name}"
+        cfg.heuristic_init = int(self._init_name == "heuristic")
         cfg.estimate_gravity = int(self.estimate_gravity)
         cfg.estimate_focal = int(self.estimate_focal)
         cfg.estimate_dist = int(self.estimate_dist)
@@ -304,40 +282,32 @@ class LMOptimizer(nn.Module):
         overlapping the LM of batch k) get different workspaces; the same stream reuses its own, in order."""
         idx = device.index if device.index is not None else torch.cuda.current_device()
         if stream is None:
-            stream = torch.cuda.current_stream(torch.device("cuda", idx)).cuda_stream
+            stream = _call.raw_stream(torch.device("cuda", idx))
         key = (idx, int(stream))
         sig = self._config_signature(idx)
         h = self._handles.pop(key, None)
-        if h is not None and h.signature == sig:         # the common case of a serving loop: nothing to rebuild
-            self._handles[key] = h
-            h.set_paced(int(self.paced_launches))
-            h.set_row_pairs(-1 if self.row_pairs is None else int(bool(self.row_pairs)))
-            return h
-        cfg = self._config(idx)
-        if h is None:
-            while len(self._handles) >= self._MAX_HANDLES:      # drop the least recently used (its stream may be gone)
-                old_key = next(iter(self._handles))
-                old = self._handles.pop(old_key)
-                torch.cuda.synchronize(torch.device("cuda", old_key[0]))   # ITS device: the workspace may still be in flight
-                old.destroy()                                             # explicit: not whenever refcounting allows
-            h = _Handle(cfg, torch.device("cuda", idx))
-        else:
-            h.configure(cfg)
+        if h is None or h.signature != sig:              # not the common case of a serving loop: something to (re)build
+            cfg = self._config(idx)
+            if h is None:
+                while len(self._handles) >= self._MAX_HANDLES:      # drop the least recently used (its stream may be gone)
+                    old_key = next(iter(self._handles))
+                    old = self._handles.pop(old_key)
+                    torch.cuda.synchronize(torch.device("cuda", old_key[0]))   # ITS device: the workspace may still be in flight
+                    old.destroy()                                             # explicit: not whenever refcounting allows
+                h = _Handle(cfg, torch.device("cuda", idx))
+            else:
+                h.configure(cfg)
+            h.signature = sig
         self._handles[key] = h            # most recently used last
-        h.signature = sig
         h.set_paced(int(self.paced_launches))
         h.set_row_pairs(-1 if self.row_pairs is None else int(bool(self.row_pairs)))
         return h
 
-    @staticmethod
-    def _ptr(t):
-        return None if t is None else t.data_ptr()
-
     def _fields(self, data):
-        lat = _dev_f32(data["latitude_field"], "latitude_field")
-        up = _dev_f32(data["up_field"], "up_field") if "up_field" in data else None
-        upc = _dev_f32(data["up_confidence"], "up_confidence") if "up_confidence" in data and up is not None else None
-        latc = _dev_f32(data["latitude_confidence"], "latitude_confidence") if "latitude_confidence" in data else None
+        lat = _call.dev_f32(data["latitude_field"], "latitude_field")
+        up = _call.dev_f32(data["up_field"], "up_field") if "up_field" in data else None
+        upc = _call.dev_f32(data["up_confidence"], "up_confidence") if "up_confidence" in data and up is not None else None
+        latc = _call.dev_f32(data["latitude_confidence"], "latitude_confidence") if "latitude_confidence" in data else None
         B, _, H, W = lat.shape
         if up is not None:
             assert up.shape == (B, 2, H, W), up.shape
@@ -351,7 +321,7 @@ class LMOptimizer(nn.Module):
         place of the radians where it can (include/gclm.h: gclm_solve_ex), or None."""
         if "sin_latitude" not in data:
             return None
-        t = _dev_f32(data["sin_latitude"], "sin_latitude")
+        t = _call.dev_f32(data["sin_latitude"], "sin_latitude")
         if t.shape != lat.shape:
             raise ValueError(f"geocalib_amd: `sin_latitude` {tuple(t.shape)} must have the shape of `latitude_field` "
                              f"{tuple(lat.shape)}")
@@ -363,15 +333,14 @@ class LMOptimizer(nn.Module):
         up, lat, upc, latc, (B, H, W) = self._fields(data)
         slat = self._sin_lat(data, lat)
         device = lat.device
-        h = self._handle(device)
-        cam = _dev_f32(camera_opt._data, "camera").clone()
-        grav = _dev_f32(gravity_opt._data, "gravity").clone()
+        stream = _call.raw_stream(device)
+        h = self._handle(device, stream)
+        cam = _call.dev_f32(camera_opt._data, "camera").clone()
+        grav = _call.dev_f32(gravity_opt._data, "gravity").clone()
         info = torch.empty((B, _lib.INFO_STRIDE), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            rc = _lib.load().gclm_solve_ex(h.ptr, self._ptr(up), self._ptr(lat), self._ptr(upc), self._ptr(latc),
-                                           B, H, W, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), self._ptr(slat), stream)
-        _lib.check(rc, h.ptr, "gclm_solve_ex")
+        P = _call.ptr
+        _call.call("gclm_solve_ex", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(), grav.data_ptr(),
+                   info.data_ptr(), P(slat), stream, handle=h.ptr)
         self._last_raw = (cam, grav, info)     # packed device results (parallel.calibrate_sharded)
         return camera_opt.__class__(cam), _unit_gravity(grav), self._unpack_info(info, up is not None)
 
@@ -386,8 +355,7 @@ class LMOptimizer(nn.Module):
         out["initial_latitude_cost"] = col[I["initial_latitude_cost"]]
         out["initial_cost"] = col[I["initial_cost"]]
         if not self.training:
-            P = (2 * self.estimate_gravity + self.estimate_focal
-                 + (self.camera_model.num_dist_params() if self.camera_has_distortion else 0))
+            P = 2 * self.estimate_gravity + self.estimate_focal + self.num_dist
             c0 = I["covariance"]
             out["covariance"] = info[:, c0:c0 + P * P].reshape(-1, P, P)
             for k in ("roll_uncertainty", "pitch_uncertainty", "gravity_uncertainty", "focal_uncertainty",
@@ -434,7 +402,7 @@ class LMOptimizer(nn.Module):
         logger.info(f"Optimized gravity:\n{rad2deg(gravity_opt.rp)}")
         return {"camera": camera_opt, "gravity": gravity_opt, **infos}
 
-    _MAX_CALL = 65535      # images per C call (grid.y of the sweep)
+    _MAX_CALL = _call.MAX_CALL      # alias: callers and tests read the per-call image limit here
 
     def _calibrate_chunked(self, data: Dict[str, torch.Tensor], B: int):
         """Batches beyond 65 535 images: independent images are solved in slices of one C call each.  The device
@@ -452,8 +420,8 @@ class LMOptimizer(nn.Module):
         per_image = ("up_field", "latitude_field", "up_confidence", "latitude_confidence", "sin_latitude", "prior_focal",
                      "prior_gravity", "prior_dist")
         cams, gravs, infos, raws = [], [], [], []
-        for lo in range(0, B, self._MAX_CALL):
-            part = {k: (v[lo:lo + self._MAX_CALL] if k in per_image else v) for k, v in data.items()}
+        for lo, n in _call.slices(B):
+            part = {k: (v[lo:lo + n] if k in per_image else v) for k, v in data.items()}
             c, g, i = self.calibrate_fields(part)
             cams.append(c._data); gravs.append(g._data); infos.append(i); raws.append(self._last_raw)
         self._last_raw = tuple(torch.cat([r[j] for r in raws]) for j in range(3))
@@ -468,39 +436,36 @@ class LMOptimizer(nn.Module):
             return self._calibrate_chunked(data, B)
         slat = self._sin_lat(data, lat)
         device = lat.device
-        stream = _raw_stream(device)      # looked up once: the handle's key and the launch stream
+        stream = _call.raw_stream(device)      # looked up once: the handle's key and the launch stream
         h = self._handle(device, stream)
 
-        def prior(key, shape):
+        def prior(key, shape=None):
             if key not in data:
                 return None
             t = data[key]
             t = t._data if hasattr(t, "_data") else torch.as_tensor(t)
             t = t.detach().to(device=device, dtype=torch.float32).contiguous()
-            assert t.numel() == int(torch.tensor(shape).prod()), (key, t.shape, shape)
+            assert shape is None or t.numel() == math.prod(shape), (key, t.shape, shape)
             return t
 
         scales = prior("scales", (2,))
         pf = prior("prior_focal", (B,))
         pg = prior("prior_gravity", (B, 3))
-        nd = self.camera_model.num_dist_params() if self.camera_has_distortion else 0
-        pd = None
-        if "prior_dist" in data and nd:
-            pd = data["prior_dist"].detach().to(device=device, dtype=torch.float32).contiguous()
+        nd = self.num_dist
+        pd = prior("prior_dist") if nd else None       # (B,) or (B, k): its own width is the number of given parameters
+        if pd is not None:
             nd = pd.shape[-1] if pd.dim() > 1 else 1
         cam = torch.empty((B, 8), dtype=torch.float32, device=device)
         grav = torch.empty((B, 3), dtype=torch.float32, device=device)
         info = torch.empty((B, _lib.INFO_STRIDE), dtype=torch.float32, device=device)
-        P = self._ptr           # (the library switches to the handle's device itself: no torch.cuda.device() context)
+        P = _call.ptr
         n_over = self._overlap_parts(B, H, W, h, lambda: all(t is None or t.data_ptr() % 16 == 0 for t in (up, lat, upc, latc)))
         if n_over > 1:
             self._calibrate_overlapped(n_over, device, (up, lat, upc, latc, slat), (B, H, W), scales, (pf, pg, pd), nd,
                                        (cam, grav, info))
         else:
-            rc = _lib.load().gclm_calibrate_ex(h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg),
-                                               P(pd), nd, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), stream)
-            if rc != 0:
-                _lib.check(rc, h.ptr, "gclm_calibrate_ex")
+            _call.call("gclm_calibrate_ex", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg), P(pd), nd,
+                       cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), stream, handle=h.ptr)
         self._last_raw = (cam, grav, info)
         return self.camera_model(cam), _unit_gravity(grav), self._unpack_info(info, up is not None)
 
@@ -545,8 +510,7 @@ class LMOptimizer(nn.Module):
         cuts = set()
         for size in {B} | {B * (i + 1) // n - B * i // n for i in range(n)}:
             rows = _lib.C.c_int(0)
-            _lib.check(_lib.load().gclm_plan_cut(handle.ptr, size, H, W, int(aligned16), _lib.C.byref(rows), None), handle.ptr,
-                       "gclm_plan_cut")
+            _call.call("gclm_plan_cut", handle.ptr, size, H, W, int(aligned16), _lib.C.byref(rows), None, handle=handle.ptr)
             cuts.add(rows.value)
         if len(cuts) == 1:
             return n
@@ -568,7 +532,7 @@ class LMOptimizer(nn.Module):
         if streams is None or len(streams) < n:
             streams = side[device.index] = [torch.cuda.Stream(device=device) for _ in range(n)]
         fork = cur.record_event()
-        lib, P = _lib.load(), self._ptr
+        P = _call.ptr
         bounds = [B * i // n for i in range(n + 1)]
 
         def part(t, lo, hi):
@@ -583,10 +547,8 @@ class LMOptimizer(nn.Module):
             up, lat, upc, latc, slat = (part(t, lo, hi) for t in fields)
             pf, pg, pd = (part(t, lo, hi) for t in priors)
             cam, grav, info = (t[lo:hi] for t in outs)
-            rc = lib.gclm_calibrate_ex(h.ptr, P(up), P(lat), P(upc), P(latc), hi - lo, H, W, P(scales), P(pf), P(pg), P(pd), nd,
-                                       cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), s.cuda_stream)
-            if rc != 0:
-                _lib.check(rc, h.ptr, "gclm_calibrate_ex")
+            _call.call("gclm_calibrate_ex", h.ptr, P(up), P(lat), P(upc), P(latc), hi - lo, H, W, P(scales), P(pf), P(pg), P(pd),
+                       nd, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), s.cuda_stream, handle=h.ptr)
             handles.append(h)
             cur.wait_event(s.record_event())                # join: whatever follows on the caller's stream sees the results
         # infos["stop_at"] is ONE number for the whole batch (the first step after which every image's cost was close,
@@ -596,9 +558,7 @@ class LMOptimizer(nn.Module):
         parts = (C.c_void_p * n)(*[h.ptr.value for h in handles])
         infos = (C.c_void_p * n)(*[info[bounds[i]:bounds[i + 1]].data_ptr() for i in range(n)])
         sizes = (C.c_int * n)(*[bounds[i + 1] - bounds[i] for i in range(n)])
-        rc = lib.gclm_merge_stop_at(parts, infos, sizes, n, cur.cuda_stream)
-        if rc != 0:
-            _lib.check(rc, handles[0].ptr, "gclm_merge_stop_at")
+        _call.call("gclm_merge_stop_at", parts, infos, sizes, n, cur.cuda_stream, handle=handles[0].ptr)
 
     # ------------------------------------------------------------------ kernel-level entry (tests, tools)
     def system(self, data: Dict[str, torch.Tensor], camera: BaseCamera, gravity: Gravity,
@@ -607,19 +567,17 @@ class LMOptimizer(nn.Module):
         (reference: calculate_residuals + calculate_costs + setup_system, lm_optimizer.py:248-461)."""
         up, lat, upc, latc, (B, H, W) = self._fields(data)
         device = lat.device
-        h = self._handle(device)
-        cam = _dev_f32(camera._data, "camera")
-        grav = _dev_f32(gravity._data, "gravity")
+        stream = _call.raw_stream(device)
+        h = self._handle(device, stream)
+        cam = _call.dev_f32(camera._data, "camera")
+        grav = _call.dev_f32(gravity._data, "gravity")
         cost = torch.empty((B, 2), dtype=torch.float32, device=device)
         grad = torch.empty((B, _lib.MAX_PARAMS), dtype=torch.float32, device=device)
         hess = torch.empty((B, _lib.MAX_PARAMS, _lib.MAX_PARAMS), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            rc = _lib.load().gclm_system(h.ptr, self._ptr(up), self._ptr(lat), self._ptr(upc), self._ptr(latc),
-                                         B, H, W, cam.data_ptr(), grav.data_ptr(), int(as_rpf),
-                                         cost.data_ptr(), grad.data_ptr(), hess.data_ptr(), stream)
-        _lib.check(rc, h.ptr, "gclm_system")
-        P = 3 + (self.camera_model.num_dist_params() if self.camera_has_distortion else 0)
+        ptr = _call.ptr
+        _call.call("gclm_system", h.ptr, ptr(up), ptr(lat), ptr(upc), ptr(latc), B, H, W, cam.data_ptr(), grav.data_ptr(),
+                   int(as_rpf), cost.data_ptr(), grad.data_ptr(), hess.data_ptr(), stream, handle=h.ptr)
+        P = 3 + self.num_dist
         return {"cost_up": cost[:, 0], "cost_lat": cost[:, 1], "G": grad[:, :P], "H": hess[:, :P, :P]}
 
     # ------------------------------------------------------------------ the reference's per-pixel stages as tensors
@@ -628,23 +586,19 @@ class LMOptimizer(nn.Module):
         """`up_residual` (B,N,2) = up_field - prediction, `latitude_residual` (B,N,1) = sin(latitude_field) -
         sin(prediction), pixels in row-major order (reference: lm_optimizer.py:248-274).  A solve never
         materialises these; this is the sweep's pixel code writing them out (gclm_residual_fields)."""
-        lat = _dev_f32(data["latitude_field"], "latitude_field") if "latitude_field" in data else None
-        up = _dev_f32(data["up_field"], "up_field") if "up_field" in data else None
+        lat = _call.dev_f32(data["latitude_field"], "latitude_field") if "latitude_field" in data else None
+        up = _call.dev_f32(data["up_field"], "up_field") if "up_field" in data else None
         ref = lat if lat is not None else up
         assert ref is not None, "data holds neither an up nor a latitude field"
         B, _, H, W = ref.shape
         device = ref.device
-        cam = _dev_f32(camera._data, "camera").reshape(-1, 8)
-        grav = _dev_f32(gravity._data, "gravity").reshape(-1, 3)
+        cam = _call.dev_f32(camera._data, "camera").reshape(-1, 8)
+        grav = _call.dev_f32(gravity._data, "gravity").reshape(-1, 3)
         r_up = torch.empty((B, H * W, 2), dtype=torch.float32, device=device) if up is not None else None
         r_lat = torch.empty((B, H * W, 1), dtype=torch.float32, device=device) if lat is not None else None
-        with torch.cuda.device(device):
-            rc = _lib.load().gclm_residual_fields(_lib.CAMERA_MODEL_IDS[self.camera_model.name()], self._ptr(up),
-                                                  self._ptr(lat), cam.data_ptr(), grav.data_ptr(), B, H, W,
-                                                  self._ptr(r_up), self._ptr(r_lat),
-                                                  torch.cuda.current_stream(device).cuda_stream)
-        if rc != 0:
-            raise _lib.GclmError(f"gclm_residual_fields failed ({rc})")
+        P = _call.ptr
+        _call.call("gclm_residual_fields", _lib.CAMERA_MODEL_IDS[self.camera_model.name()], P(up), P(lat), cam.data_ptr(),
+                   grav.data_ptr(), B, H, W, P(r_up), P(r_lat), _call.raw_stream(device), device=device)
         out = {}
         if r_up is not None:
             out["up_residual"] = r_up
@@ -661,16 +615,13 @@ class LMOptimizer(nn.Module):
                 ("latitude_residual", "latitude_confidence", self.conf.lat_loss_fn_scale, "latitude_cost", "latitude_weights")):
             if key not in residuals:
                 continue
-            r = _dev_f32(residuals[key], key)
+            r = _call.dev_f32(residuals[key], key)
             B, N, dim = r.shape
-            conf = _dev_f32(data[conf_key], conf_key).reshape(B, N) if conf_key in data else None
+            conf = _call.dev_f32(data[conf_key], conf_key).reshape(B, N) if conf_key in data else None
             cost, weight = torch.empty((B, N), dtype=torch.float32, device=r.device), torch.empty((B, N), dtype=torch.float32, device=r.device)
             scale = self._SQUARED_LOSS_SCALE if self.conf.loss_fn == "squared_loss" else float(scale)
-            with torch.cuda.device(r.device):
-                rc = _lib.load().gclm_huber_costs(r.data_ptr(), B * N, dim, scale, self._ptr(conf), cost.data_ptr(),
-                                                  weight.data_ptr(), None, torch.cuda.current_stream(r.device).cuda_stream)
-            if rc != 0:
-                raise _lib.GclmError(f"gclm_huber_costs failed ({rc})")
+            _call.call("gclm_huber_costs", r.data_ptr(), B * N, dim, scale, _call.ptr(conf), cost.data_ptr(), weight.data_ptr(),
+                       None, _call.raw_stream(r.device), device=r.device)
             costs[ckey], weights[wkey] = cost, weight
         return costs, weights
 
@@ -693,7 +644,7 @@ class LMOptimizer(nn.Module):
         if self.estimate_focal:
             dims += (2,)
         if self.camera_has_distortion:
-            dims += tuple(range(3, 3 + self.camera_model.num_dist_params()))
+            dims += tuple(range(3, 3 + self.num_dist))
         assert dims, "No parameters to optimize"
         return list(dims)
 
@@ -702,20 +653,14 @@ class LMOptimizer(nn.Module):
         """Grad = sum_px w J^T r (B,P), Hess = sum_px w J^T J (B,P,P) for materialised J (B,N,R,P_full), residuals
         (B,N,R), weights (B,N) (reference: lm_optimizer.py:317-385; contraction on the device, gclm_gradient_hessian).
         shared_intrinsics=True returns the reference's arrow-head layout: Grad (1, 2B+ni), Hess (1, 2B+ni, 2B+ni)."""
-        for t in (J, residuals, weights):
-            if not t.is_cuda:
-                raise RuntimeError("calculate_gradient_and_hessian needs HIP device tensors (no CPU fallback)")
-        Jc = J.detach().to(torch.float32)[..., self._column_dims()].contiguous()
+        Jc = _call.dev_f32(J, "J")[..., self._column_dims()].contiguous()
         B, N, R, P = Jc.shape
-        r = residuals.detach().to(torch.float32).reshape(B, N, R).contiguous()
-        w = weights.detach().to(torch.float32).reshape(B, N).contiguous()
+        r = _call.dev_f32(residuals, "residuals").reshape(B, N, R)
+        w = _call.dev_f32(weights, "weights").reshape(B, N)
         Grad = torch.empty((B, P), dtype=torch.float32, device=Jc.device)
         Hess = torch.empty((B, P, P), dtype=torch.float32, device=Jc.device)
-        with torch.cuda.device(Jc.device):
-            rc = _lib.load().gclm_gradient_hessian(Jc.data_ptr(), r.data_ptr(), w.data_ptr(), B, N, R, P, 0, Grad.data_ptr(),
-                                                   Hess.data_ptr(), torch.cuda.current_stream(Jc.device).cuda_stream)
-        if rc != 0:
-            raise _lib.GclmError(f"gclm_gradient_hessian failed ({rc})")
+        _call.call("gclm_gradient_hessian", Jc.data_ptr(), r.data_ptr(), w.data_ptr(), B, N, R, P, 0, Grad.data_ptr(),
+                   Hess.data_ptr(), _call.raw_stream(Jc.device), device=Jc.device)
         if not shared_intrinsics:
             return Grad, Hess
         # arrow-head assembly: per-frame gravity blocks on the diagonal, summed intrinsics in the last rows/columns

@@ -20,10 +20,10 @@ from typing import Dict, Tuple
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _call, _lib
 from .camera import BaseCamera
 from .gravity import Gravity
-from .lm_optimizer import LMOptimizer, _dev_f32, _unit_gravity, get_trivial_estimation
+from .lm_optimizer import LMOptimizer, _unit_gravity, get_trivial_estimation
 
 ROW = 8 + 3 + _lib.INFO_STRIDE   # packed floats per image
 
@@ -152,16 +152,12 @@ class RcclComm:
         self.nranks, self.rank, self.device = nranks, rank, device
         self._ptr = _lib.C.c_void_p()
         buf = _lib.C.create_string_buffer(unique_id, _lib.COMM_ID_BYTES)
-        rc = _lib.load().gclm_comm_create(_lib.C.byref(self._ptr), buf, nranks, rank, device)
-        if rc != 0:
-            raise _lib.GclmError(f"gclm_comm_create failed ({rc}): {_lib.load().gclm_comm_last_error(None).decode()}")
+        _call.call("gclm_comm_create", _lib.C.byref(self._ptr), buf, nranks, rank, device)
 
     @staticmethod
     def unique_id() -> bytes:
         buf = _lib.C.create_string_buffer(_lib.COMM_ID_BYTES)
-        rc = _lib.load().gclm_comm_unique_id(buf)
-        if rc != 0:
-            raise _lib.GclmError(f"gclm_comm_unique_id failed ({rc})")
+        _call.call("gclm_comm_unique_id", buf)
         return buf.raw
 
     @classmethod
@@ -171,10 +167,6 @@ class RcclComm:
         dist.broadcast_object_list(box, src=0, group=group)
         return cls(box[0], world, rank, device)
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise _lib.GclmError(f"{what} failed ({rc}): {_lib.load().gclm_comm_last_error(self._ptr).decode()}")
-
     def all_gather(self, send: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
         """(n, k) float32 rows of every rank -> (nranks * n, k), rank order; ONE collective on the current stream.
         `out`: a receive buffer kept by the caller (nothing is allocated inside a timed loop)."""
@@ -182,16 +174,14 @@ class RcclComm:
         shape = (self.nranks * send.shape[0],) + tuple(send.shape[1:])
         recv = out if out is not None else send.new_empty(shape)
         assert recv.is_contiguous() and tuple(recv.shape) == shape and recv.dtype == send.dtype
-        s = torch.cuda.current_stream(send.device).cuda_stream
-        self._check(_lib.load().gclm_comm_all_gather(self._ptr, send.data_ptr(), recv.data_ptr(), send.numel(), s),
-                    "gclm_comm_all_gather")
+        _call.call("gclm_comm_all_gather", self._ptr, send.data_ptr(), recv.data_ptr(), send.numel(),
+                   _call.raw_stream(send.device), comm=self._ptr)
         return recv
 
     def all_reduce_sum_(self, buf: torch.Tensor) -> torch.Tensor:
         assert buf.is_contiguous() and buf.dtype == torch.float32
-        s = torch.cuda.current_stream(buf.device).cuda_stream
-        self._check(_lib.load().gclm_comm_all_reduce_sum(self._ptr, buf.data_ptr(), buf.numel(), s),
-                    "gclm_comm_all_reduce_sum")
+        _call.call("gclm_comm_all_reduce_sum", self._ptr, buf.data_ptr(), buf.numel(), _call.raw_stream(buf.device),
+                   comm=self._ptr)
         return buf
 
     def __del__(self):
@@ -238,11 +228,11 @@ def calibrate_sharded(opt: LMOptimizer, local_data: Dict[str, torch.Tensor], n_t
     if not multi:
         return opt(local_data)            # one rank, no forced collective: nothing to pack, nothing to exchange
     if opt.conf.early_stop:
-        if next(iter(local_data.values())).shape[0] > opt._MAX_CALL:
+        if next(iter(local_data.values())).shape[0] > _call.MAX_CALL:
             # a shard beyond one C call is solved in slices (LMOptimizer._calibrate_chunked), each with its own sequence of
             # stop all-reduces: ranks with different slice counts would issue mismatched collectives, and the stop would
             # be per slice, not the batch's
-            raise ValueError(f"calibrate_sharded with early_stop=True is limited to {opt._MAX_CALL} images per rank "
+            raise ValueError(f"calibrate_sharded with early_stop=True is limited to {_call.MAX_CALL} images per rank "
                              "(one C call, one sequence of stop collectives): use early_stop=False or more ranks")
         # The reference's early stop is ONE decision over the whole batch (lm_optimizer.py:90-92, 619); every rank taking
         # it over its own shard would make the gathered result depend on the world size.  With an
@@ -260,7 +250,7 @@ def calibrate_sharded(opt: LMOptimizer, local_data: Dict[str, torch.Tensor], n_t
             raise ValueError("calibrate_sharded needs early_stop=False (a fixed number of steps) here: the batch-global early "
                              "stop is only shard-invariant with an RCCL communicator (`comm`, or the nccl backend)")
         stop_handle = opt._handle(next(iter(local_data.values())).device)
-        _lib.check(_lib.load().gclm_set_stop_comm(stop_handle.ptr, stop_comm._ptr), stop_handle.ptr, "gclm_set_stop_comm")
+        _call.call("gclm_set_stop_comm", stop_handle.ptr, stop_comm._ptr, handle=stop_handle.ptr)
     try:
         opt(local_data)
     finally:
@@ -293,16 +283,17 @@ class SharedIntrinsicsSplit:
         self._partials = None       # (num_groups, 32) exchange buffer, kept across calls
 
     def __call__(self, local_data: Dict[str, torch.Tensor], group_of_frame: torch.Tensor):
-        opt, lib = self.opt, _lib.load()
+        opt = self.opt
         with torch.no_grad():
             cam0, grav0 = get_trivial_estimation(local_data, opt.camera_model)
             opt.setup_optimization_and_priors(local_data, shared_intrinsics=True)
             up, lat, upc, latc, (B, H, W) = opt._fields(local_data)
             slat = opt._sin_lat(local_data, lat)
             dev = lat.device
-            h = opt._handle(dev)
-            cam = _dev_f32(cam0._data, "camera").clone()
-            grav = _dev_f32(grav0._data, "gravity").clone()
+            s = _call.raw_stream(dev)
+            h = opt._handle(dev, s)
+            cam = _call.dev_f32(cam0._data, "camera").clone()
+            grav = _call.dev_f32(grav0._data, "gravity").clone()
             gof = group_of_frame.to(device=dev, dtype=torch.int32).contiguous()
             if self._partials is None or self._partials.device != dev:
                 self._partials = torch.zeros((self.num_groups, _lib.SHARED_PARTIAL_STRIDE), dtype=torch.float32, device=dev)
@@ -320,18 +311,16 @@ class SharedIntrinsicsSplit:
                 elif multi:
                     dist.all_reduce(partials, op=dist.ReduceOp.SUM, group=self.group)
 
-            with torch.cuda.device(dev):
-                s = torch.cuda.current_stream(dev).cuda_stream
-                P = opt._ptr
-                _lib.check(lib.gclm_shared_begin_ex(h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(),
-                                                    grav.data_ptr(), gof.data_ptr(), self.num_groups, P(slat), s), h.ptr,
-                           "gclm_shared_begin_ex")
+            with torch.cuda.device(dev):       # for the collectives between the C calls (those switch to the handle's device)
+                P = _call.ptr
+                _call.call("gclm_shared_begin_ex", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(), grav.data_ptr(),
+                           gof.data_ptr(), self.num_groups, P(slat), s, handle=h.ptr)
                 for step in range(opt.num_steps):
-                    _lib.check(lib.gclm_shared_reduce(h.ptr, step, partials.data_ptr(), s), h.ptr, "gclm_shared_reduce")
+                    _call.call("gclm_shared_reduce", h.ptr, step, partials.data_ptr(), s, handle=h.ptr)
                     if self.comm is not None or multi:
                         self.timer(exchange, dev) if self.timer is not None else exchange()
-                    _lib.check(lib.gclm_shared_apply(h.ptr, step, partials.data_ptr(), s), h.ptr, "gclm_shared_apply")
-                _lib.check(lib.gclm_shared_finish(h.ptr, info.data_ptr(), s), h.ptr, "gclm_shared_finish")
+                    _call.call("gclm_shared_apply", h.ptr, step, partials.data_ptr(), s, handle=h.ptr)
+                _call.call("gclm_shared_finish", h.ptr, info.data_ptr(), s, handle=h.ptr)
         out = {"camera": cam0.__class__(cam), "gravity": Gravity(grav)}
         out.update(opt._unpack_info(info, up is not None))
         return out

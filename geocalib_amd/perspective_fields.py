@@ -19,7 +19,7 @@ from typing import Tuple
 import torch
 from torch.nn import functional as F
 
-from . import _lib, fields
+from . import _call, _lib, fields
 from .camera import BaseCamera
 from .gravity import Gravity
 
@@ -115,26 +115,17 @@ def get_perspective_field(camera: BaseCamera, gravity: Gravity, use_up: bool = T
 def _jacobian_fields(camera: BaseCamera, gravity: Gravity, spherical: bool, log_focal: bool, want_up: bool,
                      want_lat: bool):
     camera, gravity, h, w = _batched(camera, gravity)
-    cam, grav = camera._data, gravity._data
-    if not (cam.is_cuda and grav.is_cuda):
-        raise RuntimeError("geocalib_amd Jacobian fields need HIP device tensors: they are evaluated by the HIP "
-                           "extension (gclm_jacobian_fields), there is no CPU fallback")
+    cam, grav = _call.dev_f32(camera._data, "camera"), _call.dev_f32(gravity._data, "gravity")
     lead = cam.shape[:-1]
-    cam = cam.detach().reshape(-1, 8).to(torch.float32).contiguous()
-    grav = grav.detach().reshape(-1, 3).to(torch.float32).contiguous()
+    cam, grav = cam.reshape(-1, 8), grav.reshape(-1, 3)
     assert cam.shape[0] == grav.shape[0], (cam.shape, grav.shape)
     B = cam.shape[0]
     model = _lib.CAMERA_MODEL_IDS[camera.name()]
     P = 3 + (camera.num_dist_params() if hasattr(camera, "num_dist_params") else 0)
     J_up = cam.new_empty((B, h, w, 2, P)) if want_up else None
     J_lat = cam.new_empty((B, h, w, 1, P)) if want_lat else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    with torch.cuda.device(cam.device):
-        rc = _lib.load().gclm_jacobian_fields(model, cam.data_ptr(), grav.data_ptr(), B, h, w, int(spherical),
-                                              int(log_focal), ptr(J_up), ptr(J_lat),
-                                              torch.cuda.current_stream(cam.device).cuda_stream)
-    if rc != 0:
-        raise _lib.GclmError(f"gclm_jacobian_fields failed ({rc})")
+    _call.call("gclm_jacobian_fields", model, cam.data_ptr(), grav.data_ptr(), B, h, w, int(spherical), int(log_focal),
+               _call.ptr(J_up), _call.ptr(J_lat), _call.raw_stream(cam.device), device=cam.device)
     shape = lambda t: None if t is None else t.reshape(*lead, *t.shape[1:])  # noqa: E731
     return shape(J_up), shape(J_lat)
 

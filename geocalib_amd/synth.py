@@ -6,7 +6,7 @@ from typing import Dict, Tuple
 
 import torch
 
-from . import _lib
+from . import _call, _lib
 
 
 def synth_fields(camera_model: str, B: int, H: int, W: int, device, seed: int = 0, first_index: int = 0,
@@ -20,14 +20,9 @@ def synth_fields(camera_model: str, B: int, H: int, W: int, device, seed: int = 
     latc = torch.empty((B, H, W), device=device) if confidences else None
     gt_cam = torch.empty((B, 8), device=device)
     gt_grav = torch.empty((B, 3), device=device)
-    with torch.cuda.device(device):
-        rc = _lib.load().gclm_synth_fields_grouped(
-            _lib.CAMERA_MODEL_IDS[camera_model], seed, first_index, B, H, W, noise, group_size, run, run_stride,
-            up.data_ptr(), lat.data_ptr(), upc.data_ptr() if confidences else None,
-            latc.data_ptr() if confidences else None, gt_cam.data_ptr(), gt_grav.data_ptr(),
-            torch.cuda.current_stream(device).cuda_stream)
-    if rc != 0:
-        raise _lib.GclmError(f"gclm_synth_fields_grouped failed ({rc})")
+    _call.call("gclm_synth_fields_grouped", _lib.CAMERA_MODEL_IDS[camera_model], seed, first_index, B, H, W, noise, group_size,
+               run, run_stride, up.data_ptr(), lat.data_ptr(), _call.ptr(upc), _call.ptr(latc), gt_cam.data_ptr(),
+               gt_grav.data_ptr(), _call.raw_stream(device), device=device)
     data = {"up_field": up, "latitude_field": lat}
     if confidences:
         data |= {"up_confidence": upc, "latitude_confidence": latc}

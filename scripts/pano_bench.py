@@ -25,7 +25,7 @@ from torch.nn import functional as F  # noqa: E402
 
 from geocalib_amd import _lib, camera_models  # noqa: E402
 from geocalib_amd.gravity import Gravity  # noqa: E402
-from geocalib_amd.lm_optimizer import _raw_stream  # noqa: E402
+from geocalib_amd._call import raw_stream as _raw_stream  # noqa: E402
 from geocalib_amd.utils import rad2rotmat  # noqa: E402
 
 

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from geocalib_amd import Gravity, _lib, camera_models, perspective_fields as pf  # noqa: E402
-from geocalib_amd.lm_optimizer import _raw_stream  # noqa: E402
+from geocalib_amd._call import raw_stream as _raw_stream  # noqa: E402
 
 K1 = {"simple_radial": -0.3, "radial": -0.3, "simple_divisional": -0.8, "pinhole": 0.0}
 

@@ -18,7 +18,7 @@ import torch  # noqa: E402
 from torch.nn import functional as F  # noqa: E402
 
 from geocalib_amd import _lib, camera_models  # noqa: E402
-from geocalib_amd.lm_optimizer import _raw_stream  # noqa: E402
+from geocalib_amd._call import raw_stream as _raw_stream  # noqa: E402
 
 K1 = {"simple_radial": -0.3, "radial": -0.3, "simple_divisional": -0.8, "pinhole": 0.0}
 

@@ -13,7 +13,7 @@ import torch
 
 from conftest import ROOT
 
-from geocalib_amd import _lib, lm_optimizer, parallel
+from geocalib_amd import _call, _lib, lm_optimizer, parallel
 from geocalib_amd.lm_optimizer import LMOptimizer
 
 HEADER = os.path.join(ROOT, "include", "gclm.h")
@@ -99,10 +99,9 @@ class _Stream:
 def rec(monkeypatch):
     r = _Rec()
     monkeypatch.setattr(_lib, "load", lambda: r)
-    # the device check lets CPU tensors through (it still converts like the real one)
-    monkeypatch.setattr(lm_optimizer, "_dev_f32", lambda t, name: t.detach().to(torch.float32).contiguous())
-    monkeypatch.setattr(parallel, "_dev_f32", lambda t, name: t.detach().to(torch.float32).contiguous())
-    monkeypatch.setattr(lm_optimizer, "_raw_stream", lambda device: 0)
+    # the one device check lets CPU tensors through (the conversion around it stays the real one)
+    monkeypatch.setattr(_call, "require_device", lambda t, name: None)
+    monkeypatch.setattr(_call, "raw_stream", lambda device: 0)
     monkeypatch.setattr(LMOptimizer, "_handle", lambda self, device, stream=None: types.SimpleNamespace(ptr=C.c_void_p(1)))
     monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: _Stream())
     monkeypatch.setattr(torch.cuda, "Stream", _Stream)
@@ -174,7 +173,7 @@ def test_sin_latitude_is_checked_like_the_fields(monkeypatch):
     lat = torch.zeros(2, 1, 4, 4)
     with pytest.raises(RuntimeError, match="`sin_latitude` must live on a HIP device"):
         LMOptimizer._sin_lat({"sin_latitude": torch.zeros(2, 1, 4, 4)}, lat)
-    monkeypatch.setattr(lm_optimizer, "_dev_f32", lambda t, name: t)
+    monkeypatch.setattr(_call, "require_device", lambda t, name: None)
     with pytest.raises(ValueError, match="shape of `latitude_field`"):
         LMOptimizer._sin_lat({"sin_latitude": torch.zeros(2, 1, 4, 5)}, lat)
     assert LMOptimizer._sin_lat({}, lat) is None
