@@ -2,7 +2,7 @@
 //
 // A solve is 2*num_steps+4 asynchronous launches on the caller's stream and no host round trip (nor memset):
 //   init | { sweep(theta_i) ; update_i } x num_steps | prep_final ; sweep(theta_final, rpf) ; finalize
-// and num_steps+2 for a single image (one launch per LM step, use_fused; the first launch builds theta_0 itself):
+// and num_steps+2 for a single image (one launch per LM step, make_plan; the first launch builds theta_0 itself):
 //   fused(step) x num_steps | fused(final) | finalize
 // (the reference syncs twice per step: H,G -> CPU Cholesky -> device, and torch.allclose).
 #include <chrono>
@@ -20,7 +20,7 @@
 using namespace gclm;
 
 #ifndef GCLM_FUSED_MAX_WORKGROUPS
-#define GCLM_FUSED_MAX_WORKGROUPS 768      // B * workgroups-per-image up to which an LM step is ONE launch (see use_fused):
+#define GCLM_FUSED_MAX_WORKGROUPS 768      // B * workgroups-per-image up to which an LM step is ONE launch (see choose_walk):
                                            // measured with round 4's prologue (profiles/archive/r04_fused_threshold.log, 20 fixed steps) --
                                            // 640x480 (150 workgroups per image): B = 2 -19 %, 4 -15 %, 6 +-0, 8 +6 %, 12 +15 %;
                                            // 320x240 (38 per image): B = 2 ... 12 -20 ... -27 %
@@ -31,6 +31,34 @@ using namespace gclm;
 #ifndef GCLM_ISO_FINAL
 #define GCLM_ISO_FINAL 1      // A/B switch: 0 = the final sweep always takes the general focal column
 #endif
+
+namespace {
+
+bool is_aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// The field planes of one call (device pointers; every one but `lat` may be null)
+struct Fields {
+    const float *up = nullptr, *lat = nullptr, *upc = nullptr, *latc = nullptr;
+    bool five() const { return up && upc && latc; }       // a complete field set: (B,2,H,W) + four (B,H,W) planes
+    bool aligned16() const { return is_aligned16(up) && is_aligned16(lat) && is_aligned16(upc) && is_aligned16(latc); }
+};
+
+// Everything decided ONCE per call about its sweeps (make_plan): how they walk the image, whether an LM step is one launch,
+// and which plane of sin(latitude) they read.  A solve keeps it as a local; the split shared-intrinsics session keeps it
+// on the handle between its calls (gclm_handle::sh).
+struct Plan {
+    Fields f;
+    Geometry geo{};                 // the one-row walk, or row pairs (geo.mirror)
+    bool one_launch = false;        // an LM step is ONE launch (gclm_pass.hip: fused_step_kernel); never with row pairs
+    const float* given = nullptr;   // the caller's plane of sin(latitude) every sweep reads in place of `lat`, or null
+    float* slat = nullptr;          // else the library's scratch plane (gclm_handle::slat_buf), or null: sweeps compute sin(latitude)
+    bool slat_filled = false;       // ... which the first sweep fills and the later ones read (next_sweep)
+
+    void choose_walk(const gclm_handle* h, int B, int H, int W, bool aligned16, bool five);
+    SweepArgs next_sweep(const gclm_handle* h, const PBlock* pb, bool loop_params, int stop_step);
+};
+
+}  // namespace
 
 struct gclm_handle {
     gclm_config cfg;
@@ -45,11 +73,8 @@ struct gclm_handle {
     // split shared-intrinsics session
     struct {
         bool active = false;
-        const float *up = nullptr, *lat = nullptr, *upc = nullptr, *latc = nullptr;
+        Plan plan;                  // of gclm_shared_begin: every gclm_shared_reduce and gclm_shared_finish takes its next sweep from it
         float *cam_io = nullptr, *grav_io = nullptr;
-        Geometry geo{};
-        bool slat_ready = false;    // the scratch plane holds sin(latitude) of this session's fields
-        const float* given = nullptr;   // the caller's plane of sin(latitude) these sweeps read (handed_slat), or null
     } sh;
     // The sin(latitude) scratch plane is an allocation of its own, of exactly the size asked for (no headroom), and the only
     // part of the workspace a solve can do without: see ensure_slat.
@@ -58,7 +83,6 @@ struct gclm_handle {
     size_t slat_refused = 0;        // smallest plane size (bytes) whose allocation failed or was refused by the limit since the
                                     // last change of the limit / mode: such a size is not tried again on every solve
     size_t slat_limit = 0;          // gclm_set_slat_plane_limit: 0 = built-in rule (half of the free device memory), else bytes
-    float* slat = nullptr;          // the plane of the CURRENT solve / session (== slat_buf), or null: sweeps compute sin(latitude)
     int slat_plane = -1;            // gclm_set_slat_plane: -1 = built-in choice, 0 = never, 1 = wherever the sweep has it
     int row_pairs = GCLM_ROW_PAIRS_DEFAULT;   // gclm_set_row_pairs: -1 = built-in choice, 0 = never, 1 = wherever the sweep has the row-pair walk
     int sweep_iters = 0;            // gclm_set_sweep_iters: 0 = built-in choice
@@ -138,8 +162,6 @@ struct DeviceGuard {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-bool is_aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A null pointer names no range.
 bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
     const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
@@ -183,26 +205,25 @@ int ensure_workspace(gclm_handle* h, int B, int nchunks, int G) {
     return 0;
 }
 
-// The sin(latitude) scratch plane of a solve of `floats` pixels (0: none wanted): h->slat = the plane, or null when the solve
+// The sin(latitude) scratch plane of a solve of `floats` pixels (0: none wanted): returns the plane, or null when the solve
 // runs without it -- never an error.  The plane only saves arithmetic (gclm_pass.hip: row_math, SLAT); a sweep that computes
 // sin(latitude) itself produces the same bits, so whenever the plane cannot be had -- hipMalloc fails, or the plane is larger
 // than the limit (gclm_set_slat_plane_limit; built-in: half of the device memory that is free once the old plane is
 // released) -- the solve goes on without it, as the library did before it had the plane.  Exact size, no headroom: the plane
 // is 400x the rest of the workspace.  A size that was refused is remembered (slat_refused) so that a serving loop does not
 // pay a failing hipMalloc (and its device synchronisation) per call.
-void ensure_slat(gclm_handle* h, size_t floats) {
-    h->slat = nullptr;
-    if (floats == 0) return;
+float* ensure_slat(gclm_handle* h, size_t floats) {
+    if (floats == 0) return nullptr;
     const size_t bytes = floats * sizeof(float);
-    if (bytes <= h->slat_bytes) { h->slat = h->slat_buf; return; }
-    if (h->slat_refused && bytes >= h->slat_refused) return;
-    if (h->slat_limit && bytes > h->slat_limit) { h->slat_refused = bytes; return; }     // (the old, smaller plane stays)
+    if (bytes <= h->slat_bytes) return h->slat_buf;
+    if (h->slat_refused && bytes >= h->slat_refused) return nullptr;
+    if (h->slat_limit && bytes > h->slat_limit) { h->slat_refused = bytes; return nullptr; }     // (the old, smaller plane stays)
     if (!h->slat_limit) {                     // built-in rule: half of what is free once the old plane is released
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > (free_b + h->slat_bytes) / 2) {
             (void)hipGetLastError();
             h->slat_refused = bytes;          // (the old, smaller plane stays here too)
-            return;
+            return nullptr;
         }
     }
     if (h->slat_buf) (void)hipFree(h->slat_buf);
@@ -213,90 +234,11 @@ void ensure_slat(gclm_handle* h, size_t floats) {
     if (!ok) {
         (void)hipGetLastError();          // the failure is handled here: it must not surface in the next launch's status
         h->slat_refused = bytes;
-        return;
+        return nullptr;
     }
     h->slat_buf = static_cast<float*>(p);
     h->slat_bytes = bytes;
-    h->slat = h->slat_buf;
-}
-
-// Does this solve keep sin(latitude_field) in a scratch plane (gclm_pass.hip: row_math, SLAT)?  Built-in choice: the
-// VALU-bound distortion models, on the five-plane float4 sweep, whenever at least one loop sweep precedes the final one.
-// Pinhole never (memory-bound: the plane's extra write costs what the saved arithmetic gains); not the one-launch-per-step
-// path (latency-bound, a handful of workgroups).
-bool slat_wanted(const gclm_handle* h, const float* up, const float* upc, const float* latc, const Geometry& g, bool fused) {
-    if (h->slat_plane == 0 || fused || g.vec != 4 || !up || !upc || !latc || h->cfg.num_steps < 1) return false;
-    if (h->slat_plane < 0 && h->cfg.camera_model == GCLM_PINHOLE) return false;
-    return sweep_has_slat_plane(h->cfg.camera_model);
-}
-
-// The plane of sin(latitude_field) a caller handed (gclm_solve_ex, gclm_calibrate_ex, gclm_shared_begin_ex) that this
-// solve's sweeps read in place of `lat`, from the first sweep on -- or null: they read the radians, as without the plane.
-// Read by the five-plane float4 sweeps of the distortion models (one-row and row-pair walks) and by the five-plane
-// one-launch-per-step kernel of every model; ignored by pinhole's batch sweeps (memory-bound: the review keeps that kernel
-// as it is), the scalar path, four-plane and latitude-only sweeps, and a plane whose 16-byte alignment differs from the
-// other planes' (include/gclm.h says so).  Such a solve never wants the library's own plane.
-const float* handed_slat(const gclm_handle* h, const float* sl, const float* up, const float* upc, const float* latc,
-                         const Geometry& g, bool fused) {
-    if (!sl || g.vec != 4 || !is_aligned16(sl) || !up || !upc || !latc) return nullptr;
-    if (!fused && h->cfg.camera_model == GCLM_PINHOLE) return nullptr;
-    return sl;
-}
-
-// The sweep arguments of the next sweep of a solve that reads the caller's plane (every sweep: SLAT = 2), or that keeps the
-// scratch plane: the first one fills it, the others read it
-void apply_slat(const gclm_handle* h, SweepArgs& a, bool& ready, const float* given) {
-    if (given) {
-        a.slat = const_cast<float*>(given);     // (slat_mode 2 never writes through it)
-        a.lat = given;
-        a.slat_mode = 2;
-        return;
-    }
-    if (!h->slat) return;
-    a.slat = h->slat;
-    if (ready) { a.slat_mode = 2; a.lat = h->slat; }
-    else { a.slat_mode = 1; ready = true; }
-}
-
-// Does a sweep over these planes take the row-pair walk (gclm_pass.hip: row_math_mirror)?  radial / simple_divisional on the
-// five-plane float4 sweep over an even number of rows; never the one-launch-per-step path (its geometry, its prefetch).
-bool mirror_wanted(const gclm_handle* h, bool five_planes, const Geometry& g, int H) {
-    if (h->row_pairs == 0 || g.vec != 4 || !five_planes || (H & 1) || H < 4) return false;
-    return h->row_pairs > 0 ? sweep_has_mirror(h->cfg.camera_model) : sweep_mirror_builtin(h->cfg.camera_model);
-}
-
-bool use_fused(const gclm_handle* h, int B, const Geometry& g);
-
-// The geometry of this call's sweeps: the one-row walk, or -- where the sweep has it and the step is not one launch -- row pairs
-Geometry plan_sweeps(const gclm_handle* h, int B, int H, int W, bool aligned16, bool five_planes) {
-    const Geometry g = plan_geometry(B, H, W, aligned16, h->sweep_iters, h->cfg.camera_model);
-    if (!mirror_wanted(h, five_planes, g, H)) return g;
-    if (h->row_pairs < 0) {
-        // built-in choice: only launches too large for one launch per step, WHETHER OR NOT that path is valid for the call
-        // (early stop over several images, gclm_set_fused_steps(h, 0)): below the threshold a step is latency-bound, and the
-        // two-launch sequence stays the one-launch path's twin bit for bit
-        if ((long long)B * g.nchunks <= GCLM_FUSED_MAX_WORKGROUPS) return g;
-    } else if (h->fused_mode == 1 && use_fused(h, B, g)) {
-        return g;                    // asked for both: the step that can be ONE launch stays one launch
-    }
-    return plan_geometry(B, H, W, aligned16, h->sweep_iters, h->cfg.camera_model, true);
-}
-
-SweepArgs sweep_args(const gclm_handle* h, const float* up, const float* lat, const float* upc, const float* latc,
-                     const PBlock* pb, const Geometry& g, bool loop_params, int stop_step) {
-    SweepArgs a{};
-    a.up = up; a.lat = lat; a.upc = up ? upc : nullptr; a.latc = latc;
-    a.pb = pb; a.ctrl = h->ctx.ctrl; a.partials = h->ctx.partials;
-    a.B = h->ctx.B; a.H = h->ctx.H; a.W = h->ctx.W;
-    a.nchunks = g.nchunks; a.vec = g.vec;
-    a.wu = g.wu; a.cu = g.cu; a.nstrips = g.nstrips; a.rpi = g.rpi; a.rows_per_block = g.rows_per_block; a.wpt = g.wpt; a.jobs = g.jobs;
-    a.hrows = g.hrows; a.mirror = g.mirror;
-    // loop sweeps: the configured parametrisation; final sweep: the (roll, pitch, focal) block, in its log-focal form when
-    // every image is known to have fx == fy (iso_final: finalize_kernel rescales the focal column)
-    a.log_focal = loop_params ? h->cfg.use_log_focal : h->ctx.iso_final;
-    a.stop_step = stop_step;
-    a.up_scale = h->cfg.up_loss_fn_scale; a.lat_scale = h->cfg.lat_loss_fn_scale;
-    return a;
+    return h->slat_buf;
 }
 
 int timed_sweep(gclm_handle* h, const SweepArgs& a, hipStream_t s, const FusedArgs* fused = nullptr) {
@@ -319,20 +261,8 @@ int timed_sweep(gclm_handle* h, const SweepArgs& a, hipStream_t s, const FusedAr
     return 0;
 }
 
-// One launch per LM step (gclm_pass.hip: fused_step_kernel) pays when a step is bound by its two dependent launches
-// rather than by the sweep: few workgroups in flight.  It is VALID when the early-stop decision is local to a
-// workgroup (one image) or off, for independent intrinsics on the float4 path.
-bool use_fused(const gclm_handle* h, int B, const Geometry& g) {
-    const gclm_config& c = h->cfg;
-    const bool valid = !c.shared_intrinsics && g.vec == 4 && (B == 1 || !c.early_stop) && B > 0 &&
-                       !(c.early_stop && h->stop_comm);       // a stop that spans ranks is never local to a workgroup
-    if (!valid || h->fused_mode == 0) return false;
-    if (h->fused_mode == 1) return true;
-    return (long long)B * g.nchunks <= GCLM_FUSED_MAX_WORKGROUPS;
-}
-
 int check_shapes(gclm_handle* h, const float* lat, int B, int H, int W) {
-    // (an EMPTY batch has no fields: a zero-size device tensor's pointer is NULL -- run_solve's B == 0 branch)
+    // (an EMPTY batch has no fields: a zero-size device tensor's pointer is NULL -- solve_empty_shard)
     if (!lat && B != 0) return fail(h, -3, "latitude_field is required (lm_optimizer.py:31 raises KeyError without it)");
     if (B < 0 || H <= 0 || W <= 0) return fail(h, -3, "bad shape B=%d H=%d W=%d", B, H, W);
     if (B > 65535) return fail(h, -3, "batch %d exceeds 65535 images per call (grid.y): split the batch", B);
@@ -349,6 +279,225 @@ int setup_groups(gclm_handle* h, int B) {
     c.group_size = gs;
     c.n_groups = B / gs;
     return 0;
+}
+
+// How this call's sweeps walk the image, as ONE decision: one launch per LM step | row pairs | the one-row walk.
+//  * One launch per LM step (gclm_pass.hip: fused_step_kernel) pays when a step is bound by its two dependent launches
+//    rather than by the sweep: few workgroups in flight (GCLM_FUSED_MAX_WORKGROUPS).  It is VALID when the early-stop
+//    decision is local to a workgroup (one image) or off, for independent intrinsics on the float4 path.
+//  * Row pairs (gclm_pass.hip: row_math_mirror): radial / simple_divisional on the five-plane float4 sweep over an even
+//    number of rows; never the one-launch-per-step path (its geometry, its prefetch).
+void Plan::choose_walk(const gclm_handle* h, int B, int H, int W, bool aligned16, bool five) {
+    const gclm_config& c = h->cfg;
+    geo = plan_geometry(B, H, W, aligned16, h->sweep_iters, c.camera_model);
+    const bool few = (long long)B * geo.nchunks <= GCLM_FUSED_MAX_WORKGROUPS;
+    const bool fusable = !c.shared_intrinsics && geo.vec == 4 && (B == 1 || !c.early_stop) && B > 0 &&
+                         !(c.early_stop && h->stop_comm);       // a stop that spans ranks is never local to a workgroup
+    const bool pairable = geo.vec == 4 && five && !(H & 1) && H >= 4 &&
+                          (h->row_pairs > 0 ? sweep_has_mirror(c.camera_model) : sweep_mirror_builtin(c.camera_model));
+    bool pairs = false;
+    if (pairable && h->row_pairs < 0) {
+        // built-in choice: only launches too large for one launch per step, WHETHER OR NOT that path is valid for the call
+        // (early stop over several images, gclm_set_fused_steps(h, 0)): below the threshold a step is latency-bound, and the
+        // two-launch sequence stays the one-launch path's twin bit for bit
+        pairs = !few;
+    } else if (pairable && h->row_pairs > 0) {
+        pairs = !(h->fused_mode == 1 && fusable);    // asked for both: the step that can be ONE launch stays one launch
+    }
+    one_launch = !pairs && fusable && (h->fused_mode == 1 || (h->fused_mode < 0 && few));
+    if (pairs) geo = plan_geometry(B, H, W, aligned16, h->sweep_iters, c.camera_model, true);
+}
+
+// The one preamble of gclm_solve / gclm_calibrate, gclm_system and gclm_shared_begin: the plan of a call that runs `sweeps`
+// sweeps over fields `f` of B images (0: an empty shard of a session, planned as one image), the sizes in h->ctx and the
+// workspace.  The caller has set the group fields and iso_final of h->ctx.  `sin_lat`: the plane the caller handed, or null.
+int make_plan(gclm_handle* h, Plan& p, const Fields& f, int B, int H, int W, const float* sin_lat, int sweeps) {
+    const int Bp = B > 0 ? B : 1, model = h->cfg.camera_model;
+    p = Plan{};
+    p.f = f;
+    p.choose_walk(h, Bp, H, W, f.aligned16(), f.five());
+    SolveCtx& c = h->ctx;
+    c.cfg = h->cfg;
+    c.B = B; c.H = H; c.W = W; c.nchunks = p.geo.nchunks;
+    const bool float4_five = p.geo.vec == 4 && f.five();
+    // The plane of sin(latitude_field) a caller handed (gclm_solve_ex, gclm_calibrate_ex, gclm_shared_begin_ex) that this
+    // solve's sweeps read in place of `lat`, from the first sweep on -- or null: they read the radians, as without the plane.
+    // Read by the five-plane float4 sweeps of the distortion models (one-row and row-pair walks) and by the five-plane
+    // one-launch-per-step kernel of every model; ignored by pinhole's batch sweeps (memory-bound: the review keeps that kernel
+    // as it is), the scalar path, four-plane and latitude-only sweeps, and a plane whose 16-byte alignment differs from the
+    // other planes' (include/gclm.h says so).  Such a solve never wants the library's own plane.
+    if (sin_lat && float4_five && is_aligned16(sin_lat) && (p.one_launch || model != GCLM_PINHOLE)) p.given = sin_lat;
+    // Does this solve keep sin(latitude_field) in a scratch plane of its own (gclm_pass.hip: row_math, SLAT)?  Built-in choice:
+    // the VALU-bound distortion models, on the five-plane float4 sweep, whenever at least one loop sweep precedes the final one.
+    // Pinhole never (memory-bound: the plane's extra write costs what the saved arithmetic gains); not the one-launch-per-step
+    // path (latency-bound, a handful of workgroups).
+    const bool keep = !p.given && h->slat_plane != 0 && !p.one_launch && float4_five && sweeps >= 2 &&
+                      !(h->slat_plane < 0 && model == GCLM_PINHOLE) && sweep_has_slat_plane(model);
+    if (int rc = ensure_workspace(h, Bp, p.geo.nchunks, c.n_groups)) return rc;
+    p.slat = ensure_slat(h, keep ? (size_t)B * H * W : 0);
+    h->sh.active = false;
+    return 0;
+}
+
+// The arguments of the plan's next sweep with parameter blocks `pb`.  A solve that reads the caller's plane: every sweep
+// loads it (SLAT = 2); one that keeps the scratch plane: the first sweep fills it, the others read it.
+SweepArgs Plan::next_sweep(const gclm_handle* h, const PBlock* pb, bool loop_params, int stop_step) {
+    SweepArgs a{};
+    a.up = f.up; a.lat = f.lat; a.upc = f.up ? f.upc : nullptr; a.latc = f.latc;
+    a.pb = pb; a.ctrl = h->ctx.ctrl; a.partials = h->ctx.partials;
+    a.B = h->ctx.B; a.H = h->ctx.H; a.W = h->ctx.W;
+    a.nchunks = geo.nchunks; a.vec = geo.vec;
+    a.wu = geo.wu; a.cu = geo.cu; a.nstrips = geo.nstrips; a.rpi = geo.rpi; a.rows_per_block = geo.rows_per_block; a.wpt = geo.wpt; a.jobs = geo.jobs;
+    a.hrows = geo.hrows; a.mirror = geo.mirror;
+    // loop sweeps: the configured parametrisation; final sweep: the (roll, pitch, focal) block, in its log-focal form when
+    // every image is known to have fx == fy (iso_final: finalize_kernel rescales the focal column)
+    a.log_focal = loop_params ? h->cfg.use_log_focal : h->ctx.iso_final;
+    a.stop_step = stop_step;
+    a.up_scale = h->cfg.up_loss_fn_scale; a.lat_scale = h->cfg.lat_loss_fn_scale;
+    if (given) {
+        a.slat = const_cast<float*>(given);     // (slat_mode 2 never writes through it)
+        a.lat = given;
+        a.slat_mode = 2;
+    } else if (slat) {
+        a.slat = slat;
+        if (slat_filled) a.lat = slat;
+        a.slat_mode = slat_filled ? 2 : 1;
+        slat_filled = true;
+    }
+    return a;
+}
+
+// Paced launches (single image with early stop): the launches after the stop are skipped on the device, but each
+// still costs its turn on the queue (2.3 us x 21 of a default-conf solve).  Launch k is therefore only issued
+// once launch k - depth has reported (a word in host-mapped memory), and none once the stop is reported.  What
+// the host sees only decides how many launches it issues: the device-side skip stays in force, so a late or
+// missing report costs time, never correctness; the wait is bounded (kPacedPatienceUs, then a cool-down).
+struct Pacer {
+    gclm_handle* h;
+    bool paced;                 // the launches of this solve report (FusedArgs::progress) ...
+    bool waiting;               // ... and the host still waits for them
+    bool stop_seen = false;     // a report said that the early stop fired: no further loop launch is issued
+
+    // begin a solve: a new epoch in the progress word, unless the handle is cooling down after a wait that timed out
+    Pacer(gclm_handle* handle, bool single_image_early_stop)
+        : h(handle), paced(handle->paced_depth > 0 && single_image_early_stop && handle->progress_host) {
+        if (paced && h->paced_cooldown > 0) { --h->paced_cooldown; paced = false; }
+        if (paced) h->epoch = (h->epoch + 1) & kPacedEpochMask;
+        waiting = paced;
+    }
+    bool reported(int launch) {          // has `launch` (or a later one) of THIS solve reported?  sets stop_seen
+        const unsigned v = __atomic_load_n(h->progress_host, __ATOMIC_ACQUIRE);
+        if (((v >> kPacedEpochShift) & kPacedEpochMask) != h->epoch) return false;
+        if (v & kPacedStopBit) stop_seen = true;
+        return stop_seen || (v & 0xffffu) >= (unsigned)(launch + 1);
+    }
+    // before loop launch `step` is issued: wait for launch step - depth.
+    // A launch of this solve reports within a few microseconds of the previous one when the queue is ours.
+    // Spin briefly (the common case), then yield the core between polls; give up after kPacedPatienceUs.
+    // A queue backed up by other streams (a serving loop overlapping the CNN with the LM) trips that: the rest
+    // of THIS solve is issued unpaced, and the handle stops pacing for the next kPacedCooldown solves instead
+    // of burning the patience on every call.
+    void wait_before(int step) {
+        if (!waiting || step < h->paced_depth) return;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spin = 0; !reported(step - h->paced_depth); ++spin) {
+            if (spin < 256) continue;
+            std::this_thread::yield();
+            if ((spin & 0xf) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kPacedPatienceUs)) {
+                waiting = false;
+                h->paced_cooldown = kPacedCooldown;
+                break;
+            }
+        }
+    }
+};
+
+// an empty shard still owes its peers the per-step collectives of a rank-spanning early stop (zero counters)
+int solve_empty_shard(gclm_handle* h, int H, int W, const InitArgs& ia, hipStream_t s) {
+    if (!(h->cfg.early_stop && h->stop_comm && h->cfg.num_steps > 1)) return 0;
+    DeviceGuard guard(h->device);
+    GCLM_HIP(h, guard.status);
+    SolveCtx& c = h->ctx;
+    c.cfg = h->cfg;
+    c.B = 0; c.H = H; c.W = W; c.nchunks = 1; c.n_groups = 0; c.group_size = 1; c.group_of_frame = nullptr;
+    if (int rc = ensure_workspace(h, 1, 1, 0)) return rc;
+    GCLM_HIP(h, launch_init(c, ia, s));                               // thread 0 resets the counters
+    for (int step = 1; step < h->cfg.num_steps; ++step)
+        if (gclm_comm_all_reduce_sum_i32(h->stop_comm, &c.ctrl->notclose[step], 1, s) != 0)
+            return fail(h, -20, "early-stop all-reduce failed: %s", gclm_comm_last_error(h->stop_comm));
+    return 0;
+}
+
+// fused(step) x num_steps | fused(final) | finalize : num_steps + 2 launches, partial records double-buffered
+// (the first launch builds theta_0 itself: no init launch)
+int solve_one_launch_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, float* d_cam_out, float* d_grav_out,
+                              float* d_info_out, hipStream_t s) {
+    const SolveCtx& c = h->ctx;
+    float* const part[2] = {c.partials, c.partials2};
+    Pacer pacer(h, h->cfg.early_stop && c.B == 1);
+    for (int step = 0; step <= h->cfg.num_steps; ++step) {
+        const bool fin = step == h->cfg.num_steps;
+        if (!fin) pacer.wait_before(step);
+        if (pacer.stop_seen && !fin) continue;       // the final launch finds the stop in the counters, as it always does
+        SweepArgs a = p.next_sweep(h, c.pb[0], !fin, 0);        // (never the library's plane here: make_plan)
+        a.partials = part[step & 1];
+        FusedArgs f;
+        f.c = c;
+        f.step = step;
+        f.is_final = fin ? 1 : 0;
+        f.partials_in = part[(step + 1) & 1];
+        f.progress = (pacer.paced && !fin) ? h->progress_dev : nullptr;
+        f.epoch = h->epoch;
+        f.ia = ia;
+        f.init_here = step == 0 ? 1 : 0;
+        if (int rc = timed_sweep(h, a, s, &f)) return rc;
+    }
+    SolveCtx cf = c;
+    cf.partials = part[h->cfg.num_steps & 1];        // the final sweep's records
+    GCLM_HIP(h, launch_finalize(cf, d_cam_out, d_grav_out, d_info_out, s));
+    return 0;
+}
+
+// init | { sweep(theta_i) ; update_i } x num_steps | prep_final ; sweep(theta_final, rpf) ; finalize
+int solve_two_launches_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, float* d_cam_out, float* d_grav_out,
+                                float* d_info_out, hipStream_t s) {
+    const SolveCtx& c = h->ctx;
+    const bool es = h->cfg.early_stop != 0;
+    GCLM_HIP(h, launch_init(c, ia, s));
+    for (int step = 0; step < h->cfg.num_steps; ++step) {
+        if (int rc = timed_sweep(h, p.next_sweep(h, c.pb[step & 1], true, es ? step : 0), s)) return rc;
+        if (!h->cfg.shared_intrinsics) {
+            GCLM_HIP(h, launch_update(c, step, s));
+        } else {
+            GCLM_HIP(h, launch_shared_step(c, step, s));     // reduce + Schur solve + update: one launch
+        }
+        // a batch sharded over ranks: "whose cost still moved" is a count over ALL ranks' images (every step, also after
+        // the stop -- the counters of skipped steps stay 0 everywhere -- so that the ranks' collectives keep matching)
+        if (es && h->stop_comm && step >= 1)
+            if (gclm_comm_all_reduce_sum_i32(h->stop_comm, &c.ctrl->notclose[step], 1, s) != 0)
+                return fail(h, -20, "early-stop all-reduce failed: %s", gclm_comm_last_error(h->stop_comm));
+    }
+    GCLM_HIP(h, launch_prep_final(c, s));
+    if (int rc = timed_sweep(h, p.next_sweep(h, c.pb_final, false, 0), s)) return rc;
+    GCLM_HIP(h, launch_finalize(c, d_cam_out, d_grav_out, d_info_out, s));
+    return 0;
+}
+
+int run_solve(gclm_handle* h, const Fields& f, int B, int H, int W, const InitArgs& ia, float* d_cam_out,
+              float* d_grav_out, float* d_info_out, const float* d_sin_lat, void* stream) {
+    if (int rc = check_shapes(h, f.lat, B, H, W)) return rc;
+    if (B > 0 && (!d_cam_out || !d_grav_out || !d_info_out)) return fail(h, -3, "null output pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (B == 0) return solve_empty_shard(h, H, W, ia, s);
+    DeviceGuard guard(h->device);
+    GCLM_HIP(h, guard.status);
+    if (int rc = setup_groups(h, B)) return rc;
+    // trivial / heuristic initial estimate without `scales`: fx == fy at the start, and update_focal keeps the ratio
+    // (camera.py:148) -- the final sweep may then run the cheaper log-focal instantiation (see finalize_kernel)
+    h->ctx.iso_final = (ia.cam == nullptr && ia.scales == nullptr && GCLM_ISO_FINAL) ? 1 : 0;
+    Plan p;
+    if (int rc = make_plan(h, p, f, B, H, W, d_sin_lat, h->cfg.num_steps + 1)) return rc;
+    return (p.one_launch ? solve_one_launch_per_step : solve_two_launches_per_step)(h, p, ia, d_cam_out, d_grav_out, d_info_out, s);
 }
 
 }  // namespace
@@ -504,7 +653,7 @@ int gclm_release_workspace(gclm_handle* h) {
     h->ctx = SolveCtx{};
     h->group_partials = nullptr;
     if (h->slat_buf) GCLM_HIP(h, hipFree(h->slat_buf));
-    h->slat_buf = h->slat = nullptr;
+    h->slat_buf = nullptr;
     h->slat_bytes = h->slat_refused = 0;
     return 0;
 }
@@ -520,9 +669,10 @@ int gclm_set_sweep_iters(gclm_handle* h, int iters) {
 int gclm_plan_cut(const gclm_handle* h, int B, int H, int W, int aligned16, int* rows_per_chunk, int* chunks_per_image) {
     if (!h) return -1;
     if (B < 1 || H < 1 || W < 1) return -3;
-    const Geometry geo = plan_sweeps(h, B, H, W, aligned16 != 0, true);       // (as for the five planes of a complete field set)
-    if (rows_per_chunk) *rows_per_chunk = geo.rows_per_block;
-    if (chunks_per_image) *chunks_per_image = geo.nchunks;
+    Plan p;
+    p.choose_walk(h, B, H, W, aligned16 != 0, true);       // (as for the five planes of a complete field set)
+    if (rows_per_chunk) *rows_per_chunk = p.geo.rows_per_block;
+    if (chunks_per_image) *chunks_per_image = p.geo.nchunks;
     return 0;
 }
 
@@ -628,130 +778,6 @@ int gclm_last_pass_timing(gclm_handle* h, int* n_launches, float* total_ms) {
     return 0;
 }
 
-static int run_solve(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
-                     const float* d_lat_conf, int B, int H, int W, const InitArgs& ia, float* d_cam_out,
-                     float* d_grav_out, float* d_info_out, const float* d_sin_lat, void* stream) {
-    if (int rc = check_shapes(h, d_lat, B, H, W)) return rc;
-    if (B > 0 && (!d_cam_out || !d_grav_out || !d_info_out)) return fail(h, -3, "null output pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (B == 0) {
-        // an empty shard still owes its peers the per-step collectives of a rank-spanning early stop (zero counters)
-        if (h->cfg.early_stop && h->stop_comm && h->cfg.num_steps > 1) {
-            DeviceGuard guard0(h->device);
-            GCLM_HIP(h, guard0.status);
-            SolveCtx& c0 = h->ctx;
-            c0.cfg = h->cfg;
-            c0.B = 0; c0.H = H; c0.W = W; c0.nchunks = 1; c0.n_groups = 0; c0.group_size = 1; c0.group_of_frame = nullptr;
-            if (int rc = ensure_workspace(h, 1, 1, 0)) return rc;
-            GCLM_HIP(h, launch_init(c0, ia, s));                               // thread 0 resets the counters
-            for (int step = 1; step < h->cfg.num_steps; ++step)
-                if (gclm_comm_all_reduce_sum_i32(h->stop_comm, &c0.ctrl->notclose[step], 1, s) != 0)
-                    return fail(h, -20, "early-stop all-reduce failed: %s", gclm_comm_last_error(h->stop_comm));
-        }
-        return 0;
-    }
-    DeviceGuard guard(h->device);
-    GCLM_HIP(h, guard.status);
-    const bool al = is_aligned16(d_up) && is_aligned16(d_lat) && is_aligned16(d_up_conf) && is_aligned16(d_lat_conf);
-    const Geometry geo = plan_sweeps(h, B, H, W, al, d_up && d_up_conf && d_lat_conf);
-    SolveCtx& c = h->ctx;
-    c.cfg = h->cfg;
-    c.B = B; c.H = H; c.W = W; c.nchunks = geo.nchunks;
-    // trivial / heuristic initial estimate without `scales`: fx == fy at the start, and update_focal keeps the ratio
-    // (camera.py:148) -- the final sweep may then run the cheaper log-focal instantiation (see finalize_kernel)
-    c.iso_final = (ia.cam == nullptr && ia.scales == nullptr && GCLM_ISO_FINAL) ? 1 : 0;
-    if (int rc = setup_groups(h, B)) return rc;
-    const bool es = h->cfg.early_stop != 0;
-    const bool fused_path = !geo.mirror && use_fused(h, B, geo);      // (plan_sweeps only pairs rows where the step is not one launch)
-    const float* given = handed_slat(h, d_sin_lat, d_up, d_up_conf, d_lat_conf, geo, fused_path);
-    const bool keep_slat = !given && slat_wanted(h, d_up, d_up_conf, d_lat_conf, geo, fused_path);
-    if (int rc = ensure_workspace(h, B, geo.nchunks, c.n_groups)) return rc;
-    ensure_slat(h, keep_slat ? (size_t)B * H * W : 0);
-    h->sh.active = false;
-    bool slat_ready = false;
-
-    if (!fused_path) GCLM_HIP(h, launch_init(c, ia, s));      // (the one-launch-per-step path builds theta_0 in its first launch)
-    if (fused_path) {
-        // fused(step) x num_steps | fused(final) | finalize : num_steps + 2 launches, partial records double-buffered
-        float* const part[2] = {c.partials, c.partials2};
-        // Paced launches (single image with early stop): the launches after the stop are skipped on the device, but each
-        // still costs its turn on the queue (2.3 us x 21 of a default-conf solve).  Launch k is therefore only issued
-        // once launch k - depth has reported (a word in host-mapped memory), and none once the stop is reported.  What
-        // the host sees only decides how many launches it issues: the device-side skip stays in force, so a late or
-        // missing report costs time, never correctness; the wait is bounded (kPacedPatienceUs, then a cool-down).
-        bool paced = h->paced_depth > 0 && es && B == 1 && h->progress_host;
-        if (paced && h->paced_cooldown > 0) { --h->paced_cooldown; paced = false; }
-        if (paced) h->epoch = (h->epoch + 1) & kPacedEpochMask;
-        bool stop_seen = false, pace = paced;
-        auto reported = [&](int launch) {          // has `launch` (or a later one) of THIS solve reported?  sets stop_seen
-            const unsigned v = __atomic_load_n(h->progress_host, __ATOMIC_ACQUIRE);
-            if (((v >> kPacedEpochShift) & kPacedEpochMask) != h->epoch) return false;
-            if (v & kPacedStopBit) stop_seen = true;
-            return stop_seen || (v & 0xffffu) >= (unsigned)(launch + 1);
-        };
-        for (int step = 0; step <= h->cfg.num_steps; ++step) {
-            const bool fin = step == h->cfg.num_steps;
-            if (pace && !fin && step >= h->paced_depth) {
-                // A launch of this solve reports within a few microseconds of the previous one when the queue is ours.
-                // Spin briefly (the common case), then yield the core between polls; give up after kPacedPatienceUs.
-                // A queue backed up by other streams (a serving loop overlapping the CNN with the LM) trips that: the rest
-                // of THIS solve is issued unpaced, and the handle stops pacing for the next kPacedCooldown solves instead
-                // of burning the patience on every call.
-                const auto t0 = std::chrono::steady_clock::now();
-                for (unsigned spin = 0; !reported(step - h->paced_depth); ++spin) {
-                    if (spin < 256) continue;
-                    std::this_thread::yield();
-                    if ((spin & 0xf) == 0 &&
-                        std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kPacedPatienceUs)) {
-                        pace = false;
-                        h->paced_cooldown = kPacedCooldown;
-                        break;
-                    }
-                }
-            }
-            if (stop_seen && !fin) continue;       // the final launch finds the stop in the counters, as it always does
-            SweepArgs a = sweep_args(h, d_up, d_lat, d_up_conf, d_lat_conf, c.pb[0], geo, !fin, 0);
-            apply_slat(h, a, slat_ready, given);        // (never the library's plane here: slat_wanted)
-            a.partials = part[step & 1];
-            FusedArgs f;
-            f.c = c;
-            f.step = step;
-            f.is_final = fin ? 1 : 0;
-            f.partials_in = part[(step + 1) & 1];
-            f.progress = (paced && !fin) ? h->progress_dev : nullptr;
-            f.epoch = h->epoch;
-            f.ia = ia;
-            f.init_here = step == 0 ? 1 : 0;
-            if (int rc = timed_sweep(h, a, s, &f)) return rc;
-        }
-        SolveCtx cf = c;
-        cf.partials = part[h->cfg.num_steps & 1];        // the final sweep's records
-        GCLM_HIP(h, launch_finalize(cf, d_cam_out, d_grav_out, d_info_out, s));
-        return 0;
-    }
-    for (int step = 0; step < h->cfg.num_steps; ++step) {
-        SweepArgs a = sweep_args(h, d_up, d_lat, d_up_conf, d_lat_conf, c.pb[step & 1], geo, true, es ? step : 0);
-        apply_slat(h, a, slat_ready, given);
-        if (int rc = timed_sweep(h, a, s)) return rc;
-        if (!h->cfg.shared_intrinsics) {
-            GCLM_HIP(h, launch_update(c, step, s));
-        } else {
-            GCLM_HIP(h, launch_shared_step(c, step, s));     // reduce + Schur solve + update: one launch
-        }
-        // a batch sharded over ranks: "whose cost still moved" is a count over ALL ranks' images (every step, also after
-        // the stop -- the counters of skipped steps stay 0 everywhere -- so that the ranks' collectives keep matching)
-        if (es && h->stop_comm && step >= 1)
-            if (gclm_comm_all_reduce_sum_i32(h->stop_comm, &c.ctrl->notclose[step], 1, s) != 0)
-                return fail(h, -20, "early-stop all-reduce failed: %s", gclm_comm_last_error(h->stop_comm));
-    }
-    GCLM_HIP(h, launch_prep_final(c, s));
-    SweepArgs a = sweep_args(h, d_up, d_lat, d_up_conf, d_lat_conf, c.pb_final, geo, false, 0);
-    apply_slat(h, a, slat_ready, given);
-    if (int rc = timed_sweep(h, a, s)) return rc;
-    GCLM_HIP(h, launch_finalize(c, d_cam_out, d_grav_out, d_info_out, s));
-    return 0;
-}
-
 int gclm_solve_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
                   const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
                   float* d_info_out, const float* d_sin_lat, void* stream) {
@@ -760,7 +786,7 @@ int gclm_solve_ex(gclm_handle* h, const float* d_up, const float* d_lat, const f
     ia.cam = d_cam_io;
     ia.grav = d_grav_io;
     if (B != 0 && (!d_cam_io || !d_grav_io)) return fail(h, -3, "gclm_solve: null camera / gravity pointer");
-    return run_solve(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, ia, d_cam_io, d_grav_io, d_info_out, d_sin_lat, stream);
+    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_io, d_grav_io, d_info_out, d_sin_lat, stream);
 }
 
 int gclm_solve(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
@@ -790,7 +816,7 @@ int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, con
     ia.lat = d_lat;
     if (h->cfg.heuristic_init && !d_up && B != 0) return fail(h, -3, "gclm_calibrate: heuristic_init needs the up field");
     // (the initial estimate -- the heuristic one reads `lat` -- always reads the radians: ia.lat)
-    return run_solve(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, d_sin_lat, stream);
+    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, d_sin_lat, stream);
 }
 
 int gclm_calibrate(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
@@ -811,18 +837,12 @@ int gclm_system(gclm_handle* h, const float* d_up, const float* d_lat, const flo
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(h->device);
     GCLM_HIP(h, guard.status);
-    const bool al = is_aligned16(d_up) && is_aligned16(d_lat) && is_aligned16(d_up_conf) && is_aligned16(d_lat_conf);
-    const Geometry geo = plan_sweeps(h, B, H, W, al, d_up && d_up_conf && d_lat_conf);
     SolveCtx& c = h->ctx;
-    c.cfg = h->cfg;
-    c.B = B; c.H = H; c.W = W; c.nchunks = geo.nchunks;
     c.n_groups = 0; c.group_size = 1; c.group_of_frame = nullptr; c.iso_final = 0;
-    if (int rc = ensure_workspace(h, B, geo.nchunks, 0)) return rc;
-    h->slat = nullptr;
-    h->sh.active = false;
+    Plan p;      // one sweep: no plane of sin(latitude), handed or kept
+    if (int rc = make_plan(h, p, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, nullptr, 1)) return rc;
     GCLM_HIP(h, launch_pblock_from_params(c, d_cam, d_grav, as_rpf, c.pb_final, s));
-    const SweepArgs a = sweep_args(h, d_up, d_lat, d_up_conf, d_lat_conf, c.pb_final, geo, !as_rpf, 0);
-    GCLM_HIP(h, launch_sweep(h->cfg.camera_model, a, s));
+    GCLM_HIP(h, launch_sweep(h->cfg.camera_model, p.next_sweep(h, c.pb_final, !as_rpf, 0), s));
     GCLM_HIP(h, launch_system_out(c, d_cost, d_grad, d_hess, s));
     return 0;
 }
@@ -839,20 +859,10 @@ int gclm_shared_begin_ex(gclm_handle* h, const float* d_up, const float* d_lat, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(h->device);
     GCLM_HIP(h, guard.status);
-    const bool al = is_aligned16(d_up) && is_aligned16(d_lat) && is_aligned16(d_up_conf) && is_aligned16(d_lat_conf);
-    const int Bp = B_local > 0 ? B_local : 1;
-    h->sh.geo = plan_sweeps(h, Bp, H, W, al, d_up && d_up_conf && d_lat_conf);
     SolveCtx& c = h->ctx;
-    c.cfg = h->cfg;
-    c.B = B_local; c.H = H; c.W = W; c.nchunks = h->sh.geo.nchunks;
     c.n_groups = num_groups; c.group_size = 1; c.group_of_frame = d_group_of_frame; c.iso_final = 0;
-    const float* given = B_local > 0 ? handed_slat(h, d_sin_lat, d_up, d_up_conf, d_lat_conf, h->sh.geo, false) : nullptr;
-    const bool keep_slat = B_local > 0 && !given && slat_wanted(h, d_up, d_up_conf, d_lat_conf, h->sh.geo, false);
-    if (int rc = ensure_workspace(h, Bp, h->sh.geo.nchunks, num_groups)) return rc;
-    ensure_slat(h, keep_slat ? (size_t)B_local * H * W : 0);
-    h->sh.slat_ready = false;
-    h->sh.given = given;
-    h->sh.up = d_up; h->sh.lat = d_lat; h->sh.upc = d_up_conf; h->sh.latc = d_lat_conf;
+    if (int rc = make_plan(h, h->sh.plan, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B_local, H, W, d_sin_lat, h->cfg.num_steps + 1))
+        return rc;
     h->sh.cam_io = d_cam_io; h->sh.grav_io = d_grav_io;
     h->sh.active = true;
     InitArgs ia{};
@@ -878,9 +888,7 @@ int gclm_shared_reduce(gclm_handle* h, int step, float* d_partials, void* stream
     GCLM_HIP(h, guard.status);
     SolveCtx& c = h->ctx;
     if (c.B > 0) {
-        SweepArgs a = sweep_args(h, h->sh.up, h->sh.lat, h->sh.upc, h->sh.latc, c.pb[step & 1], h->sh.geo, true, 0);
-        apply_slat(h, a, h->sh.slat_ready, h->sh.given);
-        if (int rc = timed_sweep(h, a, s)) return rc;
+        if (int rc = timed_sweep(h, h->sh.plan.next_sweep(h, c.pb[step & 1], true, 0), s)) return rc;
     }
     GCLM_HIP(h, launch_shared_reduce(c, step, d_partials, s));
     return 0;
@@ -908,9 +916,7 @@ int gclm_shared_finish(gclm_handle* h, float* d_info_out, void* stream) {
     h->sh.active = false;
     if (c.B == 0) return 0;
     GCLM_HIP(h, launch_prep_final(c, s));
-    SweepArgs a = sweep_args(h, h->sh.up, h->sh.lat, h->sh.upc, h->sh.latc, c.pb_final, h->sh.geo, false, 0);
-    apply_slat(h, a, h->sh.slat_ready, h->sh.given);
-    if (int rc = timed_sweep(h, a, s)) return rc;
+    if (int rc = timed_sweep(h, h->sh.plan.next_sweep(h, c.pb_final, false, 0), s)) return rc;
     GCLM_HIP(h, launch_finalize(c, h->sh.cam_io, h->sh.grav_io, d_info_out, s));
     return 0;
 }

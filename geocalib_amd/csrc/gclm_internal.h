@@ -108,32 +108,12 @@ struct SweepArgs {
     int mirror;             // 1: the row-pair walk (gclm_pass.hip: row_math_mirror); the geometry was planned for H / 2 rows
 };
 
-struct SolveCtx;
-struct FusedArgs;
-
 struct Geometry {          // how a sweep is cut into blocks (column-stationary tiles, see gclm_pass.hip)
     int vec, nchunks;
     int wu, cu, nstrips, rpi, rows_per_block, wpt, jobs;
     int mirror, hrows;     // the row-pair walk: tiles cover rows [0, H / 2), every lane takes the mirror row along
 };
-Geometry plan_geometry(int B, int H, int W, bool aligned16, int sweep_iters = 0, int camera_model = 0, bool mirror = false);
-bool sweep_has_mirror(int camera_model);       // gclm_pass.hip: the model's five-plane float4 sweep has the row-pair instantiations
-bool sweep_mirror_builtin(int camera_model);   // ... and they are the library's own choice for it
 
-// gclm_pass.hip
-hipError_t launch_gradient_hessian(const float* d_J, const float* d_r, const float* d_w, int B, int N, int R, int P,
-                                   int accumulate, float* d_G, float* d_H, hipStream_t s);
-hipError_t launch_lm_step(const float* d_G, const float* d_H, const float* d_lambda, int lambda_stride, float eps, int B,
-                          int P, float* d_delta, int* d_failed, hipStream_t s);
-hipError_t launch_residual_fields(int camera_model, const float* d_up, const float* d_lat, const float* d_cam,
-                                  const float* d_grav, int B, int H, int W, float* d_r_up, float* d_r_lat, hipStream_t s);
-hipError_t launch_huber_costs(const float* d_residual, size_t n, int dim, float scale, const float* d_conf,
-                              float* d_cost, float* d_weight, float* d_second, hipStream_t s);
-hipError_t launch_jacobian_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W,
-                                  int spherical, int log_focal, float* d_J_up, float* d_J_lat, hipStream_t s);
-hipError_t launch_sweep(int camera_model, const SweepArgs& a, hipStream_t s);
-
-// gclm_update.hip
 struct SolveCtx {
     gclm_config cfg;
     int B, H, W, nchunks;
@@ -176,7 +156,6 @@ constexpr unsigned kPacedStopBit = 1u << 16;
 constexpr unsigned kPacedEpochShift = 20, kPacedEpochMask = 0xfffu;
 constexpr int kPacedPatienceUs = 2000;    // host wait for one report before the rest of the solve is issued unpaced ...
 constexpr int kPacedCooldown = 64;        // ... and solves of that handle that then do not pace at all
-bool sweep_has_slat_plane(int camera_model);   // gclm_pass.hip: the model's five-plane float4 sweep has the SLAT instantiations
 constexpr int kMaxMergeParts = 8;
 struct MergeStopArgs {          // gclm_merge_stop_at: parts of one batch solved by separate handles
     const Ctrl* ctrl[kMaxMergeParts];
@@ -184,18 +163,6 @@ struct MergeStopArgs {          // gclm_merge_stop_at: parts of one batch solved
     int B[kMaxMergeParts];
     int n, num_steps;
 };
-hipError_t launch_merge_stop(const MergeStopArgs& a, hipStream_t s);
-hipError_t launch_fused_step(int camera_model, const SweepArgs& a, const FusedArgs& f, hipStream_t s);
-hipError_t launch_init(const SolveCtx& c, const InitArgs& ia, hipStream_t s);
-hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s);
-hipError_t launch_prep_final(const SolveCtx& c, hipStream_t s);
-hipError_t launch_finalize(const SolveCtx& c, float* d_cam, float* d_grav, float* d_info, hipStream_t s);
-hipError_t launch_shared_reduce(const SolveCtx& c, int step, float* d_group_partials, hipStream_t s);
-hipError_t launch_shared_apply(const SolveCtx& c, int step, const float* d_group_partials, hipStream_t s);
-hipError_t launch_shared_step(const SolveCtx& c, int step, hipStream_t s);
-hipError_t launch_system_out(const SolveCtx& c, float* d_cost, float* d_grad, float* d_hess, hipStream_t s);
-hipError_t launch_pblock_from_params(const SolveCtx& c, const float* d_cam, const float* d_grav, int as_rpf, PBlock* out, hipStream_t s);
-hipError_t launch_upsample(const float* src, int planes, int h, int w, int H, int W, float* dst, hipStream_t s);
 constexpr int kMaxUpsampleTensors = 8;
 struct UpsampleMulti {          // gclm_upsample_fields_multi: several tensors of (h, w) planes in one launch
     const float* src[kMaxUpsampleTensors];
@@ -203,19 +170,54 @@ struct UpsampleMulti {          // gclm_upsample_fields_multi: several tensors o
     int planes[kMaxUpsampleTensors];
     int n;
 };
+
+// gclm_api.hip
+Geometry plan_geometry(int B, int H, int W, bool aligned16, int sweep_iters = 0, int camera_model = 0, bool mirror = false);
+
+// gclm_pass.hip
+hipError_t launch_sweep(int camera_model, const SweepArgs& a, hipStream_t s);
+hipError_t launch_fused_step(int camera_model, const SweepArgs& a, const FusedArgs& f, hipStream_t s);
+bool sweep_has_mirror(int camera_model);       // the model's five-plane float4 sweep has the row-pair instantiations
+bool sweep_mirror_builtin(int camera_model);   // ... and they are the library's own choice for it
+bool sweep_has_slat_plane(int camera_model);   // the model's five-plane float4 sweep has the SLAT instantiations
+hipError_t launch_residual_fields(int camera_model, const float* d_up, const float* d_lat, const float* d_cam,
+                                  const float* d_grav, int B, int H, int W, float* d_r_up, float* d_r_lat, hipStream_t s);
+hipError_t launch_huber_costs(const float* d_residual, size_t n, int dim, float scale, const float* d_conf,
+                              float* d_cost, float* d_weight, float* d_second, hipStream_t s);
+hipError_t launch_jacobian_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W,
+                                  int spherical, int log_focal, float* d_J_up, float* d_J_lat, hipStream_t s);
+
+// gclm_update.hip
+hipError_t launch_init(const SolveCtx& c, const InitArgs& ia, hipStream_t s);
+hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s);
+hipError_t launch_prep_final(const SolveCtx& c, hipStream_t s);
+hipError_t launch_finalize(const SolveCtx& c, float* d_cam, float* d_grav, float* d_info, hipStream_t s);
+hipError_t launch_merge_stop(const MergeStopArgs& a, hipStream_t s);
+hipError_t launch_shared_reduce(const SolveCtx& c, int step, float* d_group_partials, hipStream_t s);
+hipError_t launch_shared_apply(const SolveCtx& c, int step, const float* d_group_partials, hipStream_t s);
+hipError_t launch_shared_step(const SolveCtx& c, int step, hipStream_t s);
+hipError_t launch_system_out(const SolveCtx& c, float* d_cost, float* d_grad, float* d_hess, hipStream_t s);
+hipError_t launch_pblock_from_params(const SolveCtx& c, const float* d_cam, const float* d_grav, int as_rpf, PBlock* out, hipStream_t s);
+hipError_t launch_upsample(const float* src, int planes, int h, int w, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_upsample_multi(const UpsampleMulti& m, int h, int w, int H, int W, hipStream_t s);
 hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const float* lat_raw, const float* lat_lc,
                               int B, int H, int W, bool vec4, float* up, float* upc, float* lat, float* latc,
                               float* slat /* or nullptr */, hipStream_t s);
+hipError_t launch_read_probe(const float* const* planes, int n, size_t floats, hipStream_t s);
+hipError_t launch_synth(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
+                        float sigma, int group_size, int run, int run_stride, float* up, float* lat, float* upc, float* latc, float* gt_cam,
+                        float* gt_grav, hipStream_t s);
+hipError_t launch_lm_step(const float* d_G, const float* d_H, const float* d_lambda, int lambda_stride, float eps, int B,
+                          int P, float* d_delta, int* d_failed, hipStream_t s);
+hipError_t launch_gradient_hessian(const float* d_J, const float* d_r, const float* d_w, int B, int N, int R, int P,
+                                   int accumulate, float* d_G, float* d_H, hipStream_t s);
+
+// gclm_image.hip, gclm_pano.hip, gclm_persp.hip
 hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,
                                   int Win, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_render_from_pano(int camera_model, const float* cam, int cam_batch, const float* rot, const float* const* srcs,
                                    const int* src_hw, int n, int C, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_perspective_fields(int camera_model, const float* cam, const float* grav, int B, int H, int W, int normalize,
                                      float* up /* or nullptr */, float* lat /* or nullptr */, hipStream_t s);
-hipError_t launch_read_probe(const float* const* planes, int n, size_t floats, hipStream_t s);
-hipError_t launch_synth(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
-                        float sigma, int group_size, int run, int run_stride, float* up, float* lat, float* upc, float* latc, float* gt_cam,
-                        float* gt_grav, hipStream_t s);
 
 }  // namespace gclm

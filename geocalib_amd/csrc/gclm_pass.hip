@@ -78,20 +78,12 @@
 #ifndef GCLM_LAT_PAIRS
 #define GCLM_LAT_PAIRS 1       // row pairs, log-focal: the latitude sums of the two rows are taken together (lat_pair_accumulate)
 #endif
-#ifndef GCLM_MIRROR_MODELS
-#define GCLM_MIRROR_MODELS ((1 << GCLM_RADIAL) | (1 << GCLM_SIMPLE_DIVISIONAL))   // models whose BUILT-IN choice is the row-pair walk
-                             // (same-allocation A/B, profiles/r06_variant_row_pairs.log: simple_divisional -14.2 % per sweep at
-                             // 2 waves per SIMD; radial -3.9 % once its walker is held to 168 VGPRs = 3 waves, -1.3 % at 2)
-#endif
 #ifndef GCLM_MIRROR_WAVES
 #define GCLM_MIRROR_WAVES 2    // the row-pair walkers (sweep_body: MIRROR) hold two rows' loads: 256 VGPRs
 #endif
 #ifndef GCLM_MIRROR_WAVES_RADIAL
 #define GCLM_MIRROR_WAVES_RADIAL 3    // ... radial's log-focal walker fits 168 VGPRs = 3 waves (16-32 B of scratch: one 8-byte
 #endif                                //     reload per iteration); its general-focal form would spill 216-248 B there and keeps 2
-#ifndef GCLM_SLAT_PINHOLE
-#define GCLM_SLAT_PINHOLE 1    // pinhole has the scratch-plane instantiations too: never the built-in choice (memory-bound), only
-#endif                         // gclm_set_slat_plane(h, 1) launches them (measurement)
 
 #ifndef GCLM_TRACE
 #define GCLM_TRACE 0                // measurement build only: device timestamps of one workgroup's stages (scripts/probes/trace_probe.py)
@@ -1137,7 +1129,7 @@ __global__ __launch_bounds__(kBlock, MIRROR ? (MODEL == GCLM_RADIAL && LOGF ? GC
 // of 2 num_steps + 4.  Every workgroup of an image computes the same bits (fixed reduction order); workgroup 0 of the
 // image commits the new state and the early-stop counter.  Partial records are double-buffered (launch k reads the
 // records of launch k-1 while it writes its own).  Early stop: this kernel is only used when the decision is local to
-// a workgroup -- B == 1 -- or off (gclm_api.hip: use_fused): the stop fires in the prologue that detects it, nothing is
+// a workgroup -- B == 1 -- or off (gclm_api.hip: make_plan): the stop fires in the prologue that detects it, nothing is
 // committed, nobody sweeps, and every later launch returns at its first instruction pair.
 // The final launch (is_final) does the same with the last update, then builds the (roll, pitch, focal) block of the
 // uncertainty sweep (prep_final_kernel's job) and sweeps with it.
@@ -1429,114 +1421,108 @@ __global__ void huber_costs_kernel(const float* residual, size_t n, int dim, flo
     if (second) second[i] = y <= 1.0f ? 0.f : -isx / (2.0f * y * a2);
 }
 
-template <int MODEL, int VEC>
-hipError_t dispatch(const SweepArgs& a, hipStream_t s) {
-    const dim3 grid(a.nchunks, a.B), block(kBlock);
-    const bool up = a.up != nullptr, upc = up && a.upc != nullptr, latc = a.latc != nullptr;
-    // the log-focal specialisation only for the vector path (the scalar path is the odd-shape fallback)
-    const bool logf = VEC == 4 && a.log_focal != 0;
-    // an occupancy cap by LDS reservation for the memory-bound model (GCLM_PINHOLE_LDS above)
-    constexpr unsigned lds = (MODEL == GCLM_PINHOLE && VEC == 4 && GCLM_DYN_LDS == 0) ? GCLM_PINHOLE_LDS : GCLM_DYN_LDS;
-#define GCLM_LAUNCH(U, UC, LC)                                                                          \
-    do {                                                                                                \
-        if (logf) hipLaunchKernelGGL((sweep_kernel<MODEL, U, UC, LC, VEC == 4, VEC>), grid, block, lds, s, a); \
-        else hipLaunchKernelGGL((sweep_kernel<MODEL, U, UC, LC, false, VEC>), grid, block, lds, s, a);    \
-    } while (0)
-    // row pairs (sweep_body: MIRROR): the five-plane float4 sweeps of radial / simple_divisional over an even number of rows
-    if (a.mirror != 0) {
-        if constexpr (VEC == 4 && (MODEL == GCLM_RADIAL || MODEL == GCLM_SIMPLE_DIVISIONAL)) {
-            if (!(up && upc && latc) || (a.H & 1) || a.hrows * 2 != a.H || a.slat_mode < 0 || a.slat_mode > 2 ||
-                (a.slat_mode != 0 && a.slat == nullptr))
-                return hipErrorInvalidValue;
-#define GCLM_LAUNCH_MIRROR(LF)                                                                                              \
-    do {                                                                                                                    \
-        if (a.slat_mode == 0) hipLaunchKernelGGL((sweep_kernel<MODEL, true, true, true, LF, 4, 0, true>), grid, block, GCLM_DYN_LDS, s, a);      \
-        else if (a.slat_mode == 1) hipLaunchKernelGGL((sweep_kernel<MODEL, true, true, true, LF, 4, 1, true>), grid, block, GCLM_DYN_LDS, s, a); \
-        else hipLaunchKernelGGL((sweep_kernel<MODEL, true, true, true, LF, 4, 2, true>), grid, block, GCLM_DYN_LDS, s, a);             \
-    } while (0)
-            if (logf) GCLM_LAUNCH_MIRROR(true); else GCLM_LAUNCH_MIRROR(false);
-#undef GCLM_LAUNCH_MIRROR
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    // the sin(latitude) scratch plane (row_math: SLAT) exists for the five-plane float4 sweeps of the distortion models
-    if constexpr (VEC == 4 && (MODEL != GCLM_PINHOLE || GCLM_SLAT_PINHOLE)) {
-        if (a.slat_mode != 0) {
-            if (!(up && upc && latc) || a.slat == nullptr || a.slat_mode < 0 || a.slat_mode > 2) return hipErrorInvalidValue;
-#define GCLM_LAUNCH_SLAT(LF)                                                                                         \
-    do {                                                                                                             \
-        if (a.slat_mode == 1) hipLaunchKernelGGL((sweep_kernel<MODEL, true, true, true, LF, 4, 1>), grid, block, GCLM_DYN_LDS, s, a); \
-        else hipLaunchKernelGGL((sweep_kernel<MODEL, true, true, true, LF, 4, 2>), grid, block, GCLM_DYN_LDS, s, a);            \
-    } while (0)
-            if (logf) GCLM_LAUNCH_SLAT(true); else GCLM_LAUNCH_SLAT(false);
-#undef GCLM_LAUNCH_SLAT
-            return hipGetLastError();
-        }
-    } else if (a.slat_mode != 0) {
-        return hipErrorInvalidValue;
-    }
-    if (up) {
-        if (upc) { if (latc) GCLM_LAUNCH(true, true, true); else GCLM_LAUNCH(true, true, false); }
-        else     { if (latc) GCLM_LAUNCH(true, false, true); else GCLM_LAUNCH(true, false, false); }
-    } else {
-        if (latc) GCLM_LAUNCH(false, false, true); else GCLM_LAUNCH(false, false, false);
-    }
-#undef GCLM_LAUNCH
-    return hipGetLastError();
+// ---- which kernels exist ----------------------------------------------------------------------------------------------
+// The instantiation set of sweep_kernel, stated once: launch_sweep instantiates and launches exactly the kernels for which
+// this holds, and answers hipErrorInvalidValue for every other combination of run-time flags (the host's own choices,
+// gclm_api.hip: make_plan, are answered from it too -- sweep_has_mirror, sweep_has_slat_plane).  22 kernels per model, and
+// the 6 row-pair walkers each of radial and simple_divisional.
+//   * an up confidence needs an up field;
+//   * the scalar path (VEC = 1) is the odd-shape fallback: general focal only, no plane, no row pairs;
+//   * the sin(latitude) scratch plane (row_math: SLAT = 1 fills it, 2 reads it) exists for the five-plane float4 sweep of
+//     every model.  Pinhole has these instantiations too: never the built-in choice (memory-bound), only
+//     gclm_set_slat_plane(h, 1) launches them (measurement);
+//   * row pairs (sweep_body: MIRROR): the five-plane float4 sweeps of radial / simple_divisional, with every SLAT.
+constexpr bool sweep_exists(int model, bool up, bool upc, bool latc, bool logf, int vec, int slat, bool mirror) {
+    const bool five = up && upc && latc;
+    if (model < GCLM_PINHOLE || model > GCLM_SIMPLE_DIVISIONAL || (upc && !up) || slat < 0 || slat > 2) return false;
+    if (vec != 4) return vec == 1 && !logf && slat == 0 && !mirror;
+    if (mirror) return five && (model == GCLM_RADIAL || model == GCLM_SIMPLE_DIVISIONAL);
+    return slat == 0 || five;
 }
-
-template <int MODEL>
-hipError_t dispatch_fused(const SweepArgs& a, const FusedArgs& f, hipStream_t s) {
-    const dim3 grid(a.nchunks, a.B), block(kBlock);
-    const bool up = a.up != nullptr, upc = up && a.upc != nullptr, latc = a.latc != nullptr;
-    const bool logf = a.log_focal != 0;
-    // a plane of sin(latitude) handed by the caller (gclm_api.hip: handed_slat): the five-plane launches read it as `lat`
-    if (a.slat_mode != 0) {
-        if (a.slat_mode != 2 || !(up && upc && latc) || a.slat == nullptr || a.lat != a.slat) return hipErrorInvalidValue;
-        if (logf) hipLaunchKernelGGL((fused_step_kernel<MODEL, true, true, true, true, 2>), grid, block, 0, s, a, f);
-        else hipLaunchKernelGGL((fused_step_kernel<MODEL, true, true, true, false, 2>), grid, block, 0, s, a, f);
-        return hipGetLastError();
-    }
-#define GCLM_LAUNCH(U, UC, LC)                                                                               \
-    do {                                                                                                     \
-        if (logf) hipLaunchKernelGGL((fused_step_kernel<MODEL, U, UC, LC, true>), grid, block, 0, s, a, f);  \
-        else hipLaunchKernelGGL((fused_step_kernel<MODEL, U, UC, LC, false>), grid, block, 0, s, a, f);      \
-    } while (0)
-    if (up) {
-        if (upc) { if (latc) GCLM_LAUNCH(true, true, true); else GCLM_LAUNCH(true, true, false); }
-        else     { if (latc) GCLM_LAUNCH(true, false, true); else GCLM_LAUNCH(true, false, false); }
-    } else {
-        if (latc) GCLM_LAUNCH(false, false, true); else GCLM_LAUNCH(false, false, false);
-    }
-#undef GCLM_LAUNCH
-    return hipGetLastError();
+// ... and of fused_step_kernel (float4 only; 14 per model): every set of planes in both focal forms, and the five-plane
+// reader of a plane of sin(latitude) the caller handed (SLAT = 2; gclm_api.hip: Plan::given)
+constexpr bool fused_exists(int model, bool up, bool upc, bool latc, int slat) {
+    if (model < GCLM_PINHOLE || model > GCLM_SIMPLE_DIVISIONAL || (upc && !up)) return false;
+    return slat == 0 || (slat == 2 && up && upc && latc);
 }
+// models whose BUILT-IN choice is the row-pair walk, among those that have it
+// (same-allocation A/B, profiles/r06_variant_row_pairs.log: simple_divisional -14.2 % per sweep at
+// 2 waves per SIMD; radial -3.9 % once its walker is held to 168 VGPRs = 3 waves, -1.3 % at 2)
+constexpr int kMirrorBuiltinModels = (1 << GCLM_RADIAL) | (1 << GCLM_SIMPLE_DIVISIONAL);
 
-template <int MODEL>
-hipError_t dispatch_model(const SweepArgs& a, hipStream_t s) {
-    return a.vec == 4 ? dispatch<MODEL, 4>(a, s) : dispatch<MODEL, 1>(a, s);
+// Run-time flags become template arguments, in the idiom of with_camera_model: with_flags(f, b0, b1, ...) calls
+// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...), with_slat_mode hands std::integral_constant<int, 0 | 1 | 2>
+template <typename F>
+hipError_t with_flags(F&& f) { return f(); }
+template <typename F, typename... Bools>
+hipError_t with_flags(F&& f, bool first, Bools... rest) {
+    auto bind = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return first ? bind(std::true_type{}) : bind(std::false_type{});
+}
+template <typename F>
+hipError_t with_slat_mode(int slat_mode, F&& f) {
+    switch (slat_mode) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace
 
 hipError_t launch_sweep(int camera_model, const SweepArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    return with_camera_model(camera_model, [&](auto m) { return dispatch_model<decltype(m)::value>(a, s); });
+    // what no template argument says: a plane mode needs its plane, row pairs an even number of rows cut in halves
+    if ((a.slat_mode != 0 && a.slat == nullptr) || (a.mirror != 0 && ((a.H & 1) || a.hrows * 2 != a.H))) return hipErrorInvalidValue;
+    const dim3 grid(a.nchunks, a.B), block(kBlock);
+    const bool up = a.up != nullptr, vec4 = a.vec == 4;
+    // the log-focal specialisation only for the vector path (the scalar path is the odd-shape fallback)
+    return with_camera_model(camera_model, [&](auto m) {
+        return with_slat_mode(a.slat_mode, [&](auto sl) {
+            return with_flags([&](auto u, auto uc, auto lc, auto lf, auto v4, auto mir) {
+                constexpr int MODEL = decltype(m)::value, SLAT = decltype(sl)::value, VEC = decltype(v4)::value ? 4 : 1;
+                constexpr bool U = decltype(u)::value, UC = decltype(uc)::value, LC = decltype(lc)::value,
+                               LOGF = decltype(lf)::value, MIRROR = decltype(mir)::value;
+                if constexpr (sweep_exists(MODEL, U, UC, LC, LOGF, VEC, SLAT, MIRROR)) {
+                    // an occupancy cap by LDS reservation for the memory-bound model (GCLM_PINHOLE_LDS above) on its plain
+                    // float4 sweeps.  Pinhole's plane launches (measurement only, see sweep_exists) do not get the cap.
+                    constexpr unsigned lds = (MODEL == GCLM_PINHOLE && VEC == 4 && SLAT == 0 && !MIRROR && GCLM_DYN_LDS == 0)
+                                                 ? GCLM_PINHOLE_LDS : GCLM_DYN_LDS;
+                    hipLaunchKernelGGL((sweep_kernel<MODEL, U, UC, LC, LOGF, VEC, SLAT, MIRROR>), grid, block, lds, s, a);
+                    return hipGetLastError();
+                } else {
+                    return hipErrorInvalidValue;
+                }
+            }, up, up && a.upc != nullptr, a.latc != nullptr, vec4 && a.log_focal != 0, vec4, a.mirror != 0);
+        });
+    });
 }
 
-bool sweep_has_mirror(int camera_model) { return camera_model == GCLM_RADIAL || camera_model == GCLM_SIMPLE_DIVISIONAL; }
-bool sweep_mirror_builtin(int camera_model) { return sweep_has_mirror(camera_model) && ((GCLM_MIRROR_MODELS >> camera_model) & 1) != 0; }
-
-bool sweep_has_slat_plane(int camera_model) {
-    return camera_model > GCLM_PINHOLE ? camera_model <= GCLM_SIMPLE_DIVISIONAL : (camera_model == GCLM_PINHOLE && GCLM_SLAT_PINHOLE != 0);
-}
+bool sweep_has_mirror(int camera_model) { return sweep_exists(camera_model, true, true, true, true, 4, 0, true); }
+bool sweep_mirror_builtin(int camera_model) { return sweep_has_mirror(camera_model) && ((kMirrorBuiltinModels >> camera_model) & 1) != 0; }
+bool sweep_has_slat_plane(int camera_model) { return sweep_exists(camera_model, true, true, true, true, 4, 1, false); }
 
 hipError_t launch_fused_step(int camera_model, const SweepArgs& a, const FusedArgs& f, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
-    if (a.vec != 4) return hipErrorInvalidValue;          // the caller only fuses the float4 path
-    return with_camera_model(camera_model, [&](auto m) { return dispatch_fused<decltype(m)::value>(a, f, s); });
+    // the caller only fuses the float4 path; a plane of sin(latitude) it was handed (gclm_api.hip: Plan::given) is read as `lat`
+    if (a.vec != 4 || (a.slat_mode != 0 && (a.slat == nullptr || a.lat != a.slat))) return hipErrorInvalidValue;
+    const dim3 grid(a.nchunks, a.B), block(kBlock);
+    const bool up = a.up != nullptr;
+    return with_camera_model(camera_model, [&](auto m) {
+        return with_slat_mode(a.slat_mode, [&](auto sl) {
+            return with_flags([&](auto u, auto uc, auto lc, auto lf) {
+                constexpr int MODEL = decltype(m)::value, SLAT = decltype(sl)::value;
+                constexpr bool U = decltype(u)::value, UC = decltype(uc)::value, LC = decltype(lc)::value, LOGF = decltype(lf)::value;
+                if constexpr (fused_exists(MODEL, U, UC, LC, SLAT)) {
+                    hipLaunchKernelGGL((fused_step_kernel<MODEL, U, UC, LC, LOGF, SLAT>), grid, block, 0, s, a, f);
+                    return hipGetLastError();
+                } else {
+                    return hipErrorInvalidValue;
+                }
+            }, up, up && a.upc != nullptr, a.latc != nullptr, a.log_focal != 0);
+        });
+    });
 }
 
 hipError_t launch_residual_fields(int camera_model, const float* d_up, const float* d_lat, const float* d_cam,

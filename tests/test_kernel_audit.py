@@ -37,7 +37,9 @@ def test_no_sweep_kernel_carries_an_lds_array_or_scratch_it_was_not_given(tmp_pa
     k = kernel_metadata(tmp_path)
     sweeps = {n: v for n, v in k.items() if "sweep_kernelILi" in n}
     fused = {n: v for n, v in k.items() if "fused_step_kernelILi" in n}
-    assert len(sweeps) >= 48 and len(fused) >= 32, (len(sweeps), len(fused))
+    # exactly the instantiation set of gclm_pass.hip (sweep_exists: 22 per model + 6 row-pair walkers each of radial and
+    # simple_divisional; fused_exists: 14 per model)
+    assert len(sweeps) == 100 and len(fused) == 56, (len(sweeps), len(fused))
     # the sweep's only LDS is the 4-wave reduction buffer (4 x NACC floats: 256 B; radial 384 B)
     assert all(v["lds"] <= 384 for v in sweeps.values()), {n: v for n, v in sweeps.items() if v["lds"] > 384}
     # the one-launch-per-step kernels add the update prologue's buffers (stripes of the record reduction, parameter block)

@@ -214,7 +214,7 @@ def _expect_slat(on):
 
 
 def _expect_fused(r, steps):
-    # the one-launch-per-step path declines the scratch plane even when it is forced on (gclm_api.hip: slat_wanted), and
+    # the one-launch-per-step path declines the scratch plane even when it is forced on (gclm_api.hip: make_plan), and
     # issues one sweep launch per step plus the final one
     assert r["slat_bytes"] == 0 and r["launches"] == steps + 1, (r["slat_bytes"], r["launches"])
 
