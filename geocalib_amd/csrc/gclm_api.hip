@@ -6,6 +6,7 @@
 //   fused(step) x num_steps | fused(final) | finalize
 // (the reference syncs twice per step: H,G -> CPU Cholesky -> device, and torch.allclose).
 #include <chrono>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1043,6 +1044,43 @@ int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d
         return -3;
     hipError_t e = launch_perspective_fields(camera_model, d_cam, d_grav, B, H, W, normalize_up, d_up, d_lat,
                                              static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : -10;
+}
+
+size_t gclm_field_errors_workspace(int B, int H, int W, int n_thresholds) {
+    return field_errors_workspace(B, H, W, n_thresholds);
+}
+
+int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                      const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int n_thresholds,
+                      const float* thresholds_deg, void* d_workspace, size_t workspace_bytes, float* d_stats, float* d_up_err,
+                      float* d_lat_err, void* stream) {
+    // every check runs before the first HIP call
+    if (!d_cam || !d_grav || !d_stats || !d_workspace || (!d_up && !d_lat)) return -3;
+    if ((!d_up && (d_up_conf || d_up_err)) || (!d_lat && (d_lat_conf || d_lat_err))) return -3;
+    if (camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL) return -3;
+    const size_t ws_bytes = field_errors_workspace(B, H, W, n_thresholds);       // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    if (n_thresholds > 0 && !thresholds_deg) return -3;
+    for (int k = 0; k < n_thresholds; ++k)
+        if (!(fabsf(thresholds_deg[k]) <= FLT_MAX)) return -3;
+    const size_t px = (size_t)B * H * W * sizeof(float);
+    struct Range { const void* p; size_t bytes; };
+    const Range in[] = {{d_cam, (size_t)B * 8 * sizeof(float)}, {d_grav, (size_t)B * 3 * sizeof(float)}, {d_up, 2 * px}, {d_lat, px},
+                        {d_up_conf, px}, {d_lat_conf, px}};
+    const Range out[] = {{d_stats, (size_t)B * 2 * (2 + n_thresholds) * sizeof(float)}, {d_workspace, ws_bytes}, {d_up_err, px},
+                         {d_lat_err, px}};
+    for (const Range& r : in)
+        if (reinterpret_cast<uintptr_t>(r.p) % 4) return -3;
+    for (size_t i = 0; i < 4; ++i) {
+        if (reinterpret_cast<uintptr_t>(out[i].p) % 4) return -3;
+        for (const Range& r : in)
+            if (ranges_overlap(out[i].p, out[i].bytes, r.p, r.bytes)) return -3;
+        for (size_t j = i + 1; j < 4; ++j)
+            if (ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return -3;
+    }
+    hipError_t e = launch_field_errors(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, n_thresholds,
+                                       thresholds_deg, d_workspace, d_stats, d_up_err, d_lat_err, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : -10;
 }
 

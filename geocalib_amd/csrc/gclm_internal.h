@@ -2,7 +2,8 @@
 // (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update,
 //  gclm_api.hip: C ABI (the entry points of the solve, the stage kernels and the three render kernels) and launch
 //  sequence, gclm_comm.hip: the communicator and its entry points; the render kernels over gclm_render.h --
-//  gclm_image.hip: image undistortion, gclm_pano.hip: panorama rendering, gclm_persp.hip: perspective fields).  gfx950 only.
+//  gclm_image.hip: image undistortion, gclm_pano.hip: panorama rendering, gclm_persp.hip: perspective fields; and
+//  gclm_metrics.hip: the errors of predicted fields against a calibration, over the same header).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -219,5 +220,13 @@ hipError_t launch_render_from_pano(int camera_model, const float* cam, int cam_b
                                    const int* src_hw, int n, int C, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_perspective_fields(int camera_model, const float* cam, const float* grav, int B, int H, int W, int normalize,
                                      float* up /* or nullptr */, float* lat /* or nullptr */, hipStream_t s);
+
+
+// gclm_metrics.hip
+size_t field_errors_workspace(int B, int H, int W, int n_thresholds);     // bytes of one call's partial records; 0: sizes out of range
+hipError_t launch_field_errors(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
+                               const float* lat, const float* upc, const float* latc, int n_thresholds,
+                               const float* thresholds /* host */, void* workspace, float* stats, float* up_err /* or nullptr */,
+                               float* lat_err /* or nullptr */, hipStream_t s);
 
 }  // namespace gclm

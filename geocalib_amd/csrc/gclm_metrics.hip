@@ -1,0 +1,288 @@
+// gclm_metrics.hip -- gclm_field_errors: how well predicted perspective fields agree with a calibration, per image, in one
+// pass over the planes (the reference's up_error / latitude_error, siclib/models/utils/metrics.py:95-123, and the decoders'
+// metrics built on them, up_decoder.py:111-128, latitude_decoder.py:116-133, with the target fields of
+// get_perspective_field evaluated per pixel in registers instead of rendered to memory and read back).
+//
+// Per pixel, with t_up (normalised) and t_lat the target of gclm_render.h's persp_up / persp_lat at the camera and gravity:
+//   up:  e = deg(angle(p, t_up)) * mask,  mask = (p_x + p_y != 0) in float32 (up_decoder.py:115, as written)
+//        angle = acos(clamp(F.cosine_similarity(p, t, dim=1), -1, 1)): with P = p / max(|p|, 1e-8), T = t / max(|t|, 1e-8),
+//        the cosine is P . T.  Where both norms reach 1e-8 the angle is atan2(|p x t|, p . t), which resolves small angles
+//        (float32 acos cannot: acos(1 - 2^-24) = 0.02 deg is its smallest non-zero value); otherwise |P| |T| < 1 and the
+//        angle is atan2(sqrt((1 - |P|^2 |T|^2) + (P x T)^2), P . T), the same acos written without the cancellation.
+//   lat: e = |lat - t_lat| * 180 / pi
+// A masked pixel has error 0 (a hit at every threshold); a NaN prediction gives a NaN error (NaN * 0 stays NaN), which
+// makes the image's sums NaN and counts at no threshold.
+//
+// Per image: mean = sum e / (H W), weighted = sum(e conf) / sum conf, recall@t = #(e < t) / (H W).
+//
+// Layout: the tile geometry of gclm_render.h -- one wave walks 64 PX adjacent pixels of a row, 4 waves cover 4 rows, grid =
+// (tiles of one image, B).  A lane sums its PX pixels in float32, a wave sums its lanes with a butterfly of shuffles (every
+// lane ends with the same bits), the counts are ballots (wave-uniform integers); lane 0 of each wave leaves its record in
+// LDS, and after ONE barrier the block writes one partial record per tile into the caller's workspace:
+//   words [0, 6): float sum e_up, sum e_up c_up, sum c_up, sum e_lat, sum e_lat c_lat, sum c_lat;  then n_thresholds
+//   uint32 counts of up, then of latitude.
+// field_error_finish_kernel (grid = B) then sums each image's records in float64 in a fixed order (eight strided chains,
+// combined in order) and writes the statistics.  No atomics, no block waits on another: the bits of an image's statistics
+// depend on that image's pixels, H, W and the pixels per lane alone.
+//
+// Pixels per lane: PX = 4 (dwordx4 loads) where W % 4 == 0 and every plane is 16-byte aligned, else 2 (dwordx2) where W is
+// even and every plane 8-byte aligned, else 1; the planes of every image of a batch then share the alignment of the
+// first, so an image's path does not depend on its place in the batch.  64-bit offsets.  No scratch.
+// Measured (both confidences, four against two pixels per lane in one process): -5 % (pinhole) /
+// -1 .. 0 % (simple_divisional) kernel time at B = 1024, -13 % / -9 % at B = 16: four kept.
+#include "gclm_render.h"
+
+namespace gclm {
+namespace {
+
+constexpr int kMaxThr = GCLM_MAX_RECALL_THRESHOLDS;
+constexpr int kSumWords = 6;                 // float sums per record; 2 n_thresholds counts follow
+constexpr int kChains = 8;                   // summation chains per image of the second launch
+constexpr float kDegrees = 57.29577951308232f;
+constexpr float kCosEps = 1e-8f;             // F.cosine_similarity's eps
+
+struct FieldErrArgs {
+    const float *cam, *grav, *up, *lat, *upc, *latc;
+    float *up_err, *lat_err;
+    uint32_t* rec;
+    int H, W, tiles_x, nth;
+    float thr[kMaxThr];
+};
+
+template <int PX>
+__device__ __forceinline__ void load_px(const float* __restrict__ p, float (&v)[PX]) {
+    if constexpr (PX == 1) {
+        v[0] = *p;
+    } else if constexpr (PX == 2) {
+        const f32x2 t = *reinterpret_cast<const f32x2*>(p);
+        v[0] = t.x, v[1] = t.y;
+    } else {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    }
+}
+
+template <int PX>
+__device__ __forceinline__ void store_px(const float (&v)[PX], float* p) {
+    if constexpr (PX == 1) {
+        store_nt(v[0], p);
+    } else if constexpr (PX == 2) {
+        store_nt(f32x2{v[0], v[1]}, reinterpret_cast<f32x2*>(p));
+    } else {
+        store_nt(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
+    }
+}
+
+// Sum over the 64 lanes of a wave, the same bits in every lane (a butterfly: lane i adds lane i ^ o, o = 32 .. 1).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The masked up error in degrees (file header).
+__device__ __forceinline__ float up_error_deg(float px, float py, f32x2 t) {
+    const float pn2 = px * px + py * py, tn2 = t.x * t.x + t.y * t.y;
+    float dot = px * t.x + py * t.y, crs = px * t.y - py * t.x, sn;
+    if (pn2 >= kCosEps * kCosEps && tn2 >= kCosEps * kCosEps) {
+        sn = fabsf(crs);
+    } else {                                  // a norm below eps (or NaN): the cosine is taken of vectors shorter than 1
+        float pn = sqrtf(pn2), tn = sqrtf(tn2);
+        pn = pn < kCosEps ? kCosEps : pn;      // clamp_min; a NaN norm stays NaN
+        tn = tn < kCosEps ? kCosEps : tn;
+        const float ip = 1.f / pn, it = 1.f / tn;
+        dot *= ip * it, crs *= ip * it;
+        const float n = (pn2 * ip * ip) * (tn2 * it * it), gap = 1.f - n;
+        sn = sqrtf((gap > 0.f ? gap : 0.f) + crs * crs);
+    }
+    const float e = atan2f(sn, dot) * kDegrees;
+    return e * (px + py != 0.f ? 1.f : 0.f);  // NaN * 0 = NaN, as torch
+}
+
+template <int MODEL, int PX>
+__global__ __launch_bounds__(kBlock) void field_error_kernel(const FieldErrArgs a) {
+    __shared__ float s_sum[kTileRows][kSumWords];
+    __shared__ uint32_t s_cnt[kTileRows][2 * kMaxThr];
+    int x, y;
+    const bool in = tile_pixel<PX>(a.tiles_x, a.H, a.W, x, y);
+    const int b = blockIdx.y, wave = threadIdx.x >> 6;
+    const float nan = __builtin_nanf("");
+    float e_up[PX], e_lat[PX];
+    float sum[kSumWords] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < PX; ++j) e_up[j] = e_lat[j] = nan;      // a lane outside the image counts at no threshold
+    if (in) {
+        const float* cb = a.cam + (size_t)b * 8;
+        const float* gb = a.grav + (size_t)b * 3;
+        PerspRow r;
+        r.ifx = 1.f / cb[2];
+        r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
+        r.a = gb[0], r.b = gb[1], r.c = gb[2];
+        r.v = ((float)y - cb[5]) * (1.f / cb[3]);
+        r.v2 = r.v * r.v;
+        r.py = r.b - r.c * r.v;
+        // PX > 1 runs only where W % PX == 0: x is a multiple of PX, so x + PX <= W
+        const size_t hw = (size_t)a.H * a.W, o = (size_t)b * hw + (size_t)y * a.W + x;
+        float u[PX], r2[PX];
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            u[j] = ((float)(x + j) - r.cx) * r.ifx;
+            r2[j] = u[j] * u[j] + r.v2;
+        }
+        if (a.up) {
+            float px[PX], py[PX];
+            load_px<PX>(a.up + o + (size_t)b * hw, px);          // (B, 2, H, W): image b starts at 2 b H W
+            load_px<PX>(a.up + o + (size_t)b * hw + hw, py);
+#pragma unroll
+            for (int j = 0; j < PX; ++j) {
+                e_up[j] = up_error_deg(px[j], py[j], persp_up<MODEL>(r, u[j], r2[j], true));
+                sum[0] += e_up[j];
+            }
+            if (a.upc) {
+                float c[PX];
+                load_px<PX>(a.upc + o, c);
+#pragma unroll
+                for (int j = 0; j < PX; ++j) sum[1] += e_up[j] * c[j], sum[2] += c[j];
+            }
+            if (a.up_err) store_px<PX>(e_up, a.up_err + o);
+        }
+        if (a.lat) {
+            float l[PX];
+            load_px<PX>(a.lat + o, l);
+#pragma unroll
+            for (int j = 0; j < PX; ++j) {
+                e_lat[j] = fabsf(l[j] - persp_lat<MODEL>(r, u[j], r2[j])) * kDegrees;
+                sum[3] += e_lat[j];
+            }
+            if (a.latc) {
+                float c[PX];
+                load_px<PX>(a.latc + o, c);
+#pragma unroll
+                for (int j = 0; j < PX; ++j) sum[4] += e_lat[j] * c[j], sum[5] += c[j];
+            }
+            if (a.lat_err) store_px<PX>(e_lat, a.lat_err + o);
+        }
+    }
+    // every lane of the block from here on: wave sums, wave-uniform counts, one record per wave in LDS
+#pragma unroll
+    for (int k = 0; k < kSumWords; ++k) sum[k] = wave_sum(sum[k]);
+    uint32_t cnt[2 * kMaxThr];
+#pragma unroll
+    for (int k = 0; k < kMaxThr; ++k) {
+        uint32_t nu = 0, nl = 0;
+        if (k < a.nth) {
+            const float t = a.thr[k];
+#pragma unroll
+            for (int j = 0; j < PX; ++j) {
+                nu += (uint32_t)__popcll(__ballot(e_up[j] < t));
+                nl += (uint32_t)__popcll(__ballot(e_lat[j] < t));
+            }
+        }
+        cnt[k] = nu, cnt[kMaxThr + k] = nl;
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kSumWords; ++k) s_sum[wave][k] = sum[k];
+#pragma unroll
+        for (int k = 0; k < 2 * kMaxThr; ++k) s_cnt[wave][k] = cnt[k];
+    }
+    __syncthreads();
+    const int k = threadIdx.x, words = kSumWords + 2 * a.nth;
+    if (k < words) {
+        uint32_t w;
+        if (k < kSumWords) {
+            float s = s_sum[0][k];
+            for (int i = 1; i < kTileRows; ++i) s += s_sum[i][k];
+            w = __float_as_uint(s);
+        } else {
+            const int c = k - kSumWords, col = c < a.nth ? c : kMaxThr + (c - a.nth);
+            w = 0;
+            for (int i = 0; i < kTileRows; ++i) w += s_cnt[i][col];
+        }
+        a.rec[((size_t)b * gridDim.x + blockIdx.x) * words + k] = w;
+    }
+}
+
+// One block per image: word k of the image's records is summed by kChains chains (record t goes to chain t % kChains), the
+// chains are added in order, all in float64 (the counts are exact in it).  stats (B, 2 (2 + nth)), file header.
+__global__ __launch_bounds__(kBlock) void field_error_finish_kernel(const uint32_t* __restrict__ rec, int tiles, int nth, int hw,
+                                                                    int has_up, int has_upc, int has_lat, int has_latc,
+                                                                    float* __restrict__ stats) {
+    __shared__ double part[kChains][32];
+    const int b = blockIdx.x, k = threadIdx.x & 31, chain = threadIdx.x >> 5, words = kSumWords + 2 * nth;
+    double acc = 0.0;
+    if (k < words) {
+        const uint32_t* p = rec + (size_t)b * tiles * words + k;
+        for (int t = chain; t < tiles; t += kChains) {
+            const uint32_t w = p[(size_t)t * words];
+            acc += k < kSumWords ? (double)__uint_as_float(w) : (double)w;
+        }
+    }
+    part[chain][k] = acc;
+    __syncthreads();
+    if (threadIdx.x < 32) {
+        double s = part[0][k];
+        for (int i = 1; i < kChains; ++i) s += part[i][k];
+        part[0][k] = s;
+    }
+    __syncthreads();
+    const int per = 2 + nth, i = threadIdx.x;
+    if (i < 2 * per) {
+        const int field = i / per, m = i - field * per;
+        const bool has = field ? has_lat != 0 : has_up != 0, hasc = field ? has_latc != 0 : has_upc != 0;
+        double v;
+        if (m == 0) v = part[0][3 * field] / (double)hw;
+        else if (m == 1) v = hasc ? part[0][3 * field + 1] / part[0][3 * field + 2] : (double)__builtin_nanf("");
+        else v = part[0][kSumWords + field * nth + (m - 2)] / (double)hw;
+        stats[(size_t)b * 2 * per + i] = has ? (float)v : __builtin_nanf("");
+    }
+}
+
+// The most pixels per lane: a build with -DGCLM_METRICS_MAX_PX=2 is the measured alternative (scripts/field_metrics_bench.py
+// --variant-lib times such a build against this one).
+#ifndef GCLM_METRICS_MAX_PX
+#define GCLM_METRICS_MAX_PX 4
+#endif
+
+// pixels per lane of a call (file header)
+int pixels_per_lane(int W, const float* up, const float* lat, const float* upc, const float* latc, const float* up_err,
+                    const float* lat_err) {
+    uintptr_t bits = 0;
+    for (const float* p : {up, lat, upc, latc, up_err, lat_err}) bits |= reinterpret_cast<uintptr_t>(p);
+    if (GCLM_METRICS_MAX_PX >= 4 && W % 4 == 0 && bits % 16 == 0) return 4;
+    return W % 2 == 0 && bits % 8 == 0 ? 2 : 1;
+}
+
+}  // namespace
+
+size_t field_errors_workspace(int B, int H, int W, int n_thresholds) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || n_thresholds < 0 || n_thresholds > kMaxThr) return 0;
+    if ((int64_t)H * W > INT32_MAX || (((int64_t)W + 63) / 64) * (((int64_t)H + kTileRows - 1) / kTileRows) * kBlock > UINT32_MAX) return 0;
+    // sized for one pixel per lane, the path with the most tiles
+    return (size_t)B * tile_count(H, W, 1) * (kSumWords + 2 * n_thresholds) * sizeof(uint32_t);
+}
+
+hipError_t launch_field_errors(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
+                               const float* lat, const float* upc, const float* latc, int n_thresholds, const float* thresholds,
+                               void* workspace, float* stats, float* up_err, float* lat_err, hipStream_t st) {
+    const int px = pixels_per_lane(W, up, lat, upc, latc, up_err, lat_err);
+    FieldErrArgs a{cam, grav, up, lat, upc, latc, up_err, lat_err, static_cast<uint32_t*>(workspace), H, W, tile_columns(W, px),
+                   n_thresholds, {}};
+    for (int k = 0; k < n_thresholds; ++k) a.thr[k] = thresholds[k];
+    const int tiles = tile_count(H, W, px);
+    return with_camera_model(camera_model, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        auto kernel = px == 2 ? field_error_kernel<M, 2> : field_error_kernel<M, 1>;
+#if GCLM_METRICS_MAX_PX >= 4
+        if (px == 4) kernel = field_error_kernel<M, 4>;
+#endif
+        hipLaunchKernelGGL(kernel, dim3(tiles, B), dim3(kBlock), 0, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(field_error_finish_kernel, dim3(B), dim3(kBlock), 0, st, static_cast<const uint32_t*>(workspace), tiles,
+                           n_thresholds, H * W, up != nullptr, upc != nullptr, lat != nullptr, latc != nullptr, stats);
+        return hipGetLastError();
+    });
+}
+
+}  // namespace gclm

@@ -12,8 +12,9 @@
 // Gravity is used as stored (not renormalised), as the reference's dot product does.  |(u t, v t, 1)| >= 1 or NaN, so the
 // reference's max(|.|, 1e-12) guard of the ray never acts and is not evaluated.
 //
-// s, s' (distort scale and ds/dr2) and t (undistort scale) per model are gclm_render.h's: the reference's definitions in
-// forms that do not cancel in float32, held to float64 (tests/perspective_gate.py).
+// persp_up / persp_lat (the two formulas above) and s, s' (distort scale and ds/dr2), t (undistort scale) per model are
+// gclm_render.h's: the reference's definitions in forms that do not cancel in float32, held to float64
+// (tests/perspective_gate.py).  gclm_metrics.hip scores fields against the same text.
 //
 // NaN: a NaN or inf in the camera or gravity gives NaN wherever the torch composition gives NaN.  Both guards (the norm's
 // 1e-12 floor and the clamp) are comparisons that keep a NaN operand, not fminf / fmaxf, which would drop it.
@@ -27,43 +28,6 @@
 
 namespace gclm {
 namespace {
-
-constexpr float kLatHi = (float)(1.0 - 1e-6);                 // the reference's clamp bound, as torch rounds it to float32
-
-// Per-image and per-row terms of one lane's pixels.
-struct PerspRow {
-    float ifx, cx, k1, k2, a, b, c;
-    float v, v2, py;            // per row: v, v^2, b - c v
-};
-
-template <int MODEL>
-__device__ __forceinline__ f32x2 persp_up(const PerspRow& r, float u, float r2, bool normalize) {
-    const float px = r.a - r.c * u;
-    float qx = px, qy = r.py;
-    if constexpr (MODEL != GCLM_PINHOLE) {
-        float s, sp;
-        distort_scale<MODEL>(r2, r.k1, r.k2, s, sp);
-        const float o = 2.f * sp * (u * px + r.v * r.py);
-        qx = s * px + o * u;
-        qy = s * r.py + o * r.v;
-    }
-    if (normalize) {
-        float n = sqrtf(qx * qx + qy * qy);
-        n = n < 1e-12f ? 1e-12f : n;            // F.normalize's clamp_min; a NaN norm stays NaN
-        const float in = 1.f / n;
-        qx *= in, qy *= in;
-    }
-    return f32x2{qx, qy};
-}
-
-template <int MODEL>
-__device__ __forceinline__ float persp_lat(const PerspRow& r, float u, float r2) {
-    const float t = undistort_scale<MODEL>(r2, r.k1, r.k2);
-    const float X = u * t, Y = r.v * t;
-    float sl = (X * r.a + Y * r.b + r.c) / sqrtf(X * X + Y * Y + 1.f);
-    sl = sl < -kLatHi ? -kLatHi : (sl > kLatHi ? kLatHi : sl);    // a NaN stays NaN
-    return asinf(sl);
-}
 
 template <int MODEL, int PX>
 __global__ __launch_bounds__(kBlock) void perspective_field_kernel(const float* __restrict__ cam, const float* __restrict__ grav,

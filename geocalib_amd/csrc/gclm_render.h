@@ -1,6 +1,7 @@
-// gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_persp.hip; device
-// code, included by those three only): the camera models' undistort and distort scales, the zero-padded bilinear sampler,
-// the nontemporal store and the tile geometry.  Each kernel keeps its own coordinate formula.
+// gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_persp.hip) and of
+// the kernel that scores fields against a calibration (gclm_metrics.hip); device code, included by those four only: the
+// camera models' undistort and distort scales, the zero-padded bilinear sampler, the nontemporal store, the tile geometry
+// and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
 //
 // Nothing here is shared with the LM sweep (gclm_pass.hip) or with synth_kernel (gclm_update.hip), on purpose: the sweep
 // keeps the reference's float32 forms so that the solve rounds like the reference, and the synthetic fields' bits define
@@ -115,6 +116,45 @@ __device__ __forceinline__ float bilinear_sample(const float* __restrict__ p, co
     const float v00 = t.m00 ? p[t.o] : 0.f, v01 = t.m01 ? p[t.o + 1] : 0.f;
     const float v10 = t.m10 ? p[t.o + Win] : 0.f, v11 = t.m11 ? p[t.o + Win + 1] : 0.f;
     return v00 * t.w00 + v01 * t.w01 + v10 * t.w10 + v11 * t.w11;
+}
+
+// The perspective fields of one pixel (gclm_persp.hip renders them, gclm_metrics.hip scores predictions against them; the
+// formulas are in gclm_persp.hip's header and include/gclm.h: gclm_perspective_fields).
+constexpr float kLatHi = (float)(1.0 - 1e-6);                 // the reference's clamp bound, as torch rounds it to float32
+
+// Per-image and per-row terms of one lane's pixels.
+struct PerspRow {
+    float ifx, cx, k1, k2, a, b, c;
+    float v, v2, py;            // per row: v, v^2, b - c v
+};
+
+template <int MODEL>
+__device__ __forceinline__ f32x2 persp_up(const PerspRow& r, float u, float r2, bool normalize) {
+    const float px = r.a - r.c * u;
+    float qx = px, qy = r.py;
+    if constexpr (MODEL != GCLM_PINHOLE) {
+        float s, sp;
+        distort_scale<MODEL>(r2, r.k1, r.k2, s, sp);
+        const float o = 2.f * sp * (u * px + r.v * r.py);
+        qx = s * px + o * u;
+        qy = s * r.py + o * r.v;
+    }
+    if (normalize) {
+        float n = sqrtf(qx * qx + qy * qy);
+        n = n < 1e-12f ? 1e-12f : n;            // F.normalize's clamp_min; a NaN norm stays NaN
+        const float in = 1.f / n;
+        qx *= in, qy *= in;
+    }
+    return f32x2{qx, qy};
+}
+
+template <int MODEL>
+__device__ __forceinline__ float persp_lat(const PerspRow& r, float u, float r2) {
+    const float t = undistort_scale<MODEL>(r2, r.k1, r.k2);
+    const float X = u * t, Y = r.v * t;
+    float sl = (X * r.a + Y * r.b + r.c) / sqrtf(X * X + Y * Y + 1.f);
+    sl = sl < -kLatHi ? -kLatHi : (sl > kLatHi ? kLatHi : sl);    // a NaN stays NaN
+    return asinf(sl);
 }
 
 }  // namespace gclm

@@ -198,3 +198,47 @@ def perspective_fields(camera_model: str, cam: torch.Tensor, grav: torch.Tensor,
                    int(normalize), None if u is None else u[b0].data_ptr(), None if lat is None else lat[b0].data_ptr(),
                    _call.raw_stream(cam.device), device=cam.device)
     return u, lat
+
+
+def field_errors(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: Optional[torch.Tensor] = None,
+                 lat: Optional[torch.Tensor] = None, up_conf: Optional[torch.Tensor] = None,
+                 lat_conf: Optional[torch.Tensor] = None, thresholds=(1.0, 3.0, 5.0, 10.0), return_errors: bool = False):
+    """gclm_field_errors: predicted fields `up` (B, 2, H, W) / `lat` (B, 1, H, W) (one may be None) and their confidences
+    (B, H, W) scored against the fields of cameras `cam` (B, 8) and gravities `grav` (B, 3), float32 on one HIP device, in one
+    pass per 65 535 images on torch's current stream.  Returns (stats, up_error, latitude_error): stats (B, 2 (2 + n)) as
+    include/gclm.h lays them out -- [mean, weighted, recall@t.. ] of up, then of latitude, NaN where a plane is absent -- and
+    with `return_errors` the per-pixel errors in degrees (B, H, W) of the fields given, else None.
+    metrics.perspective_field_metrics is the public entry; not differentiable."""
+    if up is None and lat is None:
+        raise ValueError("at least one of the up and latitude fields is needed")
+    if (up is None and up_conf is not None) or (lat is None and lat_conf is not None):
+        raise ValueError("a confidence needs its field")
+    cam, grav = _call.dev_f32(cam, "cam").reshape(-1, 8), _call.dev_f32(grav, "grav").reshape(-1, 3)
+    dev, B = cam.device, cam.shape[0]
+    planes = {"up": up, "lat": lat, "up_conf": up_conf, "lat_conf": lat_conf}
+    planes = {k: None if t is None else _call.dev_f32(t, k) for k, t in planes.items()}
+    H, W = (planes["up"] if lat is None else planes["lat"]).shape[-2:]
+    for k, t in planes.items():
+        want = B * H * W * (2 if k == "up" else 1)
+        if t is not None and (t.numel() != want or t.shape[-2:] != (H, W) or t.device != dev):
+            raise ValueError(f"`{k}` {tuple(t.shape)} on {t.device} does not fit {B} images of {H} x {W} on {dev}")
+    if grav.shape[0] != B or grav.device != dev:
+        raise ValueError(f"camera batch {B} and gravity batch {grav.shape[0]} must be equal and on one device")
+    thr = [float(t) for t in thresholds]
+    S = 2 * (2 + len(thr))
+    stats = cam.new_empty((B, S))
+    up_err = cam.new_empty((B, H, W)) if return_errors and up is not None else None
+    lat_err = cam.new_empty((B, H, W)) if return_errors and lat is not None else None
+    if B * H * W == 0:
+        return stats.fill_(float("nan")), up_err, lat_err
+    lib = _lib.load()
+    ws_bytes = int(lib.gclm_field_errors_workspace(min(B, _call.MAX_CALL), H, W, len(thr)))
+    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=dev)
+    c_thr = (_lib.C.c_float * len(thr))(*thr)
+    at = lambda t, b0: None if t is None else t[b0].data_ptr()  # noqa: E731
+    for b0, n in _call.slices(B):
+        _call.call("gclm_field_errors", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, H, W,
+                   at(planes["up"], b0), at(planes["lat"], b0), at(planes["up_conf"], b0), at(planes["lat_conf"], b0), len(thr),
+                   c_thr, ws.data_ptr(), ws_bytes, stats[b0].data_ptr(), at(up_err, b0), at(lat_err, b0), _call.raw_stream(dev),
+                   device=dev)
+    return stats, up_err, lat_err

@@ -46,7 +46,8 @@ extern "C" {
  * added -- radial / simple_divisional batches walk row pairs by default, results equal the one-row walk's to summation order;
  * additive within 610: gclm_pack_fields_ex, gclm_solve_ex, gclm_calibrate_ex and gclm_shared_begin_ex added -- the head
  * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged; gclm_undistort_image,
- * gclm_render_from_pano and gclm_perspective_fields added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
+ * gclm_render_from_pano and gclm_perspective_fields added, also within 610; gclm_field_errors and
+ * gclm_field_errors_workspace added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -60,6 +61,7 @@ enum gclm_camera_model {
 
 #define GCLM_MAX_PARAMS 5     /* delta_g1, delta_g2, focal, k1, k2 */
 #define GCLM_MAX_STEPS 256
+#define GCLM_MAX_RECALL_THRESHOLDS 8     /* gclm_field_errors */
 #define GCLM_CAM_STRIDE 8     /* {w,h,fx,fy,cx,cy,k1,k2}: BaseCamera._data, camera.py:25-41 */
 #define GCLM_GRAV_STRIDE 3    /* unit gravity: Gravity._data, gravity.py:18-28 */
 
@@ -322,6 +324,47 @@ int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, co
  */
 int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W,
                             int normalize_up, float* d_up, float* d_lat, void* stream);
+
+/*
+ * How well predicted perspective fields agree with a calibration, per image, in one pass over the planes: the reference's
+ * up_error / latitude_error (siclib/models/utils/metrics.py:95-123) and the decoders' metrics built on them
+ * (up_decoder.py:111-128, latitude_decoder.py:116-133), with the target fields of gclm_perspective_fields (normalize_up = 1)
+ * at d_cam (B, 8) / d_grav (B, 3) evaluated per pixel in registers -- no target field is written or read.  Predictions in
+ * the layout the solve takes: d_up (B, 2, H, W) planar, d_lat (B, 1, H, W), either may be NULL, not both; confidences
+ * d_up_conf, d_lat_conf (B, H, W), either may be NULL.  All float32 in device memory; gravity is used as stored.
+ * Per pixel, with t_up, t_lat the target:
+ *   up:  e = deg(angle(p, t_up)) * mask.  The angle is acos(clamp(cosine_similarity(p, t_up), -1, 1)) with torch's
+ *        eps = 1e-8, i.e. of P = p / max(|p|, eps) and T = t_up / max(|t_up|, eps), evaluated as atan2(|p x t|, p . t) where
+ *        both norms reach eps and as atan2(sqrt((1 - |P|^2 |T|^2) + (P x T)^2), P . T) otherwise: forms that resolve small
+ *        angles in float32, where acos of a cosine cannot (its smallest non-zero value is 0.02 degrees).
+ *        mask = (p_x + p_y != 0) evaluated in float32, the reference's mask as written: a masked pixel has error 0 and is a
+ *        hit at every threshold.
+ *   lat: e = |lat - t_lat| * 180 / pi
+ * NaN: a NaN prediction gives a NaN error (NaN * 0 stays NaN, as in torch); it makes that image's mean and weighted mean
+ * of that field NaN and counts at no threshold; other images are untouched.
+ * d_stats (B, S), S = 2 (2 + n_thresholds):  [up_mean, up_weighted, up_recall@t0 .., lat_mean, lat_weighted, lat_recall@t0 ..]
+ *   mean = sum e / (H W) (all pixels, masked ones included);  weighted = sum(e conf) / sum conf (0 / 0 = NaN; NaN where that
+ *   confidence is NULL);  recall@t = #(e < t) / (H W), strict;  the entries of a field whose pointer is NULL are NaN.
+ * thresholds_deg is a HOST array of n_thresholds (0 .. GCLM_MAX_RECALL_THRESHOLDS) finite values in degrees, read before
+ * the call returns.  Optional d_up_err, d_lat_err (B, H, W): the per-pixel errors (up_error * mask, latitude_error).
+ * Every workgroup leaves one partial record (float32 sums, integer counts) in d_workspace, of at least
+ * gclm_field_errors_workspace(B, H, W, n_thresholds) bytes (0 for sizes the call refuses); a second small launch sums each
+ * image's records in float64 in a fixed order.  No atomics: results are bit-identical from call to call, and an image's
+ * statistics do not depend on the other images of the batch (they depend on its pixels, H, W and on the planes' alignment:
+ * four pixels per lane where W % 4 == 0 and every plane is 16-byte aligned, two where W is even and every plane 8-byte
+ * aligned, one otherwise).
+ * Returns -3 (before any HIP call) for a NULL d_cam, d_grav, d_stats or d_workspace, both fields NULL, a confidence or an
+ * error map given for a NULL field, B outside 1..65535, H or W < 1, H * W > 2^31 - 1 (or a grid of (W / 64) x (H / 4) tiles
+ * over 2^32 threads), a camera_model outside 0..3, n_thresholds outside 0..8, NULL thresholds with n_thresholds > 0, a
+ * non-finite threshold, a workspace that is too small, a pointer that is not 4-byte aligned, or an output (statistics,
+ * workspace, error maps) that overlaps an input or another output; -10 if a launch fails.  Asynchronous on `stream`; no
+ * allocation.
+ */
+size_t gclm_field_errors_workspace(int B, int H, int W, int n_thresholds);
+int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                      const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int n_thresholds,
+                      const float* thresholds_deg, void* d_workspace, size_t workspace_bytes, float* d_stats, float* d_up_err,
+                      float* d_lat_err, void* stream);
 
 /*
  * BaseCamera.get_img_from_pano (geocalib/camera.py:414-514) for n images, in one pass: d_dst (n, C, H, W) holds image i
