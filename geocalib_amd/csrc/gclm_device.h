@@ -1,5 +1,5 @@
-// gclm_device.h -- per-image device logic shared by the update kernels (gclm_update.hip) and the prologue of the
-// one-launch-per-step sweep for single images (gclm_pass.hip: fused_step_kernel).  gfx950 only.
+// gclm_device.h -- per-image device logic shared by the update kernels (gclm_update.hip), the prologue of the
+// one-launch-per-step sweep for single images (gclm_pass.hip: fused_step_kernel) and the stage kernels.  gfx950 only.
 #pragma once
 #include "gclm_internal.h"
 
@@ -135,16 +135,28 @@ __device__ inline void build_pblock(const State& s, bool spherical, bool log_foc
     fill_pblock(s, T, 1.0f / s.fx, 1.0f / s.fy, log_focal, p);
 }
 
+// A camera row (GCLM_CAM_STRIDE floats, BaseCamera._data) plus a gravity vector (normalised here) as a State, and back:
+// every kernel that takes or hands out (cam, grav) goes through these two.  The optimiser's own fields are left zero.
+static_assert(GCLM_CAM_STRIDE == 8, "w h fx fy cx cy k1 k2");
+__device__ inline State state_from_params(const float* cm, const float* grav) {
+    State s{};
+    s.w = cm[0]; s.h = cm[1]; s.fx = cm[2]; s.fy = cm[3]; s.cx = cm[4]; s.cy = cm[5]; s.k1 = cm[6]; s.k2 = cm[7];
+    const V3 g = normalize3({grav[0], grav[1], grav[2]});
+    s.gx = g.x; s.gy = g.y; s.gz = g.z;
+    return s;
+}
+__device__ inline void params_from_state(const State& s, float* cm, float* grav) {
+    cm[0] = s.w; cm[1] = s.h; cm[2] = s.fx; cm[3] = s.fy; cm[4] = s.cx; cm[5] = s.cy; cm[6] = s.k1; cm[7] = s.k2;
+    grav[0] = s.gx; grav[1] = s.gy; grav[2] = s.gz;
+}
+
 // The initial estimate of image b: the caller's (gclm_solve) or get_trivial_estimation / siclib's heuristic from the priors
 // (gclm_calibrate).  init_kernel runs it once per image; the one-launch-per-step kernel runs it in the prologue of its
 // first launch instead (every workgroup of the image, same bits), which saves a single-image solve the init launch.
 __device__ inline State init_state(const SolveCtx& c, const InitArgs& ia, int b) {
     State s;
-    V3 g;
     if (ia.cam) {       // caller-provided initial estimate
-        const float* cm = ia.cam + (size_t)b * GCLM_CAM_STRIDE;
-        s.w = cm[0]; s.h = cm[1]; s.fx = cm[2]; s.fy = cm[3]; s.cx = cm[4]; s.cy = cm[5]; s.k1 = cm[6]; s.k2 = cm[7];
-        g = normalize3({ia.grav[b * 3], ia.grav[b * 3 + 1], ia.grav[b * 3 + 2]});
+        s = state_from_params(ia.cam + (size_t)b * GCLM_CAM_STRIDE, ia.grav + b * 3);
     } else {            // get_trivial_estimation (lm_optimizer.py:20-58) + BaseCamera.from_dict (camera.py:49-93)
         const float h = (float)c.H, w = (float)c.W;
         const float focal = ia.prior_focal ? ia.prior_focal[b] : 0.7f * fmaxf(h, w);
@@ -158,7 +170,7 @@ __device__ inline State init_state(const SolveCtx& c, const InitArgs& ia, int b)
             s.k1 = ia.prior_dist[(size_t)b * nd];
             if (nd > 1) s.k2 = ia.prior_dist[(size_t)b * nd + 1];
         }
-        g = V3{-0.0f, -1.0f, 0.0f};                                   // Gravity.from_rp(0, 0)
+        V3 g{-0.0f, -1.0f, 0.0f};                                     // Gravity.from_rp(0, 0)
         if (c.cfg.heuristic_init && ia.up) {
             // get_heuristic_estimation (siclib/models/optimization/utils.py:27-82): roll = angle of the up
             // vector at the image centre, pitch = latitude at the centre, vfov = |lat(top) - lat(bottom)|
@@ -181,8 +193,8 @@ __device__ inline State init_state(const SolveCtx& c, const InitArgs& ia, int b)
             g = from_rp(roll, pitch);
         }
         if (ia.prior_gravity) g = normalize3({ia.prior_gravity[b * 3], ia.prior_gravity[b * 3 + 1], ia.prior_gravity[b * 3 + 2]});
+        s.gx = g.x; s.gy = g.y; s.gz = g.z;
     }
-    s.gx = g.x; s.gy = g.y; s.gz = g.z;
     s.lambda = c.cfg.lambda0; s.prev_cost = 0.f; s.fails = 0.f; s.init_cu = s.init_cl = 0.f;
     return s;
 }
@@ -359,26 +371,79 @@ __device__ inline bool lm_step(const gclm_config& cfg, int H, int W, int step, S
     return moved;
 }
 
-// ... applied to image b of a solve: state / parameter-block double buffers and the early-stop counters.
-template <int PM>
-__device__ inline void update_image(const SolveCtx& c, int step, int b, const float (&acc)[kNAccMax]) {
-    State s = c.state[step & 1][b];
-    if (lm_step<PM>(c.cfg, c.H, c.W, step, s, acc)) atomicAdd(&c.ctrl->notclose[step], 1);
+// The state after update `step` and its parameter block go into the OTHER half of the double buffers, for the next sweep.
+__device__ inline void commit_state(const SolveCtx& c, int step, int b, const State& s) {
     c.state[(step + 1) & 1][b] = s;
     PBlock p;
     build_pblock(s, c.cfg.use_spherical_manifold != 0, c.cfg.use_log_focal != 0, p);
     c.pb[(step + 1) & 1][b] = p;
 }
 
+// infos["stop_at"] (lm_optimizer.py:575,619-620,638): the first step after which EVERY image's cost was "close", i.e. the
+// first j in [1, num_steps) whose counter stayed 0, else num_steps (the counter of the last comparison cannot change the
+// answer).  The counters of one batch may lie in the control blocks of `n` handles (gclm_merge_stop_at): their sum decides.
+__device__ inline int first_quiet_step(const Ctrl* const* ctrl, int n, int num_steps) {
+    for (int j = 1; j < num_steps; ++j) {
+        int moved = 0;
+        for (int p = 0; p < n; ++p) moved += ctrl[p]->notclose[j];
+        if (moved == 0) return j;
+    }
+    return num_steps;
+}
+__device__ inline int first_quiet_step(const Ctrl* ctrl, int num_steps) { return first_quiet_step(&ctrl, 1, num_steps); }
+
 // ---------------------------------------------------------------- reduction of the sweep's partial records
-// Sum the workgroup partials of ONE image with the whole 256-thread block (8 groups x 32 slots), in the order the
-// update kernels use: >= kStripeMinChunks records -- 8 stripes of chunks (stripe g: g, g + 8, ...), combined in stripe
-// order; fewer -- one ascending walk.  Double accumulation, fixed order: every caller gets the same bits.  Must be
-// called by all threads of the block; the sums are valid in EVERY thread on return (read back from LDS).
+// A sweep leaves `nchunks` records of `nacc` floats per image; slot i of an image's system is the sum of slot i over them.
+// Blocks of 256 threads = kGroups groups x kSlots slots reduce them (the first nacc = 16 or 24 slots are live).
 constexpr int kGroups = 8, kSlots = 32, kStripeMinChunks = 33;
-// `after_first_batch()` runs right after the loads of the first batch of records have been ISSUED and before anything waits
-// for them: the caller's own independent loads (the one-launch-per-step kernel's first field values) queue up BEHIND the
-// records, so the reduction does not wait for them (loads return in order).
+// THE stripe rule.  Few records per image (large batches): one ascending walk per slot.  From kStripeMinChunks on (small
+// batches of large images, where one walk is a latency chain of hundreds of dependent loads): group g walks stripe g, g + 8,
+// ... and the eight stripe sums are combined in stripe order.  Everything that depends on the choice derives from here.
+struct Stripe { bool on; int first, stride; };
+__host__ __device__ inline bool records_striped(int nchunks) { return nchunks >= kStripeMinChunks; }
+__device__ inline Stripe stripe_of(int nchunks, int grp) {
+    const bool on = records_striped(nchunks);
+    return Stripe{on, on ? grp : 0, on ? kGroups : 1};
+}
+// THE record sum: records first, first + stride, ... < nchunks of one slot (`p`: that slot of record 0), in ascending
+// order, in double.  BATCH loads are in flight together (a clamped index and a select instead of a branch), so the 15
+// records of a 640x480 image, or the 19 of a stripe of a single one, cost one memory round trip.  The padding adds +0.0 to a
+// double that is never -0.0 (it starts at +0.0, and x + -x rounds to +0.0), so BATCH cannot change a bit: every caller gets
+// the same sum of the same records.  `after_first_batch()` runs once the first batch has been ISSUED and before anything
+// waits for it -- a caller's own independent loads queue up BEHIND the records (loads return in order) -- in every
+// thread, so call this in uniform control flow and say who sums with `active` (first < nchunks: an image has a record).
+template <int BATCH, typename Hook>
+__device__ inline double sum_records(bool active, const float* p, int nacc, int first, int stride, int nchunks,
+                                     Hook&& after_first_batch) {
+    float v[BATCH];
+    auto load = [&](int c0) {
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j) {
+            const int c = c0 + j * stride;
+            const float t = p[(size_t)min(c, nchunks - 1) * nacc];
+            v[j] = c < nchunks ? t : 0.f;
+        }
+    };
+    if (active) load(first);
+    after_first_batch();
+    double d = 0.0;
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j) d += v[j];
+        for (int c0 = first + BATCH * stride; c0 < nchunks; c0 += BATCH * stride) {
+            load(c0);
+#pragma unroll
+            for (int j = 0; j < BATCH; ++j) d += v[j];
+        }
+    }
+    return d;
+}
+template <int BATCH>
+__device__ inline double sum_records(bool active, const float* p, int nacc, int first, int stride, int nchunks) {
+    return sum_records<BATCH>(active, p, nacc, first, stride, nchunks, [] {});
+}
+// The records of ONE image summed by the whole block, stripes or one walk by the rule above: the prologue of the
+// one-launch-per-step kernel, which passes its first field loads as the hook.  Must be called by all threads of the block.
 // The sums are valid in the threads of WAVE 0 on return (lane i of wave 0 sums slot i over the stripes, v_readlane hands
 // the values to the whole wave): round 3 had every one of the 256 threads read all 8 x 24 doubles back from LDS -- 1 us of
 // LDS bandwidth at the head of every launch of a single-image solve (device trace, profiles/archive/r04_latency_trace.log).
@@ -387,43 +452,15 @@ __device__ inline void reduce_image_partials(const float* image_partials, int nc
                                              Hook&& after_first_batch) {
     __shared__ double sacc1[kGroups][kSlots + 1];
     const int grp = threadIdx.x / kSlots, slot = threadIdx.x % kSlots;
-    const bool striped = nchunks >= kStripeMinChunks;
-    const int first = striped ? grp : 0, stride = striped ? kGroups : 1;
-    const bool active = slot < nacc && (striped || grp == 0);
-    const float* p = image_partials + slot;
-    // batches of 32 records per thread: the 19 records of a stripe of a single 640x480 image (150 workgroups) are all
-    // in flight together -- one memory round trip; summed in ascending order (the padding adds exact zeros)
-    float v[32];
-    if (active) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const int c = first + j * stride;
-            const float t = p[(size_t)min(c, nchunks - 1) * nacc];      // unconditional load (a clamped index), then
-            v[j] = c < nchunks ? t : 0.f;                                // a select: all loads of the batch in flight
-        }
-    }
-    after_first_batch();                                                 // every thread, in uniform control flow
-    if (active) {
-        double d = 0.0;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) d += v[j];
-        for (int c0 = first + 32 * stride; c0 < nchunks; c0 += 32 * stride) {
-#pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                const int c = c0 + j * stride;
-                const float t = p[(size_t)min(c, nchunks - 1) * nacc];
-                v[j] = c < nchunks ? t : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < 32; ++j) d += v[j];
-        }
-        sacc1[grp][slot] = d;
-    }
+    const Stripe st = stripe_of(nchunks, grp);
+    const bool active = slot < nacc && (st.on || grp == 0);
+    const double sum = sum_records<32>(active, image_partials + slot, nacc, st.first, st.stride, nchunks, after_first_batch);
+    if (active) sacc1[grp][slot] = sum;
     __syncthreads();
     if (threadIdx.x < 64) {                                            // wave 0 (wave-uniform)
         double d = 0.0;
         if ((int)threadIdx.x < nacc) {
-            if (striped) { for (int g = 0; g < kGroups; ++g) d += sacc1[g][threadIdx.x]; }
+            if (st.on) { for (int g = 0; g < kGroups; ++g) d += sacc1[g][threadIdx.x]; }
             else d = sacc1[0][threadIdx.x];
         }
         const int mine = __builtin_bit_cast(int, (float)d);            // 0.0f in the lanes beyond nacc
@@ -431,12 +468,9 @@ __device__ inline void reduce_image_partials(const float* image_partials, int nc
         for (int i = 0; i < kNAccMax; ++i) acc[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(mine, i));
     }
 }
-__device__ inline void reduce_image_partials(const float* image_partials, int nchunks, int nacc, float (&acc)[kNAccMax]) {
-    reduce_image_partials(image_partials, nchunks, nacc, acc, [] {});
-}
 
 // sin(x) for |x| <= pi/2 (odd minimax polynomial, |err| < 1.2e-7 in fp32): the sweep's sin(latitude_field)
-// (gclm_pass.hip: row_slat) and the sixth plane of the head epilogue (gclm_update.hip: pack_fields_kernel), one function
+// (gclm_pass.hip: row_slat) and the sixth plane of the head epilogue (gclm_fields.hip: pack_fields_kernel), one function
 // for both so that a plane written by the epilogue holds the very floats a sweep would compute.  F = float or a 2-wide
 // vector of floats (pixel pairs): written with explicit fmas and multiplies only, so v_fma_f32 per float and v_pk_fma_f32
 // per pair round alike.  t = x * x.

@@ -1,5 +1,6 @@
 // gclm_internal.h -- shared declarations of the translation units of libgeocalib_hip.so
-// (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update,
+// (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update, gclm_fields.hip: the head
+//  epilogue and the upsampler either side of the path, gclm_synth.hip: synthetic fields and the read probe (measurement),
 //  gclm_api.hip: C ABI (the entry points of the solve, the stage kernels and the three render kernels) and launch
 //  sequence, gclm_comm.hip: the communicator and its entry points; the render kernels over gclm_render.h --
 //  gclm_image.hip: image undistortion, gclm_pano.hip: panorama rendering, gclm_persp.hip: perspective fields; and
@@ -199,19 +200,23 @@ hipError_t launch_shared_apply(const SolveCtx& c, int step, const float* d_group
 hipError_t launch_shared_step(const SolveCtx& c, int step, hipStream_t s);
 hipError_t launch_system_out(const SolveCtx& c, float* d_cost, float* d_grad, float* d_hess, hipStream_t s);
 hipError_t launch_pblock_from_params(const SolveCtx& c, const float* d_cam, const float* d_grav, int as_rpf, PBlock* out, hipStream_t s);
+hipError_t launch_lm_step(const float* d_G, const float* d_H, const float* d_lambda, int lambda_stride, float eps, int B,
+                          int P, float* d_delta, int* d_failed, hipStream_t s);
+hipError_t launch_gradient_hessian(const float* d_J, const float* d_r, const float* d_w, int B, int N, int R, int P,
+                                   int accumulate, float* d_G, float* d_H, hipStream_t s);
+
+// gclm_fields.hip
 hipError_t launch_upsample(const float* src, int planes, int h, int w, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_upsample_multi(const UpsampleMulti& m, int h, int w, int H, int W, hipStream_t s);
 hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const float* lat_raw, const float* lat_lc,
                               int B, int H, int W, bool vec4, float* up, float* upc, float* lat, float* latc,
                               float* slat /* or nullptr */, hipStream_t s);
+
+// gclm_synth.hip
 hipError_t launch_read_probe(const float* const* planes, int n, size_t floats, hipStream_t s);
 hipError_t launch_synth(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
                         float sigma, int group_size, int run, int run_stride, float* up, float* lat, float* upc, float* latc, float* gt_cam,
                         float* gt_grav, hipStream_t s);
-hipError_t launch_lm_step(const float* d_G, const float* d_H, const float* d_lambda, int lambda_stride, float eps, int B,
-                          int P, float* d_delta, int* d_failed, hipStream_t s);
-hipError_t launch_gradient_hessian(const float* d_J, const float* d_r, const float* d_w, int B, int N, int R, int P,
-                                   int accumulate, float* d_G, float* d_H, hipStream_t s);
 
 // gclm_image.hip, gclm_pano.hip, gclm_persp.hip
 hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,

@@ -1335,11 +1335,7 @@ __global__ __launch_bounds__(kBlock) void jacobian_kernel(const float* cam, cons
     __shared__ PBlock Ps;
     const int b = blockIdx.y;
     if (threadIdx.x == 0) {
-        const float* cm = cam + (size_t)b * GCLM_CAM_STRIDE;
-        State st{};
-        st.w = cm[0]; st.h = cm[1]; st.fx = cm[2]; st.fy = cm[3]; st.cx = cm[4]; st.cy = cm[5]; st.k1 = cm[6]; st.k2 = cm[7];
-        const V3 g = normalize3({grav[b * 3], grav[b * 3 + 1], grav[b * 3 + 2]});
-        st.gx = g.x; st.gy = g.y; st.gz = g.z;
+        const State st = state_from_params(cam + (size_t)b * GCLM_CAM_STRIDE, grav + b * 3);
         PBlock p;
         build_pblock(st, spherical != 0, log_focal != 0, p);
         Ps = p;
@@ -1369,11 +1365,7 @@ __global__ __launch_bounds__(kBlock) void residual_kernel(const float* up, const
     __shared__ PBlock Ps;
     const int b = blockIdx.y;
     if (threadIdx.x == 0) {
-        const float* cm = cam + (size_t)b * GCLM_CAM_STRIDE;
-        State st{};
-        st.w = cm[0]; st.h = cm[1]; st.fx = cm[2]; st.fy = cm[3]; st.cx = cm[4]; st.cy = cm[5]; st.k1 = cm[6]; st.k2 = cm[7];
-        const V3 g = normalize3({grav[b * 3], grav[b * 3 + 1], grav[b * 3 + 2]});
-        st.gx = g.x; st.gy = g.y; st.gz = g.z;
+        const State st = state_from_params(cam + (size_t)b * GCLM_CAM_STRIDE, grav + b * 3);
         PBlock p;
         build_pblock(st, false, false, p);
         Ps = p;

@@ -3,7 +3,7 @@
 // camera models' undistort and distort scales, the zero-padded bilinear sampler, the nontemporal store, the tile geometry
 // and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
 //
-// Nothing here is shared with the LM sweep (gclm_pass.hip) or with synth_kernel (gclm_update.hip), on purpose: the sweep
+// Nothing here is shared with the LM sweep (gclm_pass.hip) or with synth_kernel (gclm_synth.hip), on purpose: the sweep
 // keeps the reference's float32 forms so that the solve rounds like the reference, and the synthetic fields' bits define
 // the benchmark's inputs.
 #pragma once

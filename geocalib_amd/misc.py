@@ -104,7 +104,7 @@ class EuclideanManifold:
 class SphericalManifold:
     """Unit-sphere [+] through a Householder reflection with the LAST component as pivot
     (Hertzberg et al. B.2; Golub & Van Loan Alg. 5.1.1).  Same numerics as the device code
-    (csrc/gclm_update.hip: householder / tangent_sphere / grav_update)."""
+    (csrc/gclm_device.h: householder / tangent_sphere / grav_update)."""
 
     @staticmethod
     def householder_vector(x: torch.Tensor):

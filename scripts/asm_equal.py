@@ -2,8 +2,12 @@
 working tree?  (Round 6 pruned the closed A/B switches from the hot file; identical device assembly means identical bits and
 identical speed by construction -- stronger than the ISA statistics and than any measured A/B.)
 
-usage: python scripts/asm_equal.py REV [FILE=gclm_pass.hip]
-Compiles FILE of both trees with the Makefile's flags to gfx950 assembly (-S --cuda-device-only), drops comments, debug /
+usage: python scripts/asm_equal.py [-v] REV [FILE=gclm_pass.hip ...] [-- FILE ...]
+The files before `--` are taken at REV, those after it from the working tree (none: the same names), so code that moved
+between files is followed: `asm_equal.py REV gclm_update.hip -- gclm_update.hip gclm_fields.hip gclm_synth.hip`.  Several
+files are always compared symbol by symbol over the union of their symbols, and the report names every symbol that differs
+or exists on one side only (-v: with the first lines of its diff); exit status 0 when there is none.
+Compiles each file of both trees with the Makefile's flags to gfx950 assembly (-S --cuda-device-only), drops comments, debug /
 file directives and the compilation-unit id symbol (a hash of the source text), and compares the rest line by line.
 Where the two trees emit the same kernels in another order (the host's dispatcher decides the order of instantiation), the
 comparison is made symbol by symbol: every line of the file belongs to the block of one symbol (its code, its resource
@@ -47,9 +51,12 @@ def blocks(lines):
             key = m.group(1)
             assert key not in out, key
             out[key] = own
-        elif re.match(r"\s*\.set amdgpu\.", ln) and not key.startswith("<tail"):
+        elif re.match(r"\s*\.section\s+\.AMDGPU\.gpr_maximums", ln) and not key.startswith("<tail"):
+            own = []                               # the padding behind the last function belongs to the file, not to it
+            while out[key] and re.match(r"\s*\.(text|p2alignl|fill)\b", out[key][-1]):
+                own.insert(0, out[key].pop())
             key = "<tail>"
-            out[key] = []
+            out[key] = own
         elif ln.startswith("amdhsa.kernels:"):
             meta = True
         elif meta and ln.startswith("  - "):       # one kernel's metadata entry: named by its .name line further down
@@ -64,33 +71,56 @@ def blocks(lines):
     return out
 
 
+def union(tree, names):
+    """({symbol: lines} over the files, {file-level block: lines}, assembly lines, kernels, source lines) of `names` in `tree`."""
+    syms, per_file, n_asm, kernels, n_src = {}, {}, 0, 0, 0
+    for name in names:
+        lines = assembly(tree, name)
+        n_asm += len(lines)
+        kernels += sum(1 for ln in lines if ln.strip().startswith(".amdhsa_kernel"))
+        n_src += sum(1 for _ in open(os.path.join(tree, "geocalib_amd", "csrc", name)))
+        bl = blocks(lines)
+        assert sum(map(len, bl.values())) == len(lines)
+        for k, v in bl.items():
+            if k.startswith("<"):
+                per_file[f"{k} of {name}"] = v
+            else:
+                assert k not in syms, (k, name)        # one definition per symbol over the set
+                syms[k] = v
+    return syms, per_file, n_asm, kernels, n_src
+
+
 def main():
-    rev = sys.argv[1]
-    name = sys.argv[2] if len(sys.argv) > 2 else "gclm_pass.hip"
+    args = sys.argv[1:]
+    verbose = "-v" in args
+    args = [x for x in args if x != "-v"]
+    rev, rest = args[0], args[1:]
+    old_names = rest[:rest.index("--")] if "--" in rest else rest
+    old_names = old_names or ["gclm_pass.hip"]
+    new_names = rest[rest.index("--") + 1:] if "--" in rest else old_names
     with tempfile.TemporaryDirectory() as old:
         for path in ("geocalib_amd/csrc", "include"):
             tar = subprocess.run(["git", "-C", ROOT, "archive", rev, path], check=True, capture_output=True).stdout
             subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
-        a, b = assembly(old, name), assembly(ROOT, name)
-        n_old = sum(1 for _ in open(os.path.join(old, "geocalib_amd", "csrc", name)))
-    n_new = sum(1 for _ in open(os.path.join(ROOT, "geocalib_amd", "csrc", name)))
-    kernels = sum(1 for ln in a if ln.strip().startswith(".amdhsa_kernel"))
-    same, how, da, db = a == b, "", a, b
-    if not same:                                   # the same kernels in another order?  compare symbol by symbol
-        ba, bb = blocks(a), blocks(b)
-        assert sum(map(len, ba.values())) == len(a) and sum(map(len, bb.values())) == len(b)
-        only = sorted(set(ba) ^ set(bb))
-        differ = [k for k in ba if k in bb and ba[k] != bb[k]]
-        same, how = not only and not differ, f" per symbol ({len(ba)} blocks, compared by name)"
-        for k in only:
-            print("    only in", rev if k in ba else "the working tree", ":", k)
-        da, db = [ln for k in differ for ln in ba[k]], [ln for k in differ for ln in bb[k]]
-    print(f"{name}: {rev} ({n_old} source lines) vs working tree ({n_new} source lines): {len(a)} / {len(b)} assembly lines, "
-          f"{kernels} kernels, {'IDENTICAL' if same else 'DIFFERENT'}{how}")
-    if not same:
-        import difflib
-        for ln in list(difflib.unified_diff(da, db, lineterm="", n=0))[:40]:
-            print("   ", ln)
+        sa, fa, asm_a, kernels, src_a = union(old, old_names)
+    sb, fb, asm_b, _, src_b = union(ROOT, new_names)
+    if old_names == new_names:                     # the same files: their heads and tails must agree as well
+        sa.update(fa)
+        sb.update(fb)
+    only = sorted(set(sa) ^ set(sb))
+    differ = [k for k in sa if k in sb and sa[k] != sb[k]]
+    same = not only and not differ
+    print(f"{' '.join(old_names)} at {rev} ({src_a} source lines) vs {' '.join(new_names)} in the working tree ({src_b} source "
+          f"lines): {asm_a} / {asm_b} assembly lines, {kernels} kernels, {len(sa)} / {len(sb)} blocks compared by name: "
+          f"{'IDENTICAL' if same else f'{len(sa) - len(differ) - sum(k in sa for k in only)} IDENTICAL, {len(differ)} DIFFERENT'}")
+    for k in only:
+        print("    only in", rev if k in sa else "the working tree", ":", k)
+    import difflib
+    for k in differ:
+        diff = [ln for ln in difflib.unified_diff(sa[k], sb[k], lineterm="", n=0) if not ln.startswith(("---", "+++", "@@"))]
+        print(f"    DIFFERENT {k}: {len(sa[k])} -> {len(sb[k])} lines, -{sum(ln[0] == '-' for ln in diff)} +{sum(ln[0] == '+' for ln in diff)}")
+        for ln in diff[:40] if verbose else []:
+            print("       ", ln)
     sys.exit(0 if same else 1)
 
 

@@ -1,5 +1,5 @@
 // GPU box: stand-alone A/B of load / store cache policies for the CNN-head epilogue kernel (gclm_pack_fields):
-// five fp32 planes read and written IN PLACE (normalise / tanh-asin / sigmoid).  Same arithmetic as csrc/gclm_update.hip.
+// five fp32 planes read and written IN PLACE (normalise / tanh-asin / sigmoid).  Same arithmetic as csrc/gclm_fields.hip.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 scripts/probes/pack_bench.hip -o scripts/probes/_build/pack_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>

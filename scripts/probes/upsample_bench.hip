@@ -1,7 +1,7 @@
 // GPU box: stand-alone A/B of mappings for the bilinear upsampling kernel (gclm_upsample_fields).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=fast-honor-pragmas scripts/probes/upsample_bench.hip -o scripts/probes/_build/upsample_bench
 //   scripts/probes/_build/upsample_bench  > gpurun_out/r05/upsample_bench.log
-// Variants (same per-value formulas as csrc/gclm_update.hip upsample_strip; every output is compared with variant "r04"):
+// Variants (same per-value formulas as csrc/gclm_fields.hip upsample_strip; every output is compared with variant "r04"):
 //   r04        grid (strip, 4 row groups per block, plane), a wave = 64 float4 units x 8 rows   (the round-4 kernel)
 //   band*      a BLOCK owns whole rows (a band of consecutive output rows of one plane), its waves walk the
 //              (strip, row group) tasks of the band: the partial 128-byte lines between two strips of a ragged row are

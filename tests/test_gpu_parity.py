@@ -1154,7 +1154,7 @@ def test_upsample_fields_matches_torch_interpolate(dev, shape):
 
 def test_upsample_paths_agree_bitwise(dev):
     """The scalar, gather, consecutive-row and phase-rotated kernels of gclm_upsample_fields evaluate the same roundings per
-    output value (csrc/gclm_update.hip: up_lerp): a 4-byte shifted destination forces the scalar kernel, which every float4
+    output value (csrc/gclm_fields.hip: up_lerp): a 4-byte shifted destination forces the scalar kernel, which every float4
     path must reproduce bit for bit."""
     from geocalib_amd import _lib
     lib = _lib.load()
@@ -1956,14 +1956,22 @@ def test_one_launch_per_step_equals_the_two_launch_sequence(dev, model):
     workgroup of sweep k, gclm_set_fused_steps).  Same reduction order, same lm_step(): every output must be
     bit-identical to the sweep / update launch pairs -- with the early stop firing inside a launch (default conf, one
     image), fixed step counts, zero / one step, few and many partial records per image (flat / striped reduction), and
-    without confidences."""
+    without confidences.  Both paths sum an image's records through one function (gclm_device.h: sum_records) with
+    different batch sizes (16 / 32): the edges of its stripe rule and the second batch of a stripe are cases of their own."""
+    import ctypes as C
     from geocalib_amd import LMOptimizer, _lib
     lib = _lib.load()
 
-    def solve(conf, data, mode):
+    def solve(conf, data, mode, sweep_iters=0, records=None):
         opt = LMOptimizer(conf).eval()
         h = opt._handle(dev)
         _lib.check(lib.gclm_set_fused_steps(h.ptr, mode), h.ptr, "gclm_set_fused_steps")
+        _lib.check(lib.gclm_set_sweep_iters(h.ptr, sweep_iters), h.ptr, "gclm_set_sweep_iters")
+        if records is not None:                          # the cut the case was chosen for, as the library plans it
+            B, H, W = data["latitude_field"].shape[0], *data["latitude_field"].shape[-2:]
+            chunks = C.c_int(0)
+            _lib.check(lib.gclm_plan_cut(h.ptr, B, H, W, 1, None, C.byref(chunks)), h.ptr, "gclm_plan_cut")
+            assert chunks.value == records, (H, W, chunks.value, records)
         out = to_np(opt(data))
         torch.cuda.synchronize()
         return out
@@ -1986,6 +1994,15 @@ def test_one_launch_per_step_equals_the_two_launch_sequence(dev, model):
                 assert np.array_equal(two[k], one[k], equal_nan=True), (model, B, H, W, extra, strip, k)
             stops.append((two["stop_at"][0], conf.get("num_steps", 30)))
     assert any(s < n for s, n in stops) and any(s == n for s, n in stops)     # stops before and at the last step both occurred
+    # One image of W = 64 with one loop iteration per tile: 16 units per row, 4 rows per iteration, one workgroup per 16 rows
+    # (plan_geometry).  32 records: the last flat count; 33: the first striped one; 257: stripe 0 of the one-launch prologue
+    # (batches of 32) holds 33 records, i.e. needs its second batch
+    for H, records in ((512, 32), (528, 33), (4112, 257)):
+        data, _, _ = synth_device(model, 1, H, 64, dev, seed=33)
+        conf = {"camera_model": model, "num_steps": 5, "early_stop": False}
+        two, one = solve(conf, data, 0, 1, records), solve(conf, data, 1, 1, records)
+        for k in two:
+            assert np.array_equal(two[k], one[k], equal_nan=True), (model, H, records, k)
     # The first launch of the one-launch-per-step path builds the initial estimate itself (round 4: no init_kernel launch):
     # every source of that estimate -- priors, `scales`, siclib's heuristic (it reads three pixels of the fields), a
     # caller-provided camera / gravity (gclm_solve) -- must give the two-launch path's bits
