@@ -1,4 +1,5 @@
-// gclm_api.hip -- C ABI of libgeocalib_hip.so (include/gclm.h) and the launch sequence of a solve.
+// gclm_api.hip -- the handle of libgeocalib_hip.so's C ABI (include/gclm.h), the plan and the launch sequence of a solve, with
+// the entry points that take a handle (those that take none: gclm_entry.hip).
 //
 // A solve is 2*num_steps+4 asynchronous launches on the caller's stream and no host round trip (nor memset):
 //   init | { sweep(theta_i) ; update_i } x num_steps | prep_final ; sweep(theta_final, rpf) ; finalize
@@ -6,7 +7,6 @@
 //   fused(step) x num_steps | fused(final) | finalize
 // (the reference syncs twice per step: H,G -> CPU Cholesky -> device, and torch.allclose).
 #include <chrono>
-#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "gclm_args.h"
 #include "gclm_internal.h"
 
 using namespace gclm;
@@ -35,13 +36,11 @@ using namespace gclm;
 
 namespace {
 
-bool is_aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // The field planes of one call (device pointers; every one but `lat` may be null)
 struct Fields {
     const float *up = nullptr, *lat = nullptr, *upc = nullptr, *latc = nullptr;
     bool five() const { return up && upc && latc; }       // a complete field set: (B,2,H,W) + four (B,H,W) planes
-    bool aligned16() const { return is_aligned16(up) && is_aligned16(lat) && is_aligned16(upc) && is_aligned16(latc); }
+    bool aligned16() const { return is_aligned(up, 16) && is_aligned(lat, 16) && is_aligned(upc, 16) && is_aligned(latc, 16); }
 };
 
 // Everything decided ONCE per call about its sweeps (make_plan): how they walk the image, whether an LM step is one launch,
@@ -163,12 +162,6 @@ struct DeviceGuard {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A null pointer names no range.
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-    return pa && pb && pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 // Carve the core workspace for B images / nchunks partial records per image / G groups.  Growing it frees and re-allocates
 // (hipFree synchronises the device ONCE, on the first call of a larger shape than any before; every later call finds the
 // workspace in place -- include/gclm.h says so).  A failure here is the only allocation failure a solve reports (-10).
@@ -266,7 +259,7 @@ int check_shapes(gclm_handle* h, const float* lat, int B, int H, int W) {
     // (an EMPTY batch has no fields: a zero-size device tensor's pointer is NULL -- solve_empty_shard)
     if (!lat && B != 0) return fail(h, -3, "latitude_field is required (lm_optimizer.py:31 raises KeyError without it)");
     if (B < 0 || H <= 0 || W <= 0) return fail(h, -3, "bad shape B=%d H=%d W=%d", B, H, W);
-    if (B > 65535) return fail(h, -3, "batch %d exceeds 65535 images per call (grid.y): split the batch", B);
+    if (B > kMaxCallImages) return fail(h, -3, "batch %d exceeds %d images per call (grid.y): split the batch", B, kMaxCallImages);
     if ((size_t)H * W >= (size_t)1 << 30) return fail(h, -3, "image too large");
     return 0;
 }
@@ -327,7 +320,7 @@ int make_plan(gclm_handle* h, Plan& p, const Fields& f, int B, int H, int W, con
     // one-launch-per-step kernel of every model; ignored by pinhole's batch sweeps (memory-bound: the review keeps that kernel
     // as it is), the scalar path, four-plane and latitude-only sweeps, and a plane whose 16-byte alignment differs from the
     // other planes' (include/gclm.h says so).  Such a solve never wants the library's own plane.
-    if (sin_lat && float4_five && is_aligned16(sin_lat) && (p.one_launch || model != GCLM_PINHOLE)) p.given = sin_lat;
+    if (sin_lat && float4_five && is_aligned(sin_lat, 16) && (p.one_launch || model != GCLM_PINHOLE)) p.given = sin_lat;
     // Does this solve keep sin(latitude_field) in a scratch plane of its own (gclm_pass.hip: row_math, SLAT)?  Built-in choice:
     // the VALU-bound distortion models, on the five-plane float4 sweep, whenever at least one loop sweep precedes the final one.
     // Pinhole never (memory-bound: the plane's extra write costs what the saved arithmetic gains); not the one-launch-per-step
@@ -920,214 +913,6 @@ int gclm_shared_finish(gclm_handle* h, float* d_info_out, void* stream) {
     if (int rc = timed_sweep(h, h->sh.plan.next_sweep(h, c.pb_final, false, 0), s)) return rc;
     GCLM_HIP(h, launch_finalize(c, h->sh.cam_io, h->sh.grav_io, d_info_out, s));
     return 0;
-}
-
-int gclm_gradient_hessian(const float* d_J, const float* d_residual, const float* d_weight, int B, int N, int R,
-                          int P, int accumulate, float* d_G, float* d_H, void* stream) {
-    if (!d_J || !d_residual || !d_weight || !d_G || !d_H || B < 0 || N < 0 || R < 1 || R > 4 || P < 1 ||
-        P > GCLM_MAX_PARAMS)
-        return -3;
-    hipError_t e = launch_gradient_hessian(d_J, d_residual, d_weight, B, N, R, P, accumulate, d_G, d_H,
-                                           static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_optimizer_step(const float* d_G, const float* d_H, const float* d_lambda, int lambda_is_scalar, float eps,
-                        int B, int P, float* d_delta, int* d_failed, void* stream) {
-    if (!d_G || !d_H || !d_lambda || !d_delta || B < 0 || P < 1 || P > GCLM_MAX_PARAMS) return -3;
-    hipError_t e = launch_lm_step(d_G, d_H, d_lambda, lambda_is_scalar ? 0 : 1, eps, B, P, d_delta, d_failed,
-                                  static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_residual_fields(int camera_model, const float* d_up, const float* d_lat, const float* d_cam,
-                         const float* d_grav, int B, int H, int W, float* d_r_up, float* d_r_lat, void* stream) {
-    if (!d_cam || !d_grav || (!d_r_up && !d_r_lat) || B < 0 || H <= 0 || W <= 0) return -3;
-    if ((d_r_up && !d_up) || (d_r_lat && !d_lat)) return -3;
-    if (camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL || B > 65535) return -3;
-    hipError_t e = launch_residual_fields(camera_model, d_up, d_lat, d_cam, d_grav, B, H, W, d_r_up, d_r_lat,
-                                          static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_huber_costs(const float* d_residual, size_t n, int dim, float scale, const float* d_conf, float* d_cost,
-                     float* d_weight, float* d_second, void* stream) {
-    if (!d_residual || (!d_cost && !d_weight && !d_second) || dim < 0 || dim > 4 || !(scale > 0.f)) return -3;
-    hipError_t e = launch_huber_costs(d_residual, n, dim, scale, d_conf, d_cost, d_weight, d_second,
-                                      static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_jacobian_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W,
-                         int spherical, int log_focal, float* d_J_up, float* d_J_lat, void* stream) {
-    if (!d_cam || !d_grav || (!d_J_up && !d_J_lat) || B < 0 || H <= 0 || W <= 0) return -3;
-    if (camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL || B > 65535) return -3;
-    hipError_t e = launch_jacobian_fields(camera_model, d_cam, d_grav, B, H, W, spherical, log_focal, d_J_up, d_J_lat,
-                                          static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_upsample_fields(const float* d_src, int planes, int h, int w, int H, int W, float* d_dst, void* stream) {
-    if (!d_src || !d_dst || planes < 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return -3;
-    hipError_t e = launch_upsample(d_src, planes, h, w, H, W, d_dst, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_upsample_fields_multi(const float* const* d_srcs, float* const* d_dsts, const int* planes, int n_tensors, int h, int w,
-                               int H, int W, void* stream) {
-    if (!d_srcs || !d_dsts || !planes || n_tensors < 1 || n_tensors > kMaxUpsampleTensors || h <= 0 || w <= 0 || H <= 0 || W <= 0)
-        return -1;
-    UpsampleMulti m{};
-    m.n = n_tensors;
-    for (int t = 0; t < n_tensors; ++t) {
-        if (planes[t] < 0 || (planes[t] > 0 && (!d_srcs[t] || !d_dsts[t]))) return -1;
-        m.src[t] = d_srcs[t]; m.dst[t] = d_dsts[t]; m.planes[t] = planes[t];
-    }
-    return launch_upsample_multi(m, h, w, H, W, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -10;
-}
-
-int gclm_pack_fields_ex(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
-                        const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
-                        float* d_lat_conf, float* d_sin_lat, void* stream) {
-    if (!d_up_raw || !d_lat_raw || !d_up || !d_lat || B < 0 || H <= 0 || W <= 0) return -3;
-    if ((d_up_logconf && !d_up_conf) || (d_lat_logconf && !d_lat_conf)) return -3;
-    if (d_sin_lat) {
-        // the sixth plane is written from registers but must not land on a plane the pass still reads or writes
-        const size_t plane = (size_t)B * H * W * sizeof(float);
-        auto hits = [&](const void* p, size_t bytes) { return ranges_overlap(d_sin_lat, plane, p, bytes); };
-        if (hits(d_up_raw, 2 * plane) || hits(d_up_logconf, plane) || hits(d_lat_raw, plane) || hits(d_lat_logconf, plane) ||
-            hits(d_up, 2 * plane) || hits(d_up_conf, plane) || hits(d_lat, plane) || hits(d_lat_conf, plane))
-            return -3;
-    }
-    const bool vec4 = ((size_t)H * W) % 4 == 0 && is_aligned16(d_up_raw) && is_aligned16(d_up_logconf) &&
-                      is_aligned16(d_lat_raw) && is_aligned16(d_lat_logconf) && is_aligned16(d_up) &&
-                      is_aligned16(d_up_conf) && is_aligned16(d_lat) && is_aligned16(d_lat_conf) && is_aligned16(d_sin_lat);
-    hipError_t e = launch_pack_fields(d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, vec4, d_up, d_up_conf,
-                                      d_lat, d_lat_conf, d_sin_lat, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
-                     const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
-                     float* d_lat_conf, void* stream) {
-    return gclm_pack_fields_ex(d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, d_up, d_up_conf, d_lat, d_lat_conf,
-                               nullptr, stream);
-}
-
-int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin, int Win,
-                         int H, int W, float* d_dst, void* stream) {
-    // every check runs before the first HIP call
-    if (!d_cam || !d_src || !d_dst || B < 1 || C < 1 || Hin < 1 || Win < 1 || H < 2 || W < 2) return -3;
-    if ((cam_batch != 1 && cam_batch != B) || camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL || B > 65535)
-        return -3;
-    if ((int64_t)H * W > INT32_MAX) return -3;
-    const size_t in_bytes = (size_t)B * C * Hin * Win * sizeof(float), out_bytes = (size_t)B * C * H * W * sizeof(float);
-    if (ranges_overlap(d_dst, out_bytes, d_src, in_bytes)) return -3;
-    hipError_t e = launch_undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, d_dst,
-                                          static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,
-                            float* d_up, float* d_lat, void* stream) {
-    // every check runs before the first HIP call
-    if (!d_cam || !d_grav || (!d_up && !d_lat) || B < 1 || B > 65535 || H < 1 || W < 1) return -3;
-    if (camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL || (normalize_up != 0 && normalize_up != 1)) return -3;
-    if ((int64_t)H * W > INT32_MAX || (int64_t)((W + 63) / 64) * ((H + 3) / 4) * 256 > UINT32_MAX) return -3;
-    if (reinterpret_cast<uintptr_t>(d_up) % 8 || reinterpret_cast<uintptr_t>(d_lat) % 4) return -3;
-    const size_t px = (size_t)B * H * W;
-    const size_t cam_bytes = (size_t)B * 8 * sizeof(float), grav_bytes = (size_t)B * 3 * sizeof(float);
-    const size_t up_bytes = px * 2 * sizeof(float), lat_bytes = px * sizeof(float);
-    if (ranges_overlap(d_up, up_bytes, d_lat, lat_bytes) || ranges_overlap(d_up, up_bytes, d_cam, cam_bytes) ||
-        ranges_overlap(d_up, up_bytes, d_grav, grav_bytes) || ranges_overlap(d_lat, lat_bytes, d_cam, cam_bytes) ||
-        ranges_overlap(d_lat, lat_bytes, d_grav, grav_bytes))
-        return -3;
-    hipError_t e = launch_perspective_fields(camera_model, d_cam, d_grav, B, H, W, normalize_up, d_up, d_lat,
-                                             static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-size_t gclm_field_errors_workspace(int B, int H, int W, int n_thresholds) {
-    return field_errors_workspace(B, H, W, n_thresholds);
-}
-
-int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
-                      const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int n_thresholds,
-                      const float* thresholds_deg, void* d_workspace, size_t workspace_bytes, float* d_stats, float* d_up_err,
-                      float* d_lat_err, void* stream) {
-    // every check runs before the first HIP call
-    if (!d_cam || !d_grav || !d_stats || !d_workspace || (!d_up && !d_lat)) return -3;
-    if ((!d_up && (d_up_conf || d_up_err)) || (!d_lat && (d_lat_conf || d_lat_err))) return -3;
-    if (camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL) return -3;
-    const size_t ws_bytes = field_errors_workspace(B, H, W, n_thresholds);       // 0: sizes out of range
-    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
-    if (n_thresholds > 0 && !thresholds_deg) return -3;
-    for (int k = 0; k < n_thresholds; ++k)
-        if (!(fabsf(thresholds_deg[k]) <= FLT_MAX)) return -3;
-    const size_t px = (size_t)B * H * W * sizeof(float);
-    struct Range { const void* p; size_t bytes; };
-    const Range in[] = {{d_cam, (size_t)B * 8 * sizeof(float)}, {d_grav, (size_t)B * 3 * sizeof(float)}, {d_up, 2 * px}, {d_lat, px},
-                        {d_up_conf, px}, {d_lat_conf, px}};
-    const Range out[] = {{d_stats, (size_t)B * 2 * (2 + n_thresholds) * sizeof(float)}, {d_workspace, ws_bytes}, {d_up_err, px},
-                         {d_lat_err, px}};
-    for (const Range& r : in)
-        if (reinterpret_cast<uintptr_t>(r.p) % 4) return -3;
-    for (size_t i = 0; i < 4; ++i) {
-        if (reinterpret_cast<uintptr_t>(out[i].p) % 4) return -3;
-        for (const Range& r : in)
-            if (ranges_overlap(out[i].p, out[i].bytes, r.p, r.bytes)) return -3;
-        for (size_t j = i + 1; j < 4; ++j)
-            if (ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return -3;
-    }
-    hipError_t e = launch_field_errors(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, n_thresholds,
-                                       thresholds_deg, d_workspace, d_stats, d_up_err, d_lat_err, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_render_from_pano(int camera_model, const float* d_cam, int cam_batch, const float* d_rot, const float* const* srcs,
-                          const int* src_hw, int n, int C, int H, int W, float* d_dst, void* stream) {
-    // every check runs before the first HIP call
-    if (!d_cam || !d_rot || !srcs || !src_hw || !d_dst || n < 1 || n > 65535 || C < 1 || H < 2 || W < 2) return -3;
-    if ((cam_batch != 1 && cam_batch != n) || camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL) return -3;
-    if ((int64_t)H * W > INT32_MAX) return -3;
-    const size_t out_bytes = (size_t)n * C * H * W * sizeof(float);
-    if (ranges_overlap(d_dst, out_bytes, d_cam, (size_t)cam_batch * 8 * sizeof(float)) ||
-        ranges_overlap(d_dst, out_bytes, d_rot, (size_t)n * 9 * sizeof(float)))
-        return -3;
-    for (int i = 0; i < n; ++i) {
-        const int Hs = src_hw[2 * i], Ws = src_hw[2 * i + 1];
-        if (!srcs[i] || Hs < 2 || Ws < 2) return -3;
-        if (ranges_overlap(d_dst, out_bytes, srcs[i], (size_t)C * Hs * Ws * sizeof(float))) return -3;
-    }
-    hipError_t e = launch_render_from_pano(camera_model, d_cam, cam_batch, d_rot, srcs, src_hw, n, C, H, W, d_dst,
-                                           static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_read_probe(const float* const* d_planes, int n_planes, size_t floats, void* stream) {
-    if (!d_planes || n_planes < 1 || n_planes > 8 || floats % 4 != 0) return -3;
-    for (int k = 0; k < n_planes; ++k)
-        if (!d_planes[k] || !is_aligned16(d_planes[k])) return -3;
-    return launch_read_probe(d_planes, n_planes, floats, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -10;
-}
-
-int gclm_synth_fields_grouped(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
-                              float noise_sigma, int group_size, int run, int run_stride, float* d_up,
-                              float* d_lat, float* d_up_conf, float* d_lat_conf, float* d_gt_cam,
-                              float* d_gt_grav, void* stream) {
-    if (!d_up || !d_lat || B < 0 || H <= 0 || W <= 0 || group_size < 0 || run < 0) return -3;
-    if (camera_model < GCLM_PINHOLE || camera_model > GCLM_SIMPLE_DIVISIONAL) return -2;
-    hipError_t e = launch_synth(camera_model, seed, first_index, B, H, W, noise_sigma, group_size, run, run_stride,
-                                d_up, d_lat, d_up_conf, d_lat_conf, d_gt_cam, d_gt_grav,
-                                static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : -10;
-}
-
-int gclm_synth_fields(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
-                      float noise_sigma, float* d_up, float* d_lat, float* d_up_conf,
-                      float* d_lat_conf, float* d_gt_cam, float* d_gt_grav, void* stream) {
-    return gclm_synth_fields_grouped(camera_model, seed, first_index, B, H, W, noise_sigma, 1, 0, 0, d_up, d_lat,
-                                     d_up_conf, d_lat_conf, d_gt_cam, d_gt_grav, stream);
 }
 
 }  // extern "C"

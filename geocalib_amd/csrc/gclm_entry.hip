@@ -1,0 +1,208 @@
+// gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
+// upsampler, the three render kernels, the field errors, the synthetic fields and the read probe.  Each checks its arguments
+// before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
+// gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
+#include <cfloat>
+#include <cmath>
+
+#include "gclm_args.h"
+#include "gclm_render.h"
+
+using namespace gclm;
+
+namespace {
+int launched(hipError_t e) { return e == hipSuccess ? 0 : -10; }
+}  // namespace
+
+extern "C" {
+
+int gclm_gradient_hessian(const float* d_J, const float* d_residual, const float* d_weight, int B, int N, int R,
+                          int P, int accumulate, float* d_G, float* d_H, void* stream) {
+    if (!d_J || !d_residual || !d_weight || !d_G || !d_H || B < 0 || N < 0 || R < 1 || R > 4 || P < 1 ||
+        P > GCLM_MAX_PARAMS)
+        return -3;
+    return launched(launch_gradient_hessian(d_J, d_residual, d_weight, B, N, R, P, accumulate, d_G, d_H,
+                                            static_cast<hipStream_t>(stream)));
+}
+
+int gclm_optimizer_step(const float* d_G, const float* d_H, const float* d_lambda, int lambda_is_scalar, float eps,
+                        int B, int P, float* d_delta, int* d_failed, void* stream) {
+    if (!d_G || !d_H || !d_lambda || !d_delta || B < 0 || P < 1 || P > GCLM_MAX_PARAMS) return -3;
+    return launched(launch_lm_step(d_G, d_H, d_lambda, lambda_is_scalar ? 0 : 1, eps, B, P, d_delta, d_failed,
+                                   static_cast<hipStream_t>(stream)));
+}
+
+int gclm_residual_fields(int camera_model, const float* d_up, const float* d_lat, const float* d_cam,
+                         const float* d_grav, int B, int H, int W, float* d_r_up, float* d_r_lat, void* stream) {
+    if (!d_cam || !d_grav || (!d_r_up && !d_r_lat) || B < 0 || H <= 0 || W <= 0) return -3;
+    if ((d_r_up && !d_up) || (d_r_lat && !d_lat)) return -3;
+    if (!known_model(camera_model) || B > kMaxCallImages) return -3;
+    return launched(launch_residual_fields(camera_model, d_up, d_lat, d_cam, d_grav, B, H, W, d_r_up, d_r_lat,
+                                           static_cast<hipStream_t>(stream)));
+}
+
+int gclm_huber_costs(const float* d_residual, size_t n, int dim, float scale, const float* d_conf, float* d_cost,
+                     float* d_weight, float* d_second, void* stream) {
+    if (!d_residual || (!d_cost && !d_weight && !d_second) || dim < 0 || dim > 4 || !(scale > 0.f)) return -3;
+    return launched(launch_huber_costs(d_residual, n, dim, scale, d_conf, d_cost, d_weight, d_second,
+                                       static_cast<hipStream_t>(stream)));
+}
+
+int gclm_jacobian_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W,
+                         int spherical, int log_focal, float* d_J_up, float* d_J_lat, void* stream) {
+    if (!d_cam || !d_grav || (!d_J_up && !d_J_lat) || B < 0 || H <= 0 || W <= 0) return -3;
+    if (!known_model(camera_model) || B > kMaxCallImages) return -3;
+    return launched(launch_jacobian_fields(camera_model, d_cam, d_grav, B, H, W, spherical, log_focal, d_J_up, d_J_lat,
+                                           static_cast<hipStream_t>(stream)));
+}
+
+int gclm_upsample_fields(const float* d_src, int planes, int h, int w, int H, int W, float* d_dst, void* stream) {
+    if (!d_src || !d_dst || planes < 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return -3;
+    return launched(launch_upsample(d_src, planes, h, w, H, W, d_dst, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_upsample_fields_multi(const float* const* d_srcs, float* const* d_dsts, const int* planes, int n_tensors, int h, int w,
+                               int H, int W, void* stream) {
+    if (!d_srcs || !d_dsts || !planes || n_tensors < 1 || n_tensors > kMaxUpsampleTensors || h <= 0 || w <= 0 || H <= 0 || W <= 0)
+        return -1;
+    UpsampleMulti m{};
+    m.n = n_tensors;
+    for (int t = 0; t < n_tensors; ++t) {
+        if (planes[t] < 0 || (planes[t] > 0 && (!d_srcs[t] || !d_dsts[t]))) return -1;
+        m.src[t] = d_srcs[t]; m.dst[t] = d_dsts[t]; m.planes[t] = planes[t];
+    }
+    return launched(launch_upsample_multi(m, h, w, H, W, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_pack_fields_ex(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
+                        const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
+                        float* d_lat_conf, float* d_sin_lat, void* stream) {
+    if (!d_up_raw || !d_lat_raw || !d_up || !d_lat || B < 0 || H <= 0 || W <= 0) return -3;
+    if ((d_up_logconf && !d_up_conf) || (d_lat_logconf && !d_lat_conf)) return -3;
+    // The sixth plane is written from registers but must not land on a plane the pass still reads or writes.  The other four
+    // outputs are registered as if read: the sixth plane keeps off them, and they may alias the inputs (pack_fields(inplace=True)).
+    // (the first two hold two planes per image)
+    const float* const planes[] = {d_up_raw, d_up, d_up_logconf, d_lat_raw, d_lat_logconf, d_up_conf, d_lat, d_lat_conf};
+    ArgCheck a;
+    const size_t plane = floats(B, H, W);
+    a.writes(d_sin_lat, plane);
+    bool vec4 = ((size_t)H * W) % 4 == 0 && is_aligned(d_sin_lat, 16);
+    for (int k = 0; k < 8; ++k) {
+        a.reads(planes[k], mul_sat(plane, k < 2 ? 2 : 1));
+        vec4 = vec4 && is_aligned(planes[k], 16);
+    }
+    if (!a.pass()) return -3;
+    return launched(launch_pack_fields(d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, vec4, d_up, d_up_conf,
+                                       d_lat, d_lat_conf, d_sin_lat, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
+                     const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
+                     float* d_lat_conf, void* stream) {
+    return gclm_pack_fields_ex(d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, d_up, d_up_conf, d_lat, d_lat_conf,
+                               nullptr, stream);
+}
+
+int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin, int Win,
+                         int H, int W, float* d_dst, void* stream) {
+    if (!d_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1 || H < 2 || W < 2) return -3;
+    if ((cam_batch != 1 && cam_batch != B) || !known_model(camera_model) || (int64_t)H * W > INT32_MAX) return -3;
+    ArgCheck a;
+    a.writes(d_dst, floats(B, C, H, W));
+    a.reads(d_src, floats(B, C, Hin, Win));
+    if (!a.pass()) return -3;
+    return launched(launch_undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, d_dst,
+                                           static_cast<hipStream_t>(stream)));
+}
+
+int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,
+                            float* d_up, float* d_lat, void* stream) {
+    if (!d_cam || !d_grav || (!d_up && !d_lat) || B < 1 || B > kMaxCallImages || H < 1 || W < 1) return -3;
+    if (!known_model(camera_model) || (normalize_up != 0 && normalize_up != 1) || !tile_grid_fits(H, W)) return -3;
+    if (!is_aligned(d_up, 8) || !is_aligned(d_lat, 4)) return -3;      // (before any range arithmetic, as ever)
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_up, mul_sat(px, 2));
+    a.writes(d_lat, px);
+    a.reads(d_cam, floats(B, 8));
+    a.reads(d_grav, floats(B, 3));
+    if (!a.pass()) return -3;
+    return launched(launch_perspective_fields(camera_model, d_cam, d_grav, B, H, W, normalize_up, d_up, d_lat,
+                                              static_cast<hipStream_t>(stream)));
+}
+
+size_t gclm_field_errors_workspace(int B, int H, int W, int n_thresholds) {
+    return field_errors_workspace(B, H, W, n_thresholds);
+}
+
+int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                      const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int n_thresholds,
+                      const float* thresholds_deg, void* d_workspace, size_t workspace_bytes, float* d_stats, float* d_up_err,
+                      float* d_lat_err, void* stream) {
+    if (!d_cam || !d_grav || !d_stats || !d_workspace || (!d_up && !d_lat)) return -3;
+    if ((!d_up && (d_up_conf || d_up_err)) || (!d_lat && (d_lat_conf || d_lat_err)) || !known_model(camera_model)) return -3;
+    const size_t ws_bytes = field_errors_workspace(B, H, W, n_thresholds);       // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes || (n_thresholds > 0 && !thresholds_deg)) return -3;
+    for (int k = 0; k < n_thresholds; ++k)
+        if (!(fabsf(thresholds_deg[k]) <= FLT_MAX)) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_stats, floats(B, 2, 2 + n_thresholds), 4);
+    a.writes(d_workspace, ws_bytes, 4);
+    a.writes(d_up_err, px, 4);
+    a.writes(d_lat_err, px, 4);
+    a.reads(d_cam, floats(B, 8), 4);
+    a.reads(d_grav, floats(B, 3), 4);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    if (!a.pass()) return -3;
+    return launched(launch_field_errors(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, n_thresholds,
+                                        thresholds_deg, d_workspace, d_stats, d_up_err, d_lat_err, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_render_from_pano(int camera_model, const float* d_cam, int cam_batch, const float* d_rot, const float* const* srcs,
+                          const int* src_hw, int n, int C, int H, int W, float* d_dst, void* stream) {
+    if (!d_cam || !d_rot || !srcs || !src_hw || !d_dst || n < 1 || n > kMaxCallImages || C < 1 || H < 2 || W < 2) return -3;
+    if ((cam_batch != 1 && cam_batch != n) || !known_model(camera_model) || (int64_t)H * W > INT32_MAX) return -3;
+    ArgCheck a;
+    a.writes(d_dst, floats(n, C, H, W));
+    a.reads(d_cam, floats(cam_batch, 8));
+    a.reads(d_rot, floats(n, 9));
+    if (!a.pass()) return -3;
+    for (int i = 0; i < n; ++i) {             // (no table entry is read behind the first bad one)
+        const int Hs = src_hw[2 * i], Ws = src_hw[2 * i + 1];
+        if (!srcs[i] || Hs < 2 || Ws < 2) return -3;
+        a.reads(srcs[i], floats(C, Hs, Ws));
+        if (!a.pass()) return -3;
+    }
+    return launched(launch_render_from_pano(camera_model, d_cam, cam_batch, d_rot, srcs, src_hw, n, C, H, W, d_dst,
+                                            static_cast<hipStream_t>(stream)));
+}
+
+int gclm_read_probe(const float* const* d_planes, int n_planes, size_t n_floats, void* stream) {
+    if (!d_planes || n_planes < 1 || n_planes > 8 || n_floats % 4 != 0) return -3;
+    for (int k = 0; k < n_planes; ++k)
+        if (!d_planes[k] || !is_aligned(d_planes[k], 16)) return -3;
+    return launched(launch_read_probe(d_planes, n_planes, n_floats, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_synth_fields_grouped(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
+                              float noise_sigma, int group_size, int run, int run_stride, float* d_up,
+                              float* d_lat, float* d_up_conf, float* d_lat_conf, float* d_gt_cam,
+                              float* d_gt_grav, void* stream) {
+    if (!d_up || !d_lat || B < 0 || H <= 0 || W <= 0 || group_size < 0 || run < 0) return -3;
+    if (!known_model(camera_model)) return -2;
+    return launched(launch_synth(camera_model, seed, first_index, B, H, W, noise_sigma, group_size, run, run_stride,
+                                 d_up, d_lat, d_up_conf, d_lat_conf, d_gt_cam, d_gt_grav, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_synth_fields(int camera_model, uint64_t seed, int64_t first_index, int B, int H, int W,
+                      float noise_sigma, float* d_up, float* d_lat, float* d_up_conf, float* d_lat_conf,
+                      float* d_gt_cam, float* d_gt_grav, void* stream) {
+    return gclm_synth_fields_grouped(camera_model, seed, first_index, B, H, W, noise_sigma, 1, 0, 0, d_up, d_lat,
+                                     d_up_conf, d_lat_conf, d_gt_cam, d_gt_grav, stream);
+}
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 // gclm_internal.h -- shared declarations of the translation units of libgeocalib_hip.so
 // (gclm_pass.hip: per-pixel sweep, gclm_update.hip: per-image / per-group solve + update, gclm_fields.hip: the head
 //  epilogue and the upsampler either side of the path, gclm_synth.hip: synthetic fields and the read probe (measurement),
-//  gclm_api.hip: C ABI (the entry points of the solve, the stage kernels and the three render kernels) and launch
-//  sequence, gclm_comm.hip: the communicator and its entry points; the render kernels over gclm_render.h --
+//  gclm_api.hip: the handle, the plan and the launch sequence of a solve with their entry points, gclm_entry.hip: the entry
+//  points that take no handle (stage kernels, render kernels, field errors, synthetic fields) over the argument check of
+//  gclm_args.h, gclm_comm.hip: the communicator and its entry points; the render kernels over gclm_render.h --
 //  gclm_image.hip: image undistortion, gclm_pano.hip: panorama rendering, gclm_persp.hip: perspective fields; and
 //  gclm_metrics.hip: the errors of predicted fields against a calibration, over the same header).  gfx950 only.
 #pragma once
@@ -22,6 +23,7 @@ constexpr int kNAccMax = 24;       // ... and for the 5-parameter `radial` model
 constexpr int kPBlockFloats = 20;
 constexpr int kMaxP = GCLM_MAX_PARAMS;
 constexpr int kStateFloats = 16;
+constexpr int kMaxCallImages = 65535;   // most images of one call (grid.y); the Python package splits larger batches (_call.MAX_CALL)
 
 // Partial / accumulator record of one sweep over (part of) an image.
 //   [0] sum Huber cost up   [1] sum Huber cost latitude

@@ -256,8 +256,8 @@ int pixels_per_lane(int W, const float* up, const float* lat, const float* upc, 
 }  // namespace
 
 size_t field_errors_workspace(int B, int H, int W, int n_thresholds) {
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || n_thresholds < 0 || n_thresholds > kMaxThr) return 0;
-    if ((int64_t)H * W > INT32_MAX || (((int64_t)W + 63) / 64) * (((int64_t)H + kTileRows - 1) / kTileRows) * kBlock > UINT32_MAX) return 0;
+    if (B < 1 || B > kMaxCallImages || H < 1 || W < 1 || n_thresholds < 0 || n_thresholds > kMaxThr) return 0;
+    if (!tile_grid_fits(H, W)) return 0;
     // sized for one pixel per lane, the path with the most tiles
     return (size_t)B * tile_count(H, W, 1) * (kSumWords + 2 * n_thresholds) * sizeof(uint32_t);
 }

@@ -1,5 +1,6 @@
 // gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_persp.hip) and of
-// the kernel that scores fields against a calibration (gclm_metrics.hip); device code, included by those four only: the
+// the kernel that scores fields against a calibration (gclm_metrics.hip); device code, included by those four (and by
+// gclm_entry.hip, for the bound on the tile grid) only: the
 // camera models' undistort and distort scales, the zero-padded bilinear sampler, the nontemporal store, the tile geometry
 // and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
 //
@@ -19,6 +20,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTileRows = kBlock / 64;                        // rows per block: one per wave
 constexpr int tile_columns(int W, int px = 1) { return (W + 64 * px - 1) / (64 * px); }
 constexpr int tile_count(int H, int W, int px = 1) { return tile_columns(W, px) * ((H + kTileRows - 1) / kTileRows); }
+// The largest image of a call (host): its pixels are counted in an int, the threads of its widest grid (px = 1) in 32 bits.
+constexpr bool tile_grid_fits(int H, int W) {
+    return (int64_t)H * W <= INT32_MAX && (((int64_t)W + 63) / 64) * (((int64_t)H + kTileRows - 1) / kTileRows) * kBlock <= UINT32_MAX;
+}
 
 // This lane's first pixel (x, y); false where it lies outside the image.
 template <int PX = 1>

@@ -6,45 +6,25 @@ the C entry the arguments of include/gclm.h, and the kernels carry no scratch.""
 import ctypes as C
 import math
 import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
-
 from geocalib_amd import Gravity, _call, _lib, camera_models, fields, metrics
+from abi_harness import HEADER, LLVM, assert_declared_exported_and_bound
 import field_error_gate as fg
 import perspective_gate as pg
 from test_host_calls import MAX, STREAM, p, rec  # noqa: F401  (the recorder fixture, not edited)
 
-HEADER = os.path.join(ROOT, "include", "gclm.h")
-LLVM = "/opt/rocm/lib/llvm/bin"
 ARGS = ["int", "const float*", "const float*", "int", "int", "int", "const float*", "const float*", "const float*", "const float*",
         "int", "const float*", "void*", "size_t", "float*", "float*", "float*", "void*"]
 
 
-def _declared(name, ret):
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(ret + r"\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert m, f"{name} not declared in include/gclm.h"
-    return [re.sub(r"\s*\b\w+$", "", a.strip()).replace(" *", "*") for a in m.group(1).split(",")]
-
-
 def test_entry_points_are_declared_exported_and_bound():
-    assert _declared("gclm_field_errors", "int") == ARGS
-    assert _declared("gclm_field_errors_workspace", "size_t") == ["int"] * 4
-    res, args = _lib._SIGNATURES["gclm_field_errors"]
-    assert res is C.c_int and len(args) == len(ARGS)
+    args = assert_declared_exported_and_bound("gclm_field_errors", ARGS)
     for a, t in zip(args, ARGS):
-        assert a is {"int": C.c_int, "size_t": C.c_size_t}.get(t, a), (a, t)
         assert t in ("int", "size_t") or a in (C.c_void_p, C.POINTER(C.c_float)), (a, t)
-    res, args = _lib._SIGNATURES["gclm_field_errors_workspace"]
-    assert res is C.c_size_t and args == [C.c_int] * 4
-    lib = _lib.load()
-    for name in ("gclm_field_errors", "gclm_field_errors_workspace"):
-        assert name in _lib.EXPORTED_SYMBOLS and hasattr(C.CDLL(_lib.LIB_PATH), name)
-    assert lib.gclm_version() == 610 == _lib.ABI_VERSION
+    assert assert_declared_exported_and_bound("gclm_field_errors_workspace", ["int"] * 4, ret="size_t") == [C.c_int] * 4
     header = open(HEADER).read()
     changelog = header[header.index("ABI version:"):header.index("#define GCLM_VERSION")]
     assert "gclm_field_errors_workspace" in changelog and "gclm_field_errors " in changelog

@@ -5,39 +5,26 @@ kernels carry no scratch and no LDS."""
 import ctypes as C
 import math
 import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
-
 from geocalib_amd import _lib, camera_models
 from geocalib_amd.gravity import Gravity
+from abi_harness import LLVM, assert_declared_exported_and_bound
 import pano_gate as pg
 import undistort_gate as ug
 
-HEADER = os.path.join(ROOT, "include", "gclm.h")
-LLVM = "/opt/rocm/lib/llvm/bin"
 ARGS = ["int", "const float*", "int", "const float*", "const float* const*", "const int*", "int", "int", "int", "int",
         "float*", "void*"]
 
 
 def test_entry_point_is_declared_exported_and_bound():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int\s+gclm_render_from_pano\s*\(([^)]*)\)\s*;", src)
-    assert m, "gclm_render_from_pano not declared in include/gclm.h"
-    types = [re.sub(r"\s*\b\w+$", "", a.strip()).replace(" *", "*") for a in m.group(1).split(",")]
-    assert types == ARGS, types
-    res, args = _lib._SIGNATURES["gclm_render_from_pano"]
-    assert res is C.c_int and len(args) == 12
+    args = assert_declared_exported_and_bound("gclm_render_from_pano", ARGS)
+    assert len(args) == 12
     assert [args[i] for i in (0, 2, 6, 7, 8, 9)] == [C.c_int] * 6
     assert args[1] is args[3] is args[10] is args[11] is C.c_void_p
     assert args[4] is C.POINTER(C.c_void_p) and args[5] is C.POINTER(C.c_int)
-    assert "gclm_render_from_pano" in _lib.EXPORTED_SYMBOLS
-    lib = _lib.load()
-    assert hasattr(C.CDLL(_lib.LIB_PATH), "gclm_render_from_pano")
-    assert lib.gclm_version() == 610 == _lib.ABI_VERSION
 
 
 # fake, never dereferenced device addresses: every call below must be refused before the first HIP call

@@ -4,35 +4,22 @@ and the reference's own float64 outputs, its simple_divisional closed forms equa
 gate passes an honest float32 evaluation and fails its mutants, and the kernels carry no scratch and no LDS."""
 import ctypes as C
 import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
-
 from geocalib_amd import Gravity, _lib, camera_models, perspective_fields as pf
+from abi_harness import LLVM, assert_declared_exported_and_bound
 import perspective_gate as pg
 
-HEADER = os.path.join(ROOT, "include", "gclm.h")
-LLVM = "/opt/rocm/lib/llvm/bin"
 ARGS = ["int", "const float*", "const float*", "int", "int", "int", "int", "float*", "float*", "void*"]
 
 
 def test_entry_point_is_declared_exported_and_bound():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int\s+gclm_perspective_fields\s*\(([^)]*)\)\s*;", src)
-    assert m, "gclm_perspective_fields not declared in include/gclm.h"
-    types = [re.sub(r"\s*\b\w+$", "", a.strip()).replace(" *", "*") for a in m.group(1).split(",")]
-    assert types == ARGS, types
-    res, args = _lib._SIGNATURES["gclm_perspective_fields"]
-    assert res is C.c_int and len(args) == 10
+    args = assert_declared_exported_and_bound("gclm_perspective_fields", ARGS)
+    assert len(args) == 10
     assert [a for a in args if a is C.c_int] == [C.c_int] * 5 and args[0] is C.c_int
     assert args[1] is args[2] is args[7] is args[8] is args[9] is C.c_void_p
-    assert "gclm_perspective_fields" in _lib.EXPORTED_SYMBOLS
-    lib = _lib.load()
-    assert hasattr(C.CDLL(_lib.LIB_PATH), "gclm_perspective_fields")
-    assert lib.gclm_version() == 610 == _lib.ABI_VERSION
 
 
 # fake, never dereferenced device addresses: every call below must be refused before the first HIP call

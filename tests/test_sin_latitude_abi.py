@@ -4,28 +4,18 @@ rows of data["sin_latitude"] that match its rows of data["latitude_field"].  The
 replaced by recorders: no kernel runs here (tests/test_sin_latitude_handoff.py runs them on the GPU)."""
 import ctypes as C
 import inspect
-import os
 import re
 import types
 
 import pytest
 import torch
 
-from conftest import ROOT
-
 from geocalib_amd import _call, _lib, lm_optimizer, parallel
 from geocalib_amd.lm_optimizer import LMOptimizer
+from abi_harness import declared
 
-HEADER = os.path.join(ROOT, "include", "gclm.h")
 PARENTS = {"gclm_pack_fields_ex": "gclm_pack_fields", "gclm_solve_ex": "gclm_solve", "gclm_calibrate_ex": "gclm_calibrate",
            "gclm_shared_begin_ex": "gclm_shared_begin"}
-
-
-def declared_params(name):
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\((.*?)\);" % name, src, re.S)
-    assert m, f"{name} not declared in include/gclm.h"
-    return [p.strip() for p in m.group(1).split(",")]
 
 
 def test_ex_entry_points_are_declared_exported_and_bound_with_one_more_pointer():
@@ -33,7 +23,7 @@ def test_ex_entry_points_are_declared_exported_and_bound_with_one_more_pointer()
     for ex, parent in PARENTS.items():
         assert hasattr(lib, ex), f"{ex} not exported"
         assert ex in _lib.EXPORTED_SYMBOLS
-        pe, pp = declared_params(ex), declared_params(parent)
+        pe, pp = declared(ex, names=True), declared(parent, names=True)
         # the plane goes just before the stream: the parent's parameters, then the plane, then `void* stream`
         assert len(pe) == len(pp) + 1, (ex, pe)
         assert pe[:-2] == pp[:-1] and pe[-1] == pp[-1] == "void* stream", (ex, pe)

@@ -4,35 +4,22 @@ reference composition, the parity gate of tests/test_undistort_image.py passes a
 its mutants, and the kernels carry no scratch and no LDS."""
 import ctypes as C
 import os
-import re
 import shutil
 
 import pytest
 import torch
 
-from conftest import ROOT
-
 from geocalib_amd import _lib, camera_models
+from abi_harness import LLVM, assert_declared_exported_and_bound
 import undistort_gate as ug
 
-HEADER = os.path.join(ROOT, "include", "gclm.h")
-LLVM = "/opt/rocm/lib/llvm/bin"
 ARGS = ["int", "const float*", "int", "const float*", "int", "int", "int", "int", "int", "int", "float*", "void*"]
 
 
 def test_entry_point_is_declared_exported_and_bound():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int\s+gclm_undistort_image\s*\(([^)]*)\)\s*;", src)
-    assert m, "gclm_undistort_image not declared in include/gclm.h"
-    types = [re.sub(r"\s*\b\w+$", "", a.strip()).replace(" *", "*") for a in m.group(1).split(",")]
-    assert types == ARGS, types
-    res, args = _lib._SIGNATURES["gclm_undistort_image"]
-    assert res is C.c_int and len(args) == 12
+    args = assert_declared_exported_and_bound("gclm_undistort_image", ARGS)
+    assert len(args) == 12
     assert [a for a in args if a is C.c_int] == [C.c_int] * 8 and args[1] is args[3] is args[10] is args[11] is C.c_void_p
-    assert "gclm_undistort_image" in _lib.EXPORTED_SYMBOLS
-    lib = _lib.load()
-    assert hasattr(C.CDLL(_lib.LIB_PATH), "gclm_undistort_image")
-    assert lib.gclm_version() == 610 == _lib.ABI_VERSION
 
 
 # fake, never dereferenced device addresses: every call below must be refused before the first HIP call
