@@ -100,9 +100,11 @@ __device__ inline V3 grav_update(V3 g, float d0, float d1, bool spherical) {
 // fx rebuilt from fy by the old ratio.
 __device__ inline void update_focal(State& s, float delta, bool as_log) {
     const float fy = as_log ? expf(logf(s.fy) + delta) : s.fy + delta;
-    // fov2focal(deg2rad(150), h), fov2focal(deg2rad(5), h) with the float32 values of tan(75 deg), tan(2.5 deg)
+    // fov2focal(ones * deg2rad(150), h), fov2focal(ones * deg2rad(5), h) in float32 as the reference evaluates them: deg2rad
+    // of a Python number is a double, rounded to float32 by the product; tan of its half in float32.  (tan of the
+    // float32-ARITHMETIC 5 / 180 * pi is 0.043660946f, one ulp up: the bound came out one ulp low at 93 % of all heights.)
     const float min_f = s.h * 0.5f / 3.7320504f;
-    const float max_f = s.h * 0.5f / 0.043660946f;
+    const float max_f = s.h * 0.5f / 0.043660942f;
     const float fyc = fminf(fmaxf(fy, min_f), max_f);
     s.fx = fyc * s.fx / s.fy;
     s.fy = fyc;

@@ -642,8 +642,9 @@ static int lm_step(int n, const real *Hm, const real *G, real lambda, real *delt
 static void update_focal(cam_t *c, real delta, int as_log) {
     real fx = as_log ? rexp(rlog(c->fx) + delta) : c->fx + delta;
     real fy = as_log ? rexp(rlog(c->fy) + delta) : c->fy + delta;
-    real min_f = c->h / R(2.0) / rtan((R(150.0) / R(180.0) * (real)M_PI) / R(2.0));
-    real max_f = c->h / R(2.0) / rtan((R(5.0) / R(180.0) * (real)M_PI) / R(2.0));
+    /* deg2rad of a Python number is a double; the product with the float32 ones rounds it (camera.py:141-142) */
+    real min_f = c->h / R(2.0) / rtan((real)(150.0 / 180.0 * M_PI) / R(2.0));
+    real max_f = c->h / R(2.0) / rtan((real)(5.0 / 180.0 * M_PI) / R(2.0));
     fx = fx < min_f ? min_f : (fx > max_f ? max_f : fx);
     fy = fy < min_f ? min_f : (fy > max_f ? max_f : fy);
     (void)fx;

@@ -284,7 +284,7 @@ def restate_step(model, H, G, cam, grav, lam, groups, mutant=None):
     h, fx, fy = cam[:, 1], cam[:, 2], cam[:, 3]
     with np.errstate(all="ignore"):
         nfy = np.exp(np.log(fy) + dI[:, 0])
-        min_f, max_f = h * F32(0.5) / F32(3.7320504), h * F32(0.5) / F32(0.043660946)
+        min_f, max_f = h * F32(0.5) / F32(3.7320504), h * F32(0.5) / F32(0.043660942)
         fyc = np.minimum(np.maximum(nfy, min_f), max_f)
         nfx = fyc * fx / fy
     cam[:, 2] = np.where(applied, nfx, fx)

@@ -534,18 +534,21 @@ def test_full_size_batch_properties(dev, oracle, model):
     compare_result({k: v[idx] for k, v in a.items()}, ref, TOL, f"B1024/{model}")
 
 
-def run_virtual_ranks(dev, conf, data, selections, gofs, G, H, W):
+def run_virtual_ranks(dev, conf, data, selections, gofs, G, H, W, init=None):
     """The split protocol of BASELINE configs[4] on ONE device: rank r = its own LMOptimizer / gclm_handle holding the
     frames `selections[r]` (indices into `data`, sorted by group) with local group ids `gofs[r]`.  Per LM step every
     rank reduces its frames to Schur partials (gclm_shared_reduce), the buffers are summed (what the RCCL all-reduce
-    does) and every rank applies (gclm_shared_apply).  Returns per rank (cam, grav, info) as numpy."""
-    from geocalib_amd import LMOptimizer, _lib, get_trivial_estimation
+    does) and every rank applies (gclm_shared_apply).  Returns per rank (cam, grav, info) as numpy.  `init` = (cam (B, 8),
+    grav (B, 3)) device tensors over all frames of `data`: the session starts there instead of the trivial estimate."""
+    from geocalib_amd import Gravity, LMOptimizer, _lib, get_trivial_estimation
     lib = _lib.load()
     ranks = []
     for sel, gof in zip(selections, gofs):
         local = {k: v[sel].contiguous() for k, v in data.items()}
         opt = LMOptimizer(conf).eval()
         cam0, grav0 = get_trivial_estimation(local, opt.camera_model)
+        if init is not None:
+            cam0, grav0 = opt.camera_model(init[0][sel].contiguous()), Gravity(init[1][sel].contiguous())
         opt.setup_optimization_and_priors(local, shared_intrinsics=True)
         up, lat, upc, latc, (B, _, _) = opt._fields(local)
         h = opt._handle(dev)
