@@ -287,15 +287,18 @@ __device__ inline float total_cost(const float* acc, float invN, bool has_up, fl
     return has_up ? cu + cl : cl;
 }
 
+// update_lambda (lm_optimizer.py:95-106) of one image whose new cost is `total`
+__device__ inline void lambda_rule(float total, State& s) {
+    const float nl = s.lambda * (total > s.prev_cost ? 10.f : 0.1f);
+    s.lambda = fminf(fmaxf(nl, 1e-6f), 1e2f);
+}
+
 // lambda rule + "allclose" test of one image (lm_optimizer.py:95-106, :90-92, :612-627): returns whether the cost
 // still MOVED at this step (always false at step 0, where nothing is compared); the caller counts it.
 __device__ inline bool cost_rules(const gclm_config& cfg, int step, float total, State& s, bool update_lambda) {
     bool moved = false;
     if (step > 0) {
-        if (update_lambda) {
-            const float nl = s.lambda * (total > s.prev_cost ? 10.f : 0.1f);
-            s.lambda = fminf(fmaxf(nl, 1e-6f), 1e2f);
-        }
+        if (update_lambda) lambda_rule(total, s);
         // torch.allclose evaluates |new - prev| <= atol + |rtol * prev| in the tensors' dtype (float32: the scalar tolerances
         // do not promote; ATen isclose) -- so does this (rounds 1-3 used double: same decision unless the difference sits
         // within 1e-15 of the threshold, but it was a deviation nobody had written down)

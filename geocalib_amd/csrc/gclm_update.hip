@@ -153,8 +153,15 @@ __global__ __launch_bounds__(kGroups * kSlots) void finalize_kernel(SolveCtx c, 
     float cu, cl;
     const float total = total_cost(acc, invN, true, cu, cl);
     // the final sweep is also the "new cost" evaluation of the last executed step
+    const bool update_lambda = !cfg.fix_lambda && !cfg.shared_intrinsics;
     if (!c.ctrl->stopped)
-        cost_bookkeeping(cfg, c.ctrl, cfg.num_steps, total, s, !cfg.fix_lambda && !cfg.shared_intrinsics);
+        cost_bookkeeping(cfg, c.ctrl, cfg.num_steps, total, s, update_lambda);
+    else if (update_lambda)
+        // The stop fired on the comparison of this state's cost with s.prev_cost.  The reference updates lambda BEFORE it
+        // tests (:613, :619); that update went into the discarded tentative state, so it is made again here, without the
+        // counter: the solve reports the lambda of its fixed-length twin {num_steps: stop_at, early_stop: False}.  (Both
+        // launch paths end in this kernel.)
+        lambda_rule(total, s);
     float* o = info + (size_t)b * GCLM_INFO_STRIDE;
     for (int i = 0; i < GCLM_INFO_STRIDE; ++i) o[i] = 0.f;      // every slot is written here: no memset by the caller
     o[GCLM_INFO_STOP_AT] = (float)first_quiet_step(c.ctrl, cfg.num_steps);      // (nothing of this launch is needed for it)

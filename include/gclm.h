@@ -81,7 +81,7 @@ enum gclm_info_slot {
     GCLM_INFO_FOCAL_UNC = 10,
     GCLM_INFO_VFOV_UNC = 11,
     GCLM_INFO_NPARAMS = 12,
-    GCLM_INFO_LAMBDA = 13,
+    GCLM_INFO_LAMBDA = 13,         /* after every update_lambda of the solve: one per comparison made, the one that fired an early stop included */
     GCLM_INFO_STEP_FAILURES = 14,  /* number of LM steps rejected: Cholesky failed or the step was NaN / inf (zero step) */
     GCLM_INFO_COV = 16             /* covariance, P x P row-major, up to 25 floats */
 };
