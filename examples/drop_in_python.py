@@ -16,7 +16,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from geocalib_amd import GeoCalib, LMOptimizer  # noqa: E402
+from geocalib_amd import GeoCalib, Gravity, LMOptimizer, camera_models, metrics  # noqa: E402
 from geocalib_amd.synth import synth_fields  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -51,3 +51,13 @@ print("with a focal prior: focal", round(res["camera"].f[0, 1].item(), 1))
 res = model.calibrate(img, camera_model="radial")
 rect = res["camera"].undistort_image(img[None])                   # (1, 3, H, W): one gclm_undistort_image launch
 print("undistort_image(): k1, k2", [round(v, 4) for v in res["camera"].dist[0].tolist()], " output", tuple(rect.shape))
+
+# (4) solve one batch from three starts -- the trivial and the heuristic initialisation, and the focal length held at a guess
+#     (a prior) -- and keep, per image, the calibration that explains the fields best: one gclm_hypothesis_scores pass
+starts = [LMOptimizer({"camera_model": "simple_radial", "init_conf": {"name": name}}).eval()(fields) for name in ("trivial", "heuristic")]
+starts.append(opt({**fields, "prior_focal": torch.full((4,), 400.0, device=dev)}))
+cams = camera_models["simple_radial"](torch.stack([s["camera"]._data for s in starts], 1))          # (B, N = 3)
+gravs = Gravity(torch.stack([s["gravity"]._data for s in starts], 1))
+ranked = metrics.rank_calibrations(fields, cams, gravs)              # inliers within 1 degree, weighted by the confidences
+print("rank_calibrations(): best start per image", ranked["best"].tolist(), " scores", [[round(v) for v in r] for r in ranked["scores"].tolist()])
+print("                   focal of the winners", [round(v, 1) for v in ranked["camera"].f[:, 1].tolist()])

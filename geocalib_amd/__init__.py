@@ -5,7 +5,8 @@ Public surface (mirrors the reference's geocalib package for this path):
     Camera models / camera_models       geocalib/camera.py
     Gravity                             geocalib/gravity.py
     GeoCalib (extractor with calibrate) geocalib/extractor.py:15  (CNN supplied by the caller)
-    metrics                             siclib/models/utils/metrics.py  (+ perspective_field_metrics: fields against a calibration)
+    metrics                             siclib/models/utils/metrics.py  (+ perspective_field_metrics: fields against a calibration,
+                                        rank_calibrations: N candidate calibrations per image against its fields)
 """
 from .camera import BaseCamera, Pinhole, Radial, SimpleDivisional, SimpleRadial, camera_models  # noqa: F401
 from .gravity import Gravity  # noqa: F401

@@ -17,6 +17,7 @@ SHARED_PARTIAL_STRIDE = 32
 COMM_ID_BYTES = 128
 MAX_PARAMS = 5
 MAX_RECALL_THRESHOLDS = 8
+HYPOTHESIS_CHUNK = 16         # GCLM_HYPOTHESIS_CHUNK: hypotheses scored per read of an image's planes (gclm_hypothesis_scores)
 ABI_VERSION = 610          # GCLM_VERSION of include/gclm.h this binding was written against
 INFO = {"stop_at": 0, "initial_up_cost": 1, "initial_latitude_cost": 2, "initial_cost": 3,
         "final_up_cost": 4, "final_latitude_cost": 5, "final_cost": 6, "roll_uncertainty": 7,
@@ -92,6 +93,9 @@ _SIGNATURES = {
     "gclm_field_errors_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gclm_field_errors": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float), _P,
                                     C.c_size_t, _P, _P, _P, _P]),
+    "gclm_hypothesis_scores_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gclm_hypothesis_scores": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, _P, C.c_size_t, _P, _P, _P]),
     "gclm_pack_fields": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "gclm_pack_fields_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gclm_synth_fields": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,

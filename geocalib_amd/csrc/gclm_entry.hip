@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the three render kernels, the field errors, the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the three render kernels, the field errors, the hypothesis scores, the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -160,6 +160,36 @@ int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav,
     if (!a.pass()) return -3;
     return launched(launch_field_errors(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, n_thresholds,
                                         thresholds_deg, d_workspace, d_stats, d_up_err, d_lat_err, static_cast<hipStream_t>(stream)));
+}
+
+size_t gclm_hypothesis_scores_workspace(int B, int N, int H, int W) { return hypothesis_scores_workspace(B, N, H, W); }
+
+int gclm_hypothesis_scores(int camera_model, const float* d_cam, const float* d_grav, int B, int N, int H, int W,
+                           const float* d_up, const float* d_lat, const float* d_up_conf, const float* d_lat_conf,
+                           const float* d_mask, float up_threshold_deg, float lat_threshold_deg, float up_weight, float lat_weight,
+                           void* d_workspace, size_t workspace_bytes, float* d_scores, int* d_best, void* stream) {
+    if (!d_cam || !d_grav || !d_scores || !d_workspace || (!d_up && !d_lat)) return -3;
+    if ((!d_up && d_up_conf) || (!d_lat && d_lat_conf) || !known_model(camera_model)) return -3;
+    const size_t ws_bytes = hypothesis_scores_workspace(B, N, H, W);             // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    for (const float v : {up_threshold_deg, lat_threshold_deg, up_weight, lat_weight})
+        if (!(fabsf(v) <= FLT_MAX)) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_scores, floats(B, N, 3), 4);
+    a.writes(d_best, mul_sat((size_t)B, sizeof(int)), 4);
+    a.writes(d_workspace, ws_bytes, 4);
+    a.reads(d_cam, floats(B, N, 8), 4);
+    a.reads(d_grav, floats(B, N, 3), 4);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    a.reads(d_mask, px, 4);
+    if (!a.pass()) return -3;
+    return launched(launch_hypothesis_scores(camera_model, d_cam, d_grav, B, N, H, W, d_up, d_lat, d_up_conf, d_lat_conf, d_mask,
+                                             up_threshold_deg, lat_threshold_deg, up_weight, lat_weight, d_workspace, d_scores,
+                                             d_best, static_cast<hipStream_t>(stream)));
 }
 
 int gclm_render_from_pano(int camera_model, const float* d_cam, int cam_batch, const float* d_rot, const float* const* srcs,

@@ -5,7 +5,8 @@
 //  points that take no handle (stage kernels, render kernels, field errors, synthetic fields) over the argument check of
 //  gclm_args.h, gclm_comm.hip: the communicator and its entry points; the render kernels over gclm_render.h --
 //  gclm_image.hip: image undistortion, gclm_pano.hip: panorama rendering, gclm_persp.hip: perspective fields; and
-//  gclm_metrics.hip: the errors of predicted fields against a calibration, over the same header).  gfx950 only.
+//  gclm_metrics.hip: the errors of predicted fields against a calibration, gclm_hypotheses.hip: the scores of N candidate
+//  calibrations per image against its fields, both over the same header).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -235,5 +236,12 @@ hipError_t launch_field_errors(int camera_model, const float* cam, const float* 
                                const float* lat, const float* upc, const float* latc, int n_thresholds,
                                const float* thresholds /* host */, void* workspace, float* stats, float* up_err /* or nullptr */,
                                float* lat_err /* or nullptr */, hipStream_t s);
+
+// gclm_hypotheses.hip
+size_t hypothesis_scores_workspace(int B, int N, int H, int W);           // bytes of one call's partial records; 0: sizes out of range
+hipError_t launch_hypothesis_scores(int camera_model, const float* cam, const float* grav, int B, int N, int H, int W,
+                                    const float* up, const float* lat, const float* upc, const float* latc, const float* mask,
+                                    float up_threshold, float lat_threshold, float up_weight, float lat_weight, void* workspace,
+                                    float* scores, int* best /* or nullptr */, hipStream_t s);
 
 }  // namespace gclm

@@ -38,8 +38,6 @@ namespace {
 constexpr int kMaxThr = GCLM_MAX_RECALL_THRESHOLDS;
 constexpr int kSumWords = 6;                 // float sums per record; 2 n_thresholds counts follow
 constexpr int kChains = 8;                   // summation chains per image of the second launch
-constexpr float kDegrees = 57.29577951308232f;
-constexpr float kCosEps = 1e-8f;             // F.cosine_similarity's eps
 
 struct FieldErrArgs {
     const float *cam, *grav, *up, *lat, *upc, *latc;
@@ -50,19 +48,6 @@ struct FieldErrArgs {
 };
 
 template <int PX>
-__device__ __forceinline__ void load_px(const float* __restrict__ p, float (&v)[PX]) {
-    if constexpr (PX == 1) {
-        v[0] = *p;
-    } else if constexpr (PX == 2) {
-        const f32x2 t = *reinterpret_cast<const f32x2*>(p);
-        v[0] = t.x, v[1] = t.y;
-    } else {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    }
-}
-
-template <int PX>
 __device__ __forceinline__ void store_px(const float (&v)[PX], float* p) {
     if constexpr (PX == 1) {
         store_nt(v[0], p);
@@ -71,32 +56,6 @@ __device__ __forceinline__ void store_px(const float (&v)[PX], float* p) {
     } else {
         store_nt(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
     }
-}
-
-// Sum over the 64 lanes of a wave, the same bits in every lane (a butterfly: lane i adds lane i ^ o, o = 32 .. 1).
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The masked up error in degrees (file header).
-__device__ __forceinline__ float up_error_deg(float px, float py, f32x2 t) {
-    const float pn2 = px * px + py * py, tn2 = t.x * t.x + t.y * t.y;
-    float dot = px * t.x + py * t.y, crs = px * t.y - py * t.x, sn;
-    if (pn2 >= kCosEps * kCosEps && tn2 >= kCosEps * kCosEps) {
-        sn = fabsf(crs);
-    } else {                                  // a norm below eps (or NaN): the cosine is taken of vectors shorter than 1
-        float pn = sqrtf(pn2), tn = sqrtf(tn2);
-        pn = pn < kCosEps ? kCosEps : pn;      // clamp_min; a NaN norm stays NaN
-        tn = tn < kCosEps ? kCosEps : tn;
-        const float ip = 1.f / pn, it = 1.f / tn;
-        dot *= ip * it, crs *= ip * it;
-        const float n = (pn2 * ip * ip) * (tn2 * it * it), gap = 1.f - n;
-        sn = sqrtf((gap > 0.f ? gap : 0.f) + crs * crs);
-    }
-    const float e = atan2f(sn, dot) * kDegrees;
-    return e * (px + py != 0.f ? 1.f : 0.f);  // NaN * 0 = NaN, as torch
 }
 
 template <int MODEL, int PX>

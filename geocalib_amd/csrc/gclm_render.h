@@ -1,6 +1,6 @@
 // gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_persp.hip) and of
-// the kernel that scores fields against a calibration (gclm_metrics.hip); device code, included by those four (and by
-// gclm_entry.hip, for the bound on the tile grid) only: the
+// the kernels that score fields against one calibration (gclm_metrics.hip) or against many (gclm_hypotheses.hip); device
+// code, included by those five (and by gclm_entry.hip, for the bound on the tile grid) only: the
 // camera models' undistort and distort scales, the zero-padded bilinear sampler, the nontemporal store, the tile geometry
 // and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
 //
@@ -160,6 +160,51 @@ __device__ __forceinline__ float persp_lat(const PerspRow& r, float u, float r2)
     float sl = (X * r.a + Y * r.b + r.c) / sqrtf(X * X + Y * Y + 1.f);
     sl = sl < -kLatHi ? -kLatHi : (sl > kLatHi ? kLatHi : sl);    // a NaN stays NaN
     return asinf(sl);
+}
+
+// What the kernels that score predicted fields share (gclm_metrics.hip: one calibration per image, gclm_hypotheses.hip: N
+// per image), so that both compile the same per-pixel functions: the vector load of a lane's pixels, the wave sum and the
+// masked up error (its formula is in gclm_metrics.hip's header).
+constexpr float kDegrees = 57.29577951308232f;
+constexpr float kCosEps = 1e-8f;             // F.cosine_similarity's eps
+
+template <int PX>
+__device__ __forceinline__ void load_px(const float* __restrict__ p, float (&v)[PX]) {
+    if constexpr (PX == 1) {
+        v[0] = *p;
+    } else if constexpr (PX == 2) {
+        const f32x2 t = *reinterpret_cast<const f32x2*>(p);
+        v[0] = t.x, v[1] = t.y;
+    } else {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    }
+}
+
+// Sum over the 64 lanes of a wave, the same bits in every lane (a butterfly: lane i adds lane i ^ o, o = 32 .. 1).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The masked up error in degrees (file header).
+__device__ __forceinline__ float up_error_deg(float px, float py, f32x2 t) {
+    const float pn2 = px * px + py * py, tn2 = t.x * t.x + t.y * t.y;
+    float dot = px * t.x + py * t.y, crs = px * t.y - py * t.x, sn;
+    if (pn2 >= kCosEps * kCosEps && tn2 >= kCosEps * kCosEps) {
+        sn = fabsf(crs);
+    } else {                                  // a norm below eps (or NaN): the cosine is taken of vectors shorter than 1
+        float pn = sqrtf(pn2), tn = sqrtf(tn2);
+        pn = pn < kCosEps ? kCosEps : pn;      // clamp_min; a NaN norm stays NaN
+        tn = tn < kCosEps ? kCosEps : tn;
+        const float ip = 1.f / pn, it = 1.f / tn;
+        dot *= ip * it, crs *= ip * it;
+        const float n = (pn2 * ip * ip) * (tn2 * it * it), gap = 1.f - n;
+        sn = sqrtf((gap > 0.f ? gap : 0.f) + crs * crs);
+    }
+    const float e = atan2f(sn, dot) * kDegrees;
+    return e * (px + py != 0.f ? 1.f : 0.f);  // NaN * 0 = NaN, as torch
 }
 
 }  // namespace gclm

@@ -242,3 +242,50 @@ def field_errors(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: O
                    c_thr, ws.data_ptr(), ws_bytes, stats[b0].data_ptr(), at(up_err, b0), at(lat_err, b0), _call.raw_stream(dev),
                    device=dev)
     return stats, up_err, lat_err
+
+
+HYPOTHESIS_CHUNK = _lib.HYPOTHESIS_CHUNK      # K: hypotheses scored per read of an image's planes (GCLM_HYPOTHESIS_CHUNK)
+
+
+def hypothesis_scores(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: Optional[torch.Tensor] = None,
+                      lat: Optional[torch.Tensor] = None, up_conf: Optional[torch.Tensor] = None,
+                      lat_conf: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, up_threshold: float = 1.0,
+                      lat_threshold: float = 1.0, up_weight: float = 1.0, lat_weight: float = 1.0):
+    """gclm_hypothesis_scores: N candidate calibrations per image, cameras `cam` (B, N, 8) and gravities `grav` (B, N, 3),
+    scored against the image's predicted fields `up` (B, 2, H, W) / `lat` (B, 1, H, W) (one may be None), their confidences
+    and an optional `mask` (B, H, W), float32 on one HIP device, in one pass per 65 535 images on torch's current stream.
+    Returns (scores, best): scores (B, N, 3) = [up, lat, total] -- the confidence-weighted sums of the pixels whose error
+    lies strictly below the field's threshold (degrees), and their weighted sum -- and best (B,) int32, the first index of
+    each image's largest total.  metrics.rank_calibrations is the public entry; not differentiable."""
+    if up is None and lat is None:
+        raise ValueError("at least one of the up and latitude fields is needed")
+    if (up is None and up_conf is not None) or (lat is None and lat_conf is not None):
+        raise ValueError("a confidence needs its field")
+    cam, grav = _call.dev_f32(cam, "cam"), _call.dev_f32(grav, "grav")
+    if cam.dim() != 3 or grav.dim() != 3 or cam.shape[2] != 8 or grav.shape[2] != 3 or cam.shape[:2] != grav.shape[:2] \
+            or grav.device != cam.device:
+        raise ValueError(f"cameras {tuple(cam.shape)} and gravities {tuple(grav.shape)} must be (B, N, 8) and (B, N, 3) on one device")
+    dev, (B, N) = cam.device, cam.shape[:2]
+    planes = {"up": up, "lat": lat, "up_conf": up_conf, "lat_conf": lat_conf, "mask": mask}
+    planes = {k: None if t is None else _call.dev_f32(t, k) for k, t in planes.items()}
+    H, W = (planes["up"] if lat is None else planes["lat"]).shape[-2:]
+    for k, t in planes.items():
+        want = B * H * W * (2 if k == "up" else 1)
+        if t is not None and (t.numel() != want or t.shape[-2:] != (H, W) or t.device != dev):
+            raise ValueError(f"`{k}` {tuple(t.shape)} on {t.device} does not fit {B} images of {H} x {W} on {dev}")
+    scores = cam.new_empty((B, N, 3))
+    best = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B * N == 0 or H * W == 0:
+        return scores.zero_(), best.zero_()
+    if N > _call.MAX_CALL:
+        raise ValueError(f"at most {_call.MAX_CALL} hypotheses per image and call (got {N})")
+    lib = _lib.load()
+    ws_bytes = int(lib.gclm_hypothesis_scores_workspace(min(B, _call.MAX_CALL), N, H, W))
+    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=dev)
+    at = lambda t, b0: None if t is None else t[b0].data_ptr()  # noqa: E731
+    for b0, n in _call.slices(B):
+        _call.call("gclm_hypothesis_scores", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, N, H, W,
+                   at(planes["up"], b0), at(planes["lat"], b0), at(planes["up_conf"], b0), at(planes["lat_conf"], b0),
+                   at(planes["mask"], b0), float(up_threshold), float(lat_threshold), float(up_weight), float(lat_weight),
+                   ws.data_ptr(), ws_bytes, scores[b0].data_ptr(), best[b0].data_ptr(), _call.raw_stream(dev), device=dev)
+    return scores, best

@@ -10,8 +10,12 @@ evaluated per pixel in registers and never written); anything else (CPU, float64
 composition on get_perspective_field, which stays the differentiable path.  The one deliberate difference: the HIP path takes
 the up angle as atan2(|p x t|, p . t), which resolves small angles; the torch path in float32 takes acos of a cosine, whose
 smallest non-zero value is 0.02 degrees, so it quantises every up error below about that.
+
+`rank_calibrations` answers which of N candidate calibrations per image fits the fields best: the confidence-weighted
+inlier sums the reference's RANSAC baseline ranks its hypotheses with (siclib/models/optimization/ransac.py:
+check_up_inliers, check_latitude_inliers, get_best_index), on the same two paths (gclm_hypothesis_scores on the device).
 """
-from typing import Dict, Sequence
+from typing import Dict, Optional, Sequence
 
 import torch
 from torch.nn import functional as F
@@ -143,3 +147,87 @@ def perspective_field_metrics(pred: Dict[str, torch.Tensor], camera: BaseCamera,
         if return_errors:
             out[err_key] = up_err if i == 0 else lat_err
     return out
+
+
+_RANK_CHUNK_PIXELS = 1 << 22       # pixels x hypotheses x images of one chunk of the torch composition (a dozen such planes live)
+
+
+def _rank_torch(pred, cameras, cam, grav, thresholds, mask):
+    """The torch composition: up / latitude inlier sums (B, N) of the hypotheses `cam` (B, N, 8), `grav` (B, N, 3), the fields
+    of get_perspective_field scored by up_error / latitude_error, in chunks of hypotheses."""
+    B, N = cam.shape[:2]
+    out = []
+    for name, field, conf, _, _ in _FIELDS:
+        if field not in pred:
+            out.append(cam.new_zeros((B, N)))
+            continue
+        p = pred[field]
+        H, W = p.shape[-2:]
+        weight = pred[conf].reshape(B, H, W) if conf in pred else p.new_ones((B, H, W))
+        if mask is not None:
+            weight = weight * mask.reshape(B, H, W)
+        step, parts = max(1, _RANK_CHUNK_PIXELS // (B * H * W)), []
+        for n0 in range(0, N, step):
+            k = min(step, N - n0)
+            camera = type(cameras)(cam[:, n0:n0 + k].reshape(B * k, 8))
+            gravity = Gravity(grav[:, n0:n0 + k].reshape(B * k, 3))
+            gravity._data = grav[:, n0:n0 + k].reshape(B * k, 3)               # as stored
+            up_t, lat_t = get_perspective_field(camera, gravity, use_up=name == "up", use_latitude=name != "up")
+            rep = p[:, None].expand(B, k, *p.shape[1:]).reshape(B * k, *p.shape[1:])
+            if name == "up":
+                error = up_error(rep, up_t.to(rep.dtype)) * (rep.sum(axis=1) != 0)
+            else:
+                error = latitude_error(rep, lat_t.to(rep.dtype))
+            hit = (error < thresholds[name]).to(weight.dtype).reshape(B, k, H, W)
+            parts.append((hit * weight[:, None]).sum(axis=(2, 3)))
+        out.append(torch.cat(parts, 1))
+    return out
+
+
+def rank_calibrations(pred: Dict[str, torch.Tensor], cameras: BaseCamera, gravities: Gravity, up_threshold: float = 1.0,
+                      latitude_threshold: float = 1.0, up_weight: float = 1.0, latitude_weight: float = 1.0,
+                      mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Which of N candidate calibrations per image fits the fields in `pred` best.
+
+    `pred` is the dict perspective_field_metrics takes (B images).  `cameras` / `gravities` hold N hypotheses per image: of
+    batch shape (B, N), or flat (B N) in the reference's order (hypothesis n of image b at b N + n), N = len // B.  A
+    hypothesis' score is the reference's RANSAC score (ransac.py): per field the sum of confidence x mask over the pixels
+    whose error -- up_error times the decoders' mask, latitude_error, against the hypothesis' perspective field -- lies
+    strictly below the field's threshold in degrees, and
+        scores = up_weight up_scores + latitude_weight latitude_scores.
+    A missing confidence counts as 1, `mask` (B, H, W) multiplies both fields' contributions (the reference's inliers), a
+    missing field scores 0.  The defaults are RPFSolver.default_conf's.  Returns
+        scores, up_scores, latitude_scores (B, N);  best (B,) int64: the first index of the largest score per image;
+        camera, gravity: the winning hypotheses (batch B), gravity as stored.
+    A hypothesis with a NaN parameter scores 0; a NaN confidence makes that field's scores of that image NaN, and NaN counts
+    as the maximum (torch.argmax).
+
+    float32 HIP tensors without grad take one HIP pass (each plane read once per fields.HYPOTHESIS_CHUNK hypotheses);
+    anything else the torch composition on get_perspective_field, in chunks of hypotheses.  Not differentiable in the
+    hypotheses either way: a hit is a comparison."""
+    if "up_field" not in pred and "latitude_field" not in pred:
+        raise ValueError("`pred` holds neither up_field nor latitude_field")
+    B = (pred["up_field"] if "up_field" in pred else pred["latitude_field"]).shape[0]
+    cam, grav = cameras._data, gravities._data
+    if B < 1 or cam.shape[:-1] != grav.shape[:-1] or cam.dim() not in (2, 3) or cam.shape[:-1].numel() % B or \
+            (cam.dim() == 3 and cam.shape[0] != B):
+        raise ValueError(f"cameras {tuple(cam.shape[:-1])} and gravities {tuple(grav.shape[:-1])} must both be (B, N) or (B N,) "
+                         f"hypotheses of {B} images")
+    N = cam.shape[:-1].numel() // B
+    cam, grav = cam.reshape(B, N, 8), grav.reshape(B, N, 3)
+    given = [pred[k] for _, f, c, _, _ in _FIELDS for k in (f, c) if k in pred] + ([] if mask is None else [mask])
+    if _on_hip(given + [cam, grav]) and 1 <= N <= 65535:
+        scores, best = fields.hypothesis_scores(
+            cameras.name(), cam, grav, pred.get("up_field"), pred.get("latitude_field"), pred.get("up_confidence"),
+            pred.get("latitude_confidence"), mask, up_threshold, latitude_threshold, up_weight, latitude_weight)
+        up_s, lat_s, total, best = scores[..., 0], scores[..., 1], scores[..., 2], best.long()
+    else:
+        with torch.no_grad():
+            up_s, lat_s = _rank_torch(pred, cameras, cam, grav, {"up": up_threshold, "latitude": latitude_threshold}, mask)
+            total = up_weight * up_s + latitude_weight * lat_s
+            best = torch.argmax(total, dim=1)
+    rows = torch.arange(B, device=cam.device)
+    gravity = Gravity(grav[rows, best])
+    gravity._data = grav[rows, best]              # as stored: the constructor renormalises
+    return {"scores": total, "up_scores": up_s, "latitude_scores": lat_s, "best": best, "camera": type(cameras)(cam[rows, best]),
+            "gravity": gravity}

@@ -47,7 +47,8 @@ extern "C" {
  * additive within 610: gclm_pack_fields_ex, gclm_solve_ex, gclm_calibrate_ex and gclm_shared_begin_ex added -- the head
  * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged; gclm_undistort_image,
  * gclm_render_from_pano and gclm_perspective_fields added, also within 610; gclm_field_errors and
- * gclm_field_errors_workspace added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
+ * gclm_field_errors_workspace added, also within 610; gclm_hypothesis_scores and gclm_hypothesis_scores_workspace added, also
+ * within 610).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -62,6 +63,9 @@ enum gclm_camera_model {
 #define GCLM_MAX_PARAMS 5     /* delta_g1, delta_g2, focal, k1, k2 */
 #define GCLM_MAX_STEPS 256
 #define GCLM_MAX_RECALL_THRESHOLDS 8     /* gclm_field_errors */
+#ifndef GCLM_HYPOTHESIS_CHUNK
+#define GCLM_HYPOTHESIS_CHUNK 16         /* gclm_hypothesis_scores: hypotheses scored per read of an image's planes */
+#endif
 #define GCLM_CAM_STRIDE 8     /* {w,h,fx,fy,cx,cy,k1,k2}: BaseCamera._data, camera.py:25-41 */
 #define GCLM_GRAV_STRIDE 3    /* unit gravity: Gravity._data, gravity.py:18-28 */
 
@@ -365,6 +369,47 @@ int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav,
                       const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int n_thresholds,
                       const float* thresholds_deg, void* d_workspace, size_t workspace_bytes, float* d_stats, float* d_up_err,
                       float* d_lat_err, void* stream);
+
+/*
+ * Which of N candidate calibrations per image fits the image's predicted perspective fields best, in one pass over the
+ * planes: the scores the reference's RANSAC baseline ranks its hypotheses with (siclib/models/optimization/ransac.py:
+ * check_up_inliers, check_latitude_inliers, get_best_index), with every hypothesis' target fields evaluated per pixel in
+ * registers -- no field is rendered, and each plane of an image is read once per GCLM_HYPOTHESIS_CHUNK hypotheses.
+ * Predictions as gclm_field_errors takes them: d_up (B, 2, H, W) planar, d_lat (B, 1, H, W), either may be NULL, not both;
+ * confidences d_up_conf, d_lat_conf (B, H, W), either may be NULL: a NULL confidence counts as 1.  Optional d_mask (B, H, W)
+ * multiplies both contributions (the reference's `inliers`; usually zeros and ones, any weight is taken as it is).
+ * d_cam (B, N, 8), d_grav (B, N, 3): hypothesis n of image b is row b N + n, the reference's (B N) order; one camera model
+ * per call; gravity is used as stored.  All float32 in device memory.
+ * Per pixel and hypothesis, e_up and e_lat are exactly the per-pixel errors of gclm_field_errors at that hypothesis (the
+ * normalised target, the masked atan2 angle in degrees, |lat - t_lat| 180 / pi).  Then, with c the confidence times the mask,
+ *   up[b, n]    = sum over pixels of (e_up < up_threshold_deg ? 1 : 0) * c_up,   strict;   lat[b, n] likewise
+ *   total[b, n] = up_weight up[b, n] + lat_weight lat[b, n]
+ * d_scores (B, N, 3) = [up, lat, total]; the scores of a field whose pointer is NULL are 0 (the reference returns zeros for
+ * an absent latitude).  Optional d_best (B) int32: the first index of the largest total of that image, compared on the
+ * float32 totals as written; a NaN total counts as the maximum, as torch.argmax has it.
+ * hit * c is a multiplication, as in torch: a NaN error (a NaN prediction, a NaN in the hypothesis' camera or gravity) hits
+ * nothing and contributes 0 -- such a hypothesis scores 0 and is no error; a NaN confidence or mask pixel makes that field's
+ * score of that image NaN for EVERY hypothesis (an infinite one: NaN for the hypotheses that miss the pixel) and leaves the
+ * other images untouched.  The thresholds (degrees) and weights are host floats, finite.
+ * Every workgroup scores one tile of pixels against one chunk of hypotheses and leaves one partial record (float32 sums)
+ * per hypothesis in d_workspace, of at least gclm_hypothesis_scores_workspace(B, N, H, W) bytes (0 for sizes the call
+ * refuses); a second small launch sums each hypothesis' records in float64 in a fixed order, forms total in float64, rounds
+ * once and takes the argmax.  No atomics: results are bit-identical from call to call, and the bits of d_scores[b, n]
+ * depend on image b's pixels, H, W, the planes' alignment (pixels per lane, as gclm_field_errors: four where W % 4 == 0 and
+ * every plane is 16-byte aligned, two where W is even and every plane 8-byte aligned, one otherwise) and the eleven
+ * numbers of hypothesis (b, n) alone -- not on N, on n, on the other hypotheses or on the other images.
+ * Returns -3 (before any HIP call) for a NULL d_cam, d_grav, d_scores or d_workspace, both fields NULL, a confidence given
+ * for a NULL field, B or N outside 1..65535, H or W < 1, H * W > 2^31 - 1 (or a grid of (W / 64) x (H / 4) tiles over 2^32
+ * threads), a camera_model outside 0..3, a non-finite threshold or weight, a workspace that is too small, a pointer that is
+ * not 4-byte aligned, or an output (scores, best, workspace) that overlaps an input or another output; -10 if a launch
+ * fails.  Asynchronous on `stream`; no allocation.
+ */
+size_t gclm_hypothesis_scores_workspace(int B, int N, int H, int W);
+int gclm_hypothesis_scores(int camera_model, const float* d_cam, const float* d_grav, int B, int N, int H, int W,
+                           const float* d_up, const float* d_lat, const float* d_up_conf, const float* d_lat_conf,
+                           const float* d_mask, float up_threshold_deg, float lat_threshold_deg, float up_weight,
+                           float lat_weight, void* d_workspace, size_t workspace_bytes, float* d_scores, int* d_best,
+                           void* stream);
 
 /*
  * BaseCamera.get_img_from_pano (geocalib/camera.py:414-514) for n images, in one pass: d_dst (n, C, H, W) holds image i
