@@ -117,6 +117,10 @@ _SIGNATURES = {
     "gclm_set_slat_plane_limit": (C.c_int, [_P, C.c_size_t]),
     "gclm_slat_plane_bytes": (C.c_size_t, [_P]),
     "gclm_release_workspace": (C.c_int, [_P]),
+    "gclm_set_conf_pack": (C.c_int, [_P, C.c_int]),
+    "gclm_plan_conf_pack": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "gclm_conf_pack_bytes": (C.c_size_t, [_P]),
+    "gclm_conf_pack_fallbacks": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "gclm_read_probe": (C.c_int, [C.POINTER(_P), C.c_int, C.c_size_t, _P]),
     "gclm_plan_cut": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gclm_set_row_pairs": (C.c_int, [_P, C.c_int]),

@@ -30,6 +30,9 @@ using namespace gclm;
 #ifndef GCLM_ROW_PAIRS_DEFAULT
 #define GCLM_ROW_PAIRS_DEFAULT -1   // a handle's initial gclm_set_row_pairs mode (1: test builds that run the whole suite on row pairs)
 #endif
+#ifndef GCLM_CONF_PACK_MIN_PIXELS
+#define GCLM_CONF_PACK_MIN_PIXELS (256ll << 20)  // B * H * W from which a pinhole solve packs its confidence planes on its own (wants_conf_pack)
+#endif
 #ifndef GCLM_ISO_FINAL
 #define GCLM_ISO_FINAL 1      // A/B switch: 0 = the final sweep always takes the general focal column
 #endif
@@ -51,8 +54,10 @@ struct Plan {
     Geometry geo{};                 // the one-row walk, or row pairs (geo.mirror)
     bool one_launch = false;        // an LM step is ONE launch (gclm_pass.hip: fused_step_kernel); never with row pairs
     const float* given = nullptr;   // the caller's plane of sin(latitude) every sweep reads in place of `lat`, or null
-    float* slat = nullptr;          // else the library's scratch plane (gclm_handle::slat_buf), or null: sweeps compute sin(latitude)
+    float* slat = nullptr;          // else the library's scratch plane (gclm_handle::slat), or null: sweeps compute sin(latitude)
     bool slat_filled = false;       // ... which the first sweep fills and the later ones read (next_sweep)
+    uint32_t* cpack = nullptr;      // the library's plane of packed confidences (gclm_handle::cpack), or null: sweeps read the caller's two
+    bool cpack_filled = false;      // ... filled by the first sweep, read by the later ones, like `slat`; never both planes in one solve
 
     void choose_walk(const gclm_handle* h, int B, int H, int W, bool aligned16, bool five);
     SweepArgs next_sweep(const gclm_handle* h, const PBlock* pb, bool loop_params, int stop_step);
@@ -76,14 +81,20 @@ struct gclm_handle {
         Plan plan;                  // of gclm_shared_begin: every gclm_shared_reduce and gclm_shared_finish takes its next sweep from it
         float *cam_io = nullptr, *grav_io = nullptr;
     } sh;
-    // The sin(latitude) scratch plane is an allocation of its own, of exactly the size asked for (no headroom), and the only
-    // part of the workspace a solve can do without: see ensure_slat.
-    float* slat_buf = nullptr;      // owned: (slat_bytes / 4) floats, or null
-    size_t slat_bytes = 0;
-    size_t slat_refused = 0;        // smallest plane size (bytes) whose allocation failed or was refused by the limit since the
-                                    // last change of the limit / mode: such a size is not tried again on every solve
-    size_t slat_limit = 0;          // gclm_set_slat_plane_limit: 0 = built-in rule (half of the free device memory), else bytes
+    // The two scratch planes -- sin(latitude) for the distortion models, the packed confidences for pinhole -- are allocations of
+    // their own, of exactly the size asked for (no headroom), and the only parts of the workspace a solve can do without: see
+    // ensure_plane.
+    struct ScratchPlane {
+        void* buf = nullptr;        // owned: `bytes` bytes, or null
+        size_t bytes = 0;
+        size_t refused = 0;         // smallest plane size (bytes) whose allocation failed or was refused by the limit since the
+                                    // last change of the limit / mode: such a size is not tried again on every solve ...
+        int refused_asks = 0;       // ... but after kRefusalAsks solves that wanted it (memory others held may be free again)
+    } slat, cpack;
+    size_t slat_limit = 0;          // gclm_set_slat_plane_limit (either plane): 0 = built-in rule (half of the free device memory), else bytes
     int slat_plane = -1;            // gclm_set_slat_plane: -1 = built-in choice, 0 = never, 1 = wherever the sweep has it
+    int conf_pack = -1;             // gclm_set_conf_pack: -1 = built-in choice, 0 = never, 1 = wherever the sweep has it
+    int cpack_images = 0;           // images of the last solve if it packed its confidences, else 0 (gclm_conf_pack_fallbacks)
     int row_pairs = GCLM_ROW_PAIRS_DEFAULT;   // gclm_set_row_pairs: -1 = built-in choice, 0 = never, 1 = wherever the sweep has the row-pair walk
     int sweep_iters = 0;            // gclm_set_sweep_iters: 0 = built-in choice
     int fused_mode = -1;            // gclm_set_fused_steps: -1 = built-in choice, 0 = never, 1 = whenever it is valid
@@ -175,6 +186,7 @@ int ensure_workspace(gclm_handle* h, int B, int nchunks, int G) {
     const size_t o_fsys = take(sizeof(float) * kNAccMax * (size_t)B);
     const size_t o_gp = take(sizeof(float) * GCLM_SHARED_PARTIAL_STRIDE * (size_t)(G > 0 ? G : 1));
     const size_t o_ctrl = take(sizeof(Ctrl));
+    const size_t o_cpf = take(sizeof(unsigned) * B);
     if (off > h->ws_bytes) {
         if (h->ws) GCLM_HIP(h, hipFree(h->ws));
         h->ws = nullptr;
@@ -195,44 +207,45 @@ int ensure_workspace(gclm_handle* h, int B, int nchunks, int G) {
     c.partials2 = reinterpret_cast<float*>(base + o_part2);
     c.frame_sys = reinterpret_cast<float*>(base + o_fsys);
     c.ctrl = reinterpret_cast<Ctrl*>(base + o_ctrl);
+    c.cpack_flags = reinterpret_cast<unsigned*>(base + o_cpf);
     h->group_partials = reinterpret_cast<float*>(base + o_gp);
     return 0;
 }
 
-// The sin(latitude) scratch plane of a solve of `floats` pixels (0: none wanted): returns the plane, or null when the solve
-// runs without it -- never an error.  The plane only saves arithmetic (gclm_pass.hip: row_math, SLAT); a sweep that computes
-// sin(latitude) itself produces the same bits, so whenever the plane cannot be had -- hipMalloc fails, or the plane is larger
-// than the limit (gclm_set_slat_plane_limit; built-in: half of the device memory that is free once the old plane is
-// released) -- the solve goes on without it, as the library did before it had the plane.  Exact size, no headroom: the plane
-// is 400x the rest of the workspace.  A size that was refused is remembered (slat_refused) so that a serving loop does not
-// pay a failing hipMalloc (and its device synchronisation) per call.
-float* ensure_slat(gclm_handle* h, size_t floats) {
-    if (floats == 0) return nullptr;
-    const size_t bytes = floats * sizeof(float);
-    if (bytes <= h->slat_bytes) return h->slat_buf;
-    if (h->slat_refused && bytes >= h->slat_refused) return nullptr;
-    if (h->slat_limit && bytes > h->slat_limit) { h->slat_refused = bytes; return nullptr; }     // (the old, smaller plane stays)
+// A scratch plane of `bytes` bytes for this solve (0: none wanted): returns the plane, or null when the solve runs without it
+// -- never an error.  Either plane only saves work (gclm_pass.hip: row_math, SLAT / CPACK): the sweeps that do without it are
+// the library's own earlier ones, so whenever the plane cannot be had -- hipMalloc fails, or the plane is larger than the limit
+// (gclm_set_slat_plane_limit; built-in: half of the device memory that is free once the old plane is released) -- the solve
+// goes on without it.  Exact size, no headroom: a plane is 400x the rest of the workspace.  A plane the handle holds is given
+// up only once its larger successor is in hand.  A size that was refused is remembered so that a serving loop does not pay a
+// failing hipMalloc (and its device synchronisation) per call; the refusal expires after kRefusalAsks solves that wanted it.
+constexpr int kRefusalAsks = 64;
+void* ensure_plane(gclm_handle* h, gclm_handle::ScratchPlane& pl, size_t bytes) {
+    if (bytes == 0) return nullptr;
+    if (bytes <= pl.bytes) return pl.buf;
+    if (pl.refused && bytes >= pl.refused) {
+        if (++pl.refused_asks < kRefusalAsks) return nullptr;
+        pl.refused = 0;                       // expired: this solve asks again
+    }
+    auto refuse = [&]() -> void* { pl.refused = bytes; pl.refused_asks = 0; return nullptr; };     // (the old, smaller plane stays)
+    if (h->slat_limit && bytes > h->slat_limit) return refuse();
     if (!h->slat_limit) {                     // built-in rule: half of what is free once the old plane is released
         size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > (free_b + h->slat_bytes) / 2) {
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > (free_b + pl.bytes) / 2) {
             (void)hipGetLastError();
-            h->slat_refused = bytes;          // (the old, smaller plane stays here too)
-            return nullptr;
+            return refuse();
         }
     }
-    if (h->slat_buf) (void)hipFree(h->slat_buf);
-    h->slat_buf = nullptr;
-    h->slat_bytes = 0;
     void* p = nullptr;
     const bool ok = hipMalloc(&p, bytes) == hipSuccess && p != nullptr;
     if (!ok) {
         (void)hipGetLastError();          // the failure is handled here: it must not surface in the next launch's status
-        h->slat_refused = bytes;
-        return nullptr;
+        return refuse();
     }
-    h->slat_buf = static_cast<float*>(p);
-    h->slat_bytes = bytes;
-    return h->slat_buf;
+    if (pl.buf) (void)hipFree(pl.buf);
+    pl.buf = p;
+    pl.bytes = bytes;
+    return pl.buf;
 }
 
 int timed_sweep(gclm_handle* h, const SweepArgs& a, hipStream_t s, const FusedArgs* fused = nullptr) {
@@ -302,10 +315,19 @@ void Plan::choose_walk(const gclm_handle* h, int B, int H, int W, bool aligned16
     if (pairs) geo = plan_geometry(B, H, W, aligned16, h->sweep_iters, c.camera_model, true);
 }
 
+// Would a call of `pixels` pixels that runs `sweeps` sweeps on plan `p` keep its confidences packed, the handle's mode and the
+// kernels permitting?  (make_plan, which also knows the call's other planes, and gclm_plan_conf_pack.)
+bool wants_conf_pack(const gclm_handle* h, const Plan& p, bool five, int sweeps, long long pixels) {
+    const int model = h->cfg.camera_model;
+    return model == GCLM_PINHOLE && p.geo.vec == 4 && five && !p.one_launch && sweeps >= 2 && h->conf_pack != 0 &&
+           sweep_has_conf_pack(model) && (h->conf_pack > 0 || (pixels >= GCLM_CONF_PACK_MIN_PIXELS && sweeps >= 6));
+}
+
 // The one preamble of gclm_solve / gclm_calibrate, gclm_system and gclm_shared_begin: the plan of a call that runs `sweeps`
 // sweeps over fields `f` of B images (0: an empty shard of a session, planned as one image), the sizes in h->ctx and the
 // workspace.  The caller has set the group fields and iso_final of h->ctx.  `sin_lat`: the plane the caller handed, or null.
-int make_plan(gclm_handle* h, Plan& p, const Fields& f, int B, int H, int W, const float* sin_lat, int sweeps) {
+int make_plan(gclm_handle* h, Plan& p, const Fields& f, int B, int H, int W, const float* sin_lat, int sweeps,
+              bool may_pack = true) {
     const int Bp = B > 0 ? B : 1, model = h->cfg.camera_model;
     p = Plan{};
     p.f = f;
@@ -328,13 +350,24 @@ int make_plan(gclm_handle* h, Plan& p, const Fields& f, int B, int H, int W, con
     const bool keep = !p.given && h->slat_plane != 0 && !p.one_launch && float4_five && sweeps >= 2 &&
                       !(h->slat_plane < 0 && model == GCLM_PINHOLE) && sweep_has_slat_plane(model);
     if (int rc = ensure_workspace(h, Bp, p.geo.nchunks, c.n_groups)) return rc;
-    p.slat = ensure_slat(h, keep ? (size_t)B * H * W : 0);
+    p.slat = static_cast<float*>(ensure_plane(h, h->slat, keep ? (size_t)B * H * W * sizeof(float) : 0));
+    // Does it keep its two confidence planes as one plane of packed words (gclm_pass.hip: row_math, CPACK)?  Pinhole's batch
+    // sweeps only (memory-bound: 16 instead of 20 bytes per pixel from the second sweep on), never beside another plane, not a
+    // split shared-intrinsics session (`may_pack`).  Built-in choice: large calls (GCLM_CONF_PACK_MIN_PIXELS, 874 images of
+    // 640x480: the plane pays from 110 images on, profiles/conf_pack_crossover.json, but below the threshold a sweep's launch
+    // time over the caller's five planes stays a true HBM rate, which the benchmark's records of such batches state) that are
+    // long enough to pay for the fill, which costs about three later sweeps' saving (wants_conf_pack).
+    const long long pixels = (long long)B * H * W;
+    const bool pack = may_pack && !p.given && !p.slat && wants_conf_pack(h, p, f.five(), sweeps, pixels);
+    p.cpack = static_cast<uint32_t*>(ensure_plane(h, h->cpack, pack ? (size_t)pixels * sizeof(uint32_t) : 0));
+    h->cpack_images = p.cpack ? B : 0;
     h->sh.active = false;
     return 0;
 }
 
 // The arguments of the plan's next sweep with parameter blocks `pb`.  A solve that reads the caller's plane: every sweep
-// loads it (SLAT = 2); one that keeps the scratch plane: the first sweep fills it, the others read it.
+// loads it (SLAT = 2); one that keeps a scratch plane (sin(latitude), or the packed confidences): the first sweep fills it,
+// the others read it.
 SweepArgs Plan::next_sweep(const gclm_handle* h, const PBlock* pb, bool loop_params, int stop_step) {
     SweepArgs a{};
     a.up = f.up; a.lat = f.lat; a.upc = f.up ? f.upc : nullptr; a.latc = f.latc;
@@ -357,6 +390,12 @@ SweepArgs Plan::next_sweep(const gclm_handle* h, const PBlock* pb, bool loop_par
         if (slat_filled) a.lat = slat;
         a.slat_mode = slat_filled ? 2 : 1;
         slat_filled = true;
+    }
+    if (cpack) {
+        a.cpack = cpack;
+        a.cpack_flags = h->ctx.cpack_flags;
+        a.cpack_mode = cpack_filled ? 2 : 1;
+        cpack_filled = true;
     }
     return a;
 }
@@ -616,7 +655,8 @@ int gclm_destroy(gclm_handle* h) {
     DeviceGuard guard(h->device);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->ws) (void)hipFree(h->ws);
-    if (h->slat_buf) (void)hipFree(h->slat_buf);
+    if (h->slat.buf) (void)hipFree(h->slat.buf);
+    if (h->cpack.buf) (void)hipFree(h->cpack.buf);
     if (h->progress_host) (void)hipHostFree(h->progress_host);
     delete h;
     return 0;
@@ -624,14 +664,16 @@ int gclm_destroy(gclm_handle* h) {
 
 const char* gclm_last_error(const gclm_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-size_t gclm_workspace_bytes(const gclm_handle* h) { return h ? h->ws_bytes + h->slat_bytes : 0; }
+size_t gclm_workspace_bytes(const gclm_handle* h) { return h ? h->ws_bytes + h->slat.bytes + h->cpack.bytes : 0; }
 
-size_t gclm_slat_plane_bytes(const gclm_handle* h) { return h ? h->slat_bytes : 0; }
+size_t gclm_slat_plane_bytes(const gclm_handle* h) { return h ? h->slat.bytes : 0; }
+
+size_t gclm_conf_pack_bytes(const gclm_handle* h) { return h ? h->cpack.bytes : 0; }
 
 int gclm_set_slat_plane_limit(gclm_handle* h, size_t max_bytes) {
     if (!h) return -1;
     h->slat_limit = max_bytes;
-    h->slat_refused = 0;
+    h->slat.refused = h->cpack.refused = 0;
     h->sh.active = false;
     return 0;
 }
@@ -646,9 +688,11 @@ int gclm_release_workspace(gclm_handle* h) {
     h->ws_bytes = 0;
     h->ctx = SolveCtx{};
     h->group_partials = nullptr;
-    if (h->slat_buf) GCLM_HIP(h, hipFree(h->slat_buf));
-    h->slat_buf = nullptr;
-    h->slat_bytes = h->slat_refused = 0;
+    for (gclm_handle::ScratchPlane* pl : {&h->slat, &h->cpack}) {
+        if (pl->buf) GCLM_HIP(h, hipFree(pl->buf));
+        *pl = gclm_handle::ScratchPlane{};
+    }
+    h->cpack_images = 0;
     return 0;
 }
 
@@ -670,12 +714,42 @@ int gclm_plan_cut(const gclm_handle* h, int B, int H, int W, int aligned16, int*
     return 0;
 }
 
+int gclm_plan_conf_pack(const gclm_handle* h, int B, int H, int W, int aligned16, int five_planes, int sweeps, int* pack) {
+    if (!h || !pack) return -1;
+    if (B < 1 || H < 1 || W < 1) return -3;
+    Plan p;
+    p.choose_walk(h, B, H, W, aligned16 != 0, five_planes != 0);
+    *pack = wants_conf_pack(h, p, five_planes != 0, sweeps, (long long)B * H * W) ? 1 : 0;
+    return 0;
+}
+
 int gclm_set_slat_plane(gclm_handle* h, int mode) {
     if (!h) return -1;
     if (mode < -1 || mode > 1) return fail(h, -3, "gclm_set_slat_plane: mode %d not in {-1, 0, 1}", mode);
     h->slat_plane = mode;
-    h->slat_refused = 0;
+    h->slat.refused = 0;
     h->sh.active = false;
+    return 0;
+}
+
+int gclm_set_conf_pack(gclm_handle* h, int mode) {
+    if (!h) return -1;
+    if (mode < -1 || mode > 1) return fail(h, -3, "gclm_set_conf_pack: mode %d not in {-1, 0, 1}", mode);
+    h->conf_pack = mode;
+    h->cpack.refused = 0;
+    return 0;
+}
+
+int gclm_conf_pack_fallbacks(gclm_handle* h, int* n) {
+    if (!h || !n) return -1;
+    *n = 0;
+    if (h->cpack_images == 0 || !h->ctx.cpack_flags) return 0;
+    DeviceGuard guard(h->device);
+    GCLM_HIP(h, guard.status);
+    GCLM_HIP(h, hipDeviceSynchronize());
+    std::vector<unsigned> flags(h->cpack_images);
+    GCLM_HIP(h, hipMemcpy(flags.data(), h->ctx.cpack_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (unsigned f : flags) *n += f != 0;
     return 0;
 }
 
@@ -855,7 +929,8 @@ int gclm_shared_begin_ex(gclm_handle* h, const float* d_up, const float* d_lat, 
     GCLM_HIP(h, guard.status);
     SolveCtx& c = h->ctx;
     c.n_groups = num_groups; c.group_size = 1; c.group_of_frame = d_group_of_frame; c.iso_final = 0;
-    if (int rc = make_plan(h, h->sh.plan, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B_local, H, W, d_sin_lat, h->cfg.num_steps + 1))
+    if (int rc = make_plan(h, h->sh.plan, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B_local, H, W, d_sin_lat, h->cfg.num_steps + 1,
+                           false))
         return rc;
     h->sh.cam_io = d_cam_io; h->sh.grav_io = d_grav_io;
     h->sh.active = true;

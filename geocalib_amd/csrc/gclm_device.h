@@ -490,6 +490,19 @@ __device__ __forceinline__ F sin_halfpi(F x, F t) {
 template <typename F>
 __device__ __forceinline__ F sin_halfpi(F x) { return sin_halfpi(x, x * x); }
 
+// The packed confidence plane of a pinhole solve (gclm_pass.hip: row_conf; gclm_api.hip: Plan::cpack): the two confidences of a
+// pixel as unsigned 16-bit fixed point in one 32-bit word, the up confidence in the low half.  In numpy, on float32 arrays:
+//   q    = np.rint(c * np.float32(65535)).astype(np.uint32)          (float32 product, round half to even)
+//   word = q_up | q_lat << 16
+//   c'   = q.astype(np.float32) * (np.float32(1) / np.float32(65535))   (the float32 constant, a float32 product)
+// conf_encode is defined for c in [0, 1]; anything else (NaN included) is the caller's to keep out (row_conf raises the image's
+// flag and never reads the word back).  A confidence that is already c' of some q survives the round trip bit for bit.
+constexpr float kConfScale = 65535.0f;
+constexpr float kConfStep = 1.0f / 65535.0f;
+__device__ __forceinline__ uint32_t conf_encode(float c) { return (uint32_t)rintf(c * kConfScale); }
+__device__ __forceinline__ float conf_decode(uint32_t q) { return (float)q * kConfStep; }
+__device__ __forceinline__ uint32_t conf_word(uint32_t q_up, uint32_t q_lat) { return q_up | (q_lat << 16); }
+
 #pragma clang fp contract(fast)
 
 }  // namespace dev

@@ -111,6 +111,10 @@ struct SweepArgs {
                             // 2: `lat` IS the filled scratch plane (sin(latitude) is loaded, not computed)
     int hrows;              // rows the tiles walk: H, or H / 2 when a lane takes row H - y along with row y (mirror)
     int mirror;             // 1: the row-pair walk (gclm_pass.hip: row_math_mirror); the geometry was planned for H / 2 rows
+    uint32_t* cpack;        // library-owned plane (B,H,W) of packed confidence words (gclm_device.h: conf_word), or nullptr
+    unsigned* cpack_flags;  // (B) per image: non-zero once the fill sweep met a confidence the format cannot hold
+    int cpack_mode;         // 0: `upc` / `latc` are read; 1: ... and this sweep fills `cpack` and raises `cpack_flags`;
+                            // 2: `cpack` is read in their place, except by the images whose flag is up (gclm_pass.hip: row_conf)
 };
 
 struct Geometry {          // how a sweep is cut into blocks (column-stationary tiles, see gclm_pass.hip)
@@ -133,6 +137,7 @@ struct SolveCtx {
     float* partials2;           // second half of the double buffer (fused small-batch path)
     float* frame_sys;           // (B, acc_floats(model)) reduced per-frame system (shared mode)
     Ctrl* ctrl;
+    unsigned* cpack_flags;      // (B) flags of the packed confidence plane: reset with the control block (init_kernel)
 };
 struct InitArgs {              // initial estimate: explicit (cam, grav) or trivial estimation from the priors
     const float* cam;           // (B,8) or nullptr -> get_trivial_estimation on the device
@@ -185,6 +190,7 @@ hipError_t launch_fused_step(int camera_model, const SweepArgs& a, const FusedAr
 bool sweep_has_mirror(int camera_model);       // the model's five-plane float4 sweep has the row-pair instantiations
 bool sweep_mirror_builtin(int camera_model);   // ... and they are the library's own choice for it
 bool sweep_has_slat_plane(int camera_model);   // the model's five-plane float4 sweep has the SLAT instantiations
+bool sweep_has_conf_pack(int camera_model);    // ... the CPACK instantiations (the packed confidence plane)
 hipError_t launch_residual_fields(int camera_model, const float* d_up, const float* d_lat, const float* d_cam,
                                   const float* d_grav, int B, int H, int W, float* d_r_up, float* d_r_lat, hipStream_t s);
 hipError_t launch_huber_costs(const float* d_residual, size_t n, int dim, float scale, const float* d_conf,

@@ -72,6 +72,10 @@
                                // waves (the no-math build: 6.89 TB/s at 6-8 waves, 6.97 at 3, 7.03 at 2, r06_variant_occupancy.log) and
                                // pinhole's arithmetic still hides at 3 (-0.7 ... -1.9 % per sweep on six allocations of three boxes; 2
                                // waves +1.4 %, simple_radial 4 -> 3 +0.6 ... +1.9 %: r06_variant_occupancy_{math,pinhole}.log).  Same bits.
+#ifndef GCLM_CPACK_LDS
+#define GCLM_CPACK_LDS 30720   // ... of the launches that READ the packed confidence plane: FIVE workgroups per CU.  Four streams per lane put a
+#endif                         // fifth less in flight per wave, and at 201 VALU per 4 pixels the arithmetic no longer hides at 3 waves: same-allocation
+                               // gain of the whole solve over the unpacked one at 3 / 4 / 5 workgroups +9.2 / +11.1 / +12.2 % (profiles/conf_pack_occupancy.json)
 #ifndef GCLM_DYN_LDS
 #define GCLM_DYN_LDS 0         // measurement only: dynamic LDS bytes of a sweep launch, i.e. a cap on the workgroups per CU (with GCLM_NOMATH:
 #endif                         // what the access pattern streams at 2 ... 8 waves per SIMD, profiles/r06_variant_occupancy.log)
@@ -771,6 +775,14 @@ struct Lane<4> {
         __builtin_nontemporal_store(v4{v[0].x, v[0].y, v[1].x, v[1].y},
                                     reinterpret_cast<v4*>(reinterpret_cast<char*>(base) + byte_off));
     }
+    // the lane's four packed confidence words (gclm_device.h: conf_word), streamed like the sin(latitude) plane
+    typedef uint32_t P __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ P ldp(const uint32_t* base, uint32_t byte_off) {
+        return __builtin_nontemporal_load(reinterpret_cast<const P*>(reinterpret_cast<const char*>(base) + byte_off));
+    }
+    static __device__ __forceinline__ void stp(uint32_t* base, uint32_t byte_off, P w) {
+        __builtin_nontemporal_store(w, reinterpret_cast<P*>(reinterpret_cast<char*>(base) + byte_off));
+    }
     static __device__ __forceinline__ F get(const V& v, int k) { return k == 0 ? f2{v.x, v.y} : f2{v.z, v.w}; }
     static __device__ __forceinline__ V ones() { return make_float4(1.f, 1.f, 1.f, 1.f); }
     static __device__ __forceinline__ bool any_zero(F a) { return a.x == 0.f || a.y == 0.f; }
@@ -785,6 +797,7 @@ template <>
 struct Lane<1> {
     using F = float;
     using V = float;
+    using P = uint32_t;              // (the scalar path has no packed confidence plane)
     static constexpr int kPairs = 1;
     static __device__ __forceinline__ V ld(const float* base, uint32_t byte_off) {
         return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
@@ -826,14 +839,17 @@ __device__ __forceinline__ LaneJob<VEC> lane_job(const SweepArgs& a, const int c
     return j;
 }
 
-// The five values a lane reads per loop iteration (one float4 -- or one pixel -- of every plane)
+// The five values a lane reads per loop iteration (one float4 -- or one pixel -- of every plane); CPACK = 2: four, the two
+// confidences come as one packed word per pixel (vpk; row_conf)
 template <int VEC>
 struct RowData {
     typename Lane<VEC>::V vux, vuy, vlat, vcu, vcl;
+    typename Lane<VEC>::P vpk;
 };
-template <bool HAS_UP, bool HAS_UPC, bool HAS_LATC, int VEC>
+template <bool HAS_UP, bool HAS_UPC, bool HAS_LATC, int VEC, int CPACK = 0>
 __device__ __forceinline__ RowData<VEC> load_row(const float* upx, const float* upy, const float* lat, const float* upc,
-                                                 const float* latc, const uint32_t off) {
+                                                 const float* latc, const uint32_t off,
+                                                 [[maybe_unused]] const uint32_t* cpk = nullptr) {
     using L = Lane<VEC>;
     RowData<VEC> r;
     r.vcu = L::ones();
@@ -843,9 +859,69 @@ __device__ __forceinline__ RowData<VEC> load_row(const float* upx, const float* 
         r.vuy = L::ld(upy, off);
     }
     r.vlat = L::ld(lat, off);
-    if constexpr (HAS_UP && HAS_UPC) r.vcu = L::ld(upc, off);
-    if constexpr (HAS_LATC) r.vcl = L::ld(latc, off);
+    if constexpr (CPACK == 2) {
+        r.vpk = L::ldp(cpk, off);
+    } else {
+        if constexpr (HAS_UP && HAS_UPC) r.vcu = L::ld(upc, off);
+        if constexpr (HAS_LATC) r.vcl = L::ld(latc, off);
+    }
     return r;
+}
+
+// The confidences of the lane's pixels of one row, per CPACK (see row_math)
+template <int VEC, int CPACK>
+__device__ __forceinline__ void row_conf(const RowData<VEC>& r, typename Lane<VEC>::F (&cu)[Lane<VEC>::kPairs],
+                                         typename Lane<VEC>::F (&cl)[Lane<VEC>::kPairs], [[maybe_unused]] uint32_t* cp_out,
+                                         [[maybe_unused]] const uint32_t off, [[maybe_unused]] bool* cp_bad) {
+    using L = Lane<VEC>;
+    if constexpr (CPACK == 0) {
+#pragma unroll
+        for (int k = 0; k < L::kPairs; ++k) { cu[k] = L::get(r.vcu, k); cl[k] = L::get(r.vcl, k); }
+    } else {
+        static_assert(VEC == 4, "the packed confidence plane: float4 path only");
+        // two pixels' decode in one packed multiply: the bits of dev::conf_decode per pixel
+        auto decode2 = [](uint32_t qa, uint32_t qb) { return f2{(float)qa, (float)qb} * dev::kConfStep; };
+        if constexpr (CPACK == 2) {
+            const uint32_t w[4] = {r.vpk.x, r.vpk.y, r.vpk.z, r.vpk.w};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                cu[k] = decode2(w[2 * k] & 0xffffu, w[2 * k + 1] & 0xffffu);
+                cl[k] = decode2(w[2 * k] >> 16, w[2 * k + 1] >> 16);
+            }
+        } else {
+            // fill: every confidence the format holds is evaluated as decode(encode(c)), what every later sweep of the solve
+            // will read; one it cannot hold (outside [0, 1], NaN) keeps its value here and raises the image's flag
+            const float vu[4] = {r.vcu.x, r.vcu.y, r.vcu.z, r.vcu.w}, vl[4] = {r.vcl.x, r.vcl.y, r.vcl.z, r.vcl.w};
+            uint32_t qu[4], ql[4];
+            bool bad = false;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bool oku = vu[i] >= 0.f && vu[i] <= 1.f, okl = vl[i] >= 0.f && vl[i] <= 1.f;     // (false for a NaN)
+                qu[i] = dev::conf_encode(oku ? vu[i] : 0.f);
+                ql[i] = dev::conf_encode(okl ? vl[i] : 0.f);
+                bad = bad || !oku || !okl;
+            }
+            typename L::P word;
+            word.x = dev::conf_word(qu[0], ql[0]); word.y = dev::conf_word(qu[1], ql[1]);
+            word.z = dev::conf_word(qu[2], ql[2]); word.w = dev::conf_word(qu[3], ql[3]);
+            L::stp(cp_out, off, word);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                cu[k] = decode2(qu[2 * k], qu[2 * k + 1]);
+                cl[k] = decode2(ql[2 * k], ql[2 * k + 1]);
+            }
+            if (bad) {                                       // (rare: the exact values, lane by lane)
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    cu[k] = f2{vu[2 * k] >= 0.f && vu[2 * k] <= 1.f ? cu[k].x : vu[2 * k],
+                               vu[2 * k + 1] >= 0.f && vu[2 * k + 1] <= 1.f ? cu[k].y : vu[2 * k + 1]};
+                    cl[k] = f2{vl[2 * k] >= 0.f && vl[2 * k] <= 1.f ? cl[k].x : vl[2 * k],
+                               vl[2 * k + 1] >= 0.f && vl[2 * k + 1] <= 1.f ? cl[k].y : vl[2 * k + 1]};
+                }
+                *cp_bad = true;
+            }
+        }
+    }
 }
 
 // sin(latitude_field) of the lane's pixels of one row, per SLAT (see row_math)
@@ -885,21 +961,34 @@ __device__ __forceinline__ void row_slat(const RowData<VEC>& r, typename Lane<VE
 //             or a plane the CALLER handed (gclm_solve_ex ...: written by the head epilogue, gclm_pack_fields_ex, with the
 //             same sin_halfpi), read by every sweep of the solve from the first, also by the one-launch-per-step kernel
 // Same polynomial, same bits: a float stored and loaded is the float that was computed.
-template <int MODEL, bool HAS_UP, bool LOGF, int VEC, int SLAT = 0>
+//
+// CPACK -- pinhole's batch sweep is bound by the bytes it reads, 20 per pixel.  The two confidence planes are the one pair of
+// inputs that compresses for free (16-bit fixed point moves a solve by what float32 rounding inside it does: DESIGN.md 9.4), so a
+// pinhole solve keeps them in a LIBRARY-owned plane of one 32-bit word per pixel (gclm_device.h: conf_word; the boundary is
+// unchanged) and every sweep after the first reads 16 bytes per pixel:
+//   CPACK = 0  the caller's two planes are read
+//   CPACK = 1  ... and packed into the plane (the first sweep of a solve; `cp_out` + `off`), the pixel itself is evaluated
+//              with decode(encode(c)): all sweeps of the solve see ONE objective.  A confidence the format cannot hold keeps
+//              its value and sets *cp_bad (sweep_body raises the image's flag)
+//   CPACK = 2  the plane is read in place of the two (every later sweep; an image whose flag is up takes CPACK = 0: sweep_kernel)
+// The decoded confidence enters the same expressions as a loaded one: confidences that are c' of some q give the bits of CPACK = 0.
+template <int MODEL, bool HAS_UP, bool LOGF, int VEC, int SLAT = 0, int CPACK = 0>
 __device__ __forceinline__ void row_math(const PBlock& P, const HuberK& hk, const typename Lane<VEC>::F (&col_u)[Lane<VEC>::kPairs],
                                          const typename Lane<VEC>::F (&col_px)[Lane<VEC>::kPairs], const int y,
                                          const RowData<VEC>& r, typename Lane<VEC>::F (&acc)[Layout<MODEL>::NACC],
                                          [[maybe_unused]] const bool col_zero, [[maybe_unused]] const bool div_k_tiny,
-                                         [[maybe_unused]] float* slat_out = nullptr, [[maybe_unused]] const uint32_t off = 0) {
+                                         [[maybe_unused]] float* slat_out = nullptr, [[maybe_unused]] const uint32_t off = 0,
+                                         [[maybe_unused]] uint32_t* cp_out = nullptr, [[maybe_unused]] bool* cp_bad = nullptr) {
     using L = Lane<VEC>;
     using F = typename L::F;
-    F slat[L::kPairs];
+    F slat[L::kPairs], cu[L::kPairs], cl[L::kPairs];
     row_slat<VEC, SLAT>(r, slat, slat_out, off);
+    row_conf<VEC, CPACK>(r, cu, cl, cp_out, off, cp_bad);
     const float v = ((float)y - P.cy) * P.ify;
 #if GCLM_NOMATH     // measurement only: the memory-system ceiling of this exact access pattern
 #pragma unroll
     for (int k = 0; k < L::kPairs; ++k)
-        acc[0] = acc[0] + (HAS_UP ? L::get(r.vux, k) + L::get(r.vuy, k) : F(0.f)) + L::get(r.vlat, k) + L::get(r.vcu, k) + L::get(r.vcl, k);
+        acc[0] = acc[0] + (HAS_UP ? L::get(r.vux, k) + L::get(r.vuy, k) : F(0.f)) + L::get(r.vlat, k) + cu[k] + cl[k];
     (void)v;
     (void)hk;
 #else
@@ -910,19 +999,19 @@ __device__ __forceinline__ void row_math(const PBlock& P, const HuberK& hk, cons
 #pragma unroll
         for (int k = 0; k < L::kPairs; ++k)
             pixel_accumulate<MODEL, HAS_UP, LOGF, F, 0, 1>(P, hk, col_u[k], col_px[k], v, HAS_UP ? L::get(r.vux, k) : F(0.f),
-                                                               HAS_UP ? L::get(r.vuy, k) : F(0.f), slat[k], L::get(r.vcu, k),
-                                                               L::get(r.vcl, k), acc, nullptr, nullptr, patch);
+                                                               HAS_UP ? L::get(r.vuy, k) : F(0.f), slat[k], cu[k],
+                                                               cl[k], acc, nullptr, nullptr, patch);
     } else {
 #pragma unroll
         for (int k = 0; k < L::kPairs; ++k) {
             if constexpr (MODEL == GCLM_PINHOLE || MODEL == GCLM_SIMPLE_RADIAL)
                 pixel_accumulate_fast<MODEL, HAS_UP, LOGF, F>(P, hk, col_u[k], col_px[k], v, HAS_UP ? L::get(r.vux, k) : F(0.f),
                                                         HAS_UP ? L::get(r.vuy, k) : F(0.f), slat[k],
-                                                        L::get(r.vcu, k), L::get(r.vcl, k), acc);
+                                                        cu[k], cl[k], acc);
             else
                 pixel_accumulate<MODEL, HAS_UP, LOGF, F>(P, hk, col_u[k], col_px[k], v, HAS_UP ? L::get(r.vux, k) : F(0.f),
-                                                   HAS_UP ? L::get(r.vuy, k) : F(0.f), slat[k], L::get(r.vcu, k),
-                                                   L::get(r.vcl, k), acc);
+                                                   HAS_UP ? L::get(r.vuy, k) : F(0.f), slat[k], cu[k],
+                                                   cl[k], acc);
         }
     }
 #endif
@@ -994,12 +1083,15 @@ __device__ __forceinline__ void row_math_mirror(const PBlock& P, const HuberK& h
 //
 // PRE > 0 (one-launch-per-step kernel only): the values of the lane's first PRE iterations were requested by the caller
 // before its prologue (`pre`, with the lane's job `pj`), so their memory round trip runs under the prologue's.
-template <int MODEL, bool HAS_UP, bool HAS_UPC, bool HAS_LATC, bool LOGF, int VEC, int PRE = 0, int SLAT = 0, bool MIRROR = false>
+template <int MODEL, bool HAS_UP, bool HAS_UPC, bool HAS_LATC, bool LOGF, int VEC, int PRE = 0, int SLAT = 0, bool MIRROR = false,
+          int CPACK = 0>
 __device__ __forceinline__ void sweep_body(const SweepArgs& a, const PBlock& P, const int b, const int chunk,
                                            [[maybe_unused]] const LaneJob<VEC>* pj = nullptr,
                                            [[maybe_unused]] const RowData<VEC>* pre = nullptr) {
     constexpr int NACC = Layout<MODEL>::NACC;
     static_assert(PRE == 0 || SLAT != 1, "the prefetched iterations of the one-launch-per-step kernel store no plane");
+    static_assert(CPACK == 0 || (PRE == 0 && !MIRROR && SLAT == 0 && VEC == 4 && HAS_UP && HAS_UPC && HAS_LATC),
+                  "the packed confidence plane: the plain five-plane float4 sweep");
     const int tid = threadIdx.x;
     HuberK hk;
     hk.a2u = a.up_scale * a.up_scale;
@@ -1014,6 +1106,8 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const PBlock& P, 
     const float* upc = HAS_UPC ? a.upc + (size_t)b * N : nullptr;
     const float* latc = HAS_LATC ? a.latc + (size_t)b * N : nullptr;
     [[maybe_unused]] float* slat_out = SLAT == 1 ? a.slat + (size_t)b * N : nullptr;
+    [[maybe_unused]] uint32_t* cpk = CPACK != 0 ? a.cpack + (size_t)b * N : nullptr;
+    [[maybe_unused]] bool cp_bad = false;
 
     using L = Lane<VEC>;
     using F = typename L::F;
@@ -1082,12 +1176,15 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const PBlock& P, 
             }
         } else
         for (; y < y_end; y += a.rpi, off += off_step) {
-            const RowData<VEC> r = load_row<HAS_UP, HAS_UPC, HAS_LATC, VEC>(upx, upy, lat, upc, latc, off);
+            const RowData<VEC> r = load_row<HAS_UP, HAS_UPC, HAS_LATC, VEC, CPACK>(upx, upy, lat, upc, latc, off, cpk);
             // keep every load of the iteration ahead of the math: left alone, the scheduler sinks loads next to
             // their first use to save registers in some instantiations (load -> wait -> use, five times over)
             __builtin_amdgcn_sched_barrier(0);
-            row_math<MODEL, HAS_UP, LOGF, VEC, SLAT>(P, hk, col_u, col_px, y, r, acc, col_zero, div_k_tiny, slat_out, off);
+            row_math<MODEL, HAS_UP, LOGF, VEC, SLAT, CPACK>(P, hk, col_u, col_px, y, r, acc, col_zero, div_k_tiny, slat_out, off,
+                                                            cpk, &cp_bad);
         }
+        // the fill met a confidence the packed format cannot hold: this image's later sweeps read the caller's planes
+        if constexpr (CPACK == 1) { if (cp_bad) atomicOr(a.cpack_flags + b, 1u); }
     }
 
     // wave64 DPP sum, then the 4 waves through LDS; one record per workgroup
@@ -1120,6 +1217,25 @@ __global__ __launch_bounds__(kBlock, MIRROR ? (MODEL == GCLM_RADIAL && LOGF ? GC
     const int b = blockIdx.y, chunk = blockIdx.x;
     const PBlock P = a.pb[b];                            // workgroup-uniform -> scalar loads
     sweep_body<MODEL, HAS_UP, HAS_UPC, HAS_LATC, LOGF, VEC, 0, SLAT, MIRROR>(a, P, b, chunk);
+}
+
+// The sweeps of a pinhole solve that keeps its confidences packed (row_math: CPACK = 1 fills the plane, 2 reads it): the plain
+// five-plane float4 sweep, a kernel of its own name so that sweep_kernel's instantiation set stays what it was.  Held to 96
+// VGPRs: the fill holds both the floats and their words, the reader also carries the five-plane loop of the flagged images and
+// would spill 8 B at 80.
+template <bool LOGF, int CPACK>
+__global__ __launch_bounds__(kBlock, 5) void conf_pack_sweep_kernel(const SweepArgs a) {
+    if (stop_fired_before(a.ctrl, a.stop_step)) return;
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const PBlock P = a.pb[b];
+    if constexpr (CPACK == 2) {
+        // an image whose confidences the plane does not hold (its flag: one scalar load, workgroup-uniform) reads the caller's planes
+        if (a.cpack_flags[b] != 0) {
+            sweep_body<GCLM_PINHOLE, true, true, true, LOGF, 4, 0, 0, false, 0>(a, P, b, chunk);
+            return;
+        }
+    }
+    sweep_body<GCLM_PINHOLE, true, true, true, LOGF, 4, 0, 0, false, CPACK>(a, P, b, chunk);
 }
 
 // ONE launch per LM step for small batches (the interactive B = 1 case of the reference's demo, interactive_demo.py:403):
@@ -1271,7 +1387,7 @@ __global__ __launch_bounds__(kBlock) void fused_step_kernel(const SweepArgs a, c
             }
             if (threadIdx.x == 0) {
                 fin = init_state(c, f.ia, b);
-                if (chunk == 0) c.state[0][b] = fin;
+                if (chunk == 0) { c.state[0][b] = fin; c.cpack_flags[b] = 0; }
             }
         } else if (threadIdx.x == 0) {
             fin = c.state[stop_j > 0 ? (stop_j & 1) : 0][b];           // an earlier stop's theta_j, or theta_0 (num_steps == 0)
@@ -1416,17 +1532,20 @@ __global__ void huber_costs_kernel(const float* residual, size_t n, int dim, flo
 // ---- which kernels exist ----------------------------------------------------------------------------------------------
 // The instantiation set of sweep_kernel, stated once: launch_sweep instantiates and launches exactly the kernels for which
 // this holds, and answers hipErrorInvalidValue for every other combination of run-time flags (the host's own choices,
-// gclm_api.hip: make_plan, are answered from it too -- sweep_has_mirror, sweep_has_slat_plane).  22 kernels per model, and
-// the 6 row-pair walkers each of radial and simple_divisional.
+// gclm_api.hip: make_plan, are answered from it too -- sweep_has_mirror, sweep_has_slat_plane, sweep_has_conf_pack).  22 kernels
+// per model, the 6 row-pair walkers each of radial and simple_divisional, and pinhole's 4 packed-confidence kernels.
 //   * an up confidence needs an up field;
 //   * the scalar path (VEC = 1) is the odd-shape fallback: general focal only, no plane, no row pairs;
 //   * the sin(latitude) scratch plane (row_math: SLAT = 1 fills it, 2 reads it) exists for the five-plane float4 sweep of
 //     every model.  Pinhole has these instantiations too: never the built-in choice (memory-bound), only
 //     gclm_set_slat_plane(h, 1) launches them (measurement);
-//   * row pairs (sweep_body: MIRROR): the five-plane float4 sweeps of radial / simple_divisional, with every SLAT.
-constexpr bool sweep_exists(int model, bool up, bool upc, bool latc, bool logf, int vec, int slat, bool mirror) {
+//   * row pairs (sweep_body: MIRROR): the five-plane float4 sweeps of radial / simple_divisional, with every SLAT;
+//   * the packed confidence plane (row_math: CPACK = 1 fills it, 2 reads it): pinhole's plain five-plane float4 sweep, in
+//     both focal forms (the 4 instantiations of conf_pack_sweep_kernel).
+constexpr bool sweep_exists(int model, bool up, bool upc, bool latc, bool logf, int vec, int slat, bool mirror, int cpack = 0) {
     const bool five = up && upc && latc;
     if (model < GCLM_PINHOLE || model > GCLM_SIMPLE_DIVISIONAL || (upc && !up) || slat < 0 || slat > 2) return false;
+    if (cpack != 0) return (cpack == 1 || cpack == 2) && model == GCLM_PINHOLE && five && vec == 4 && slat == 0 && !mirror;
     if (vec != 4) return vec == 1 && !logf && slat == 0 && !mirror;
     if (mirror) return five && (model == GCLM_RADIAL || model == GCLM_SIMPLE_DIVISIONAL);
     return slat == 0 || five;
@@ -1444,6 +1563,7 @@ constexpr int kMirrorBuiltinModels = (1 << GCLM_RADIAL) | (1 << GCLM_SIMPLE_DIVI
 
 // Run-time flags become template arguments, in the idiom of with_camera_model: with_flags(f, b0, b1, ...) calls
 // f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...), with_slat_mode hands std::integral_constant<int, 0 | 1 | 2>
+// (the plane modes: SLAT, and CPACK likewise)
 template <typename F>
 hipError_t with_flags(F&& f) { return f(); }
 template <typename F, typename... Bools>
@@ -1467,26 +1587,31 @@ hipError_t launch_sweep(int camera_model, const SweepArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     // what no template argument says: a plane mode needs its plane, row pairs an even number of rows cut in halves
     if ((a.slat_mode != 0 && a.slat == nullptr) || (a.mirror != 0 && ((a.H & 1) || a.hrows * 2 != a.H))) return hipErrorInvalidValue;
+    if (a.cpack_mode != 0 && (a.cpack == nullptr || a.cpack_flags == nullptr)) return hipErrorInvalidValue;
     const dim3 grid(a.nchunks, a.B), block(kBlock);
     const bool up = a.up != nullptr, vec4 = a.vec == 4;
     // the log-focal specialisation only for the vector path (the scalar path is the odd-shape fallback)
     return with_camera_model(camera_model, [&](auto m) {
         return with_slat_mode(a.slat_mode, [&](auto sl) {
+          return with_slat_mode(a.cpack_mode, [&](auto cp) {
             return with_flags([&](auto u, auto uc, auto lc, auto lf, auto v4, auto mir) {
                 constexpr int MODEL = decltype(m)::value, SLAT = decltype(sl)::value, VEC = decltype(v4)::value ? 4 : 1;
+                constexpr int CPACK = decltype(cp)::value;
                 constexpr bool U = decltype(u)::value, UC = decltype(uc)::value, LC = decltype(lc)::value,
                                LOGF = decltype(lf)::value, MIRROR = decltype(mir)::value;
-                if constexpr (sweep_exists(MODEL, U, UC, LC, LOGF, VEC, SLAT, MIRROR)) {
+                if constexpr (sweep_exists(MODEL, U, UC, LC, LOGF, VEC, SLAT, MIRROR, CPACK)) {
                     // an occupancy cap by LDS reservation for the memory-bound model (GCLM_PINHOLE_LDS above) on its plain
                     // float4 sweeps.  Pinhole's plane launches (measurement only, see sweep_exists) do not get the cap.
                     constexpr unsigned lds = (MODEL == GCLM_PINHOLE && VEC == 4 && SLAT == 0 && !MIRROR && GCLM_DYN_LDS == 0)
-                                                 ? GCLM_PINHOLE_LDS : GCLM_DYN_LDS;
-                    hipLaunchKernelGGL((sweep_kernel<MODEL, U, UC, LC, LOGF, VEC, SLAT, MIRROR>), grid, block, lds, s, a);
+                                                 ? (CPACK == 2 ? GCLM_CPACK_LDS : GCLM_PINHOLE_LDS) : GCLM_DYN_LDS;
+                    if constexpr (CPACK != 0) hipLaunchKernelGGL((conf_pack_sweep_kernel<LOGF, CPACK>), grid, block, lds, s, a);
+                    else hipLaunchKernelGGL((sweep_kernel<MODEL, U, UC, LC, LOGF, VEC, SLAT, MIRROR>), grid, block, lds, s, a);
                     return hipGetLastError();
                 } else {
                     return hipErrorInvalidValue;
                 }
             }, up, up && a.upc != nullptr, a.latc != nullptr, vec4 && a.log_focal != 0, vec4, a.mirror != 0);
+          });
         });
     });
 }
@@ -1494,6 +1619,7 @@ hipError_t launch_sweep(int camera_model, const SweepArgs& a, hipStream_t s) {
 bool sweep_has_mirror(int camera_model) { return sweep_exists(camera_model, true, true, true, true, 4, 0, true); }
 bool sweep_mirror_builtin(int camera_model) { return sweep_has_mirror(camera_model) && ((kMirrorBuiltinModels >> camera_model) & 1) != 0; }
 bool sweep_has_slat_plane(int camera_model) { return sweep_exists(camera_model, true, true, true, true, 4, 1, false); }
+bool sweep_has_conf_pack(int camera_model) { return sweep_exists(camera_model, true, true, true, true, 4, 0, false, 1); }
 
 hipError_t launch_fused_step(int camera_model, const SweepArgs& a, const FusedArgs& f, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;

@@ -60,6 +60,7 @@ __global__ void init_kernel(SolveCtx c, InitArgs ia) {
         for (int i = 0; i < GCLM_MAX_STEPS + 4; ++i) c.ctrl->notclose[i] = 0;
     }
     if (b >= c.B) return;
+    c.cpack_flags[b] = 0;
     const State s = init_state(c, ia, b);
     c.state[0][b] = s;
     PBlock p;

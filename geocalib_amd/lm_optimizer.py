@@ -60,6 +60,7 @@ class _Handle:
         self.device = cfg.device
         self.paced = 0
         self.row_pairs = -1
+        self.conf_pack = -1
         self.signature = None           # LMOptimizer._config_signature the handle was last configured for
 
     def set_paced(self, depth: int):
@@ -71,6 +72,11 @@ class _Handle:
         if mode != self.row_pairs:
             _call.call("gclm_set_row_pairs", self.ptr, int(mode), handle=self.ptr)
             self.row_pairs = mode
+
+    def set_conf_pack(self, mode: int):
+        if mode != self.conf_pack:
+            _call.call("gclm_set_conf_pack", self.ptr, int(mode), handle=self.ptr)
+            self.conf_pack = mode
 
     def destroy(self):
         if self.ptr:
@@ -277,6 +283,12 @@ class LMOptimizer(nn.Module):
     # simple_divisional images); False: never -- the one-row walk, bit for bit; True: wherever the sweep can (small launches too).
     row_pairs = None
 
+    # Host-side knob without a reference counterpart (include/gclm.h: gclm_set_conf_pack).  A pinhole batch may keep its two
+    # confidence planes as one library-owned plane of 16-bit pairs after its first sweep (16 instead of 20 bytes read per pixel
+    # and sweep; results move by what float32 rounding inside the solve does).  None: the library decides (large batches only);
+    # False: never -- the unpacked solve, bit for bit; True: wherever the sweep can.
+    conf_pack = None
+
     def _handle(self, device: torch.device, stream: int = None) -> _Handle:
         """The gclm_handle of (device, stream): solves issued from different torch streams (e.g. the CNN of batch k+1
         overlapping the LM of batch k) get different workspaces; the same stream reuses its own, in order."""
@@ -301,6 +313,7 @@ class LMOptimizer(nn.Module):
         self._handles[key] = h            # most recently used last
         h.set_paced(int(self.paced_launches))
         h.set_row_pairs(-1 if self.row_pairs is None else int(bool(self.row_pairs)))
+        h.set_conf_pack(-1 if self.conf_pack is None else int(bool(self.conf_pack)))
         return h
 
     def _fields(self, data):
@@ -538,12 +551,24 @@ class LMOptimizer(nn.Module):
         def part(t, lo, hi):
             return None if t is None else t[lo:hi]
 
+        # the parts take the WHOLE batch's decision on packing the confidences (the library says which: gclm_plan_conf_pack),
+        # so that they compute what the single call computes
+        pack = self.conf_pack
+        if pack is None:
+            five = all(t is not None for t in fields[:4])
+            aligned = all(t is None or t.data_ptr() % 16 == 0 for t in fields[:4])
+            whole, planned = self._handle(device), _lib.C.c_int(0)
+            _call.call("gclm_plan_conf_pack", whole.ptr, B, H, W, int(aligned), int(five), int(self.num_steps) + 1,
+                       _lib.C.byref(planned), handle=whole.ptr)
+            pack = planned.value == 1
         handles = []
         for i in range(n):
             lo, hi = bounds[i], bounds[i + 1]
             s = streams[i]
             s.wait_event(fork)                              # the caller's stream produced the fields
             h = self._handle(device, s.cuda_stream)
+            _call.call("gclm_set_conf_pack", h.ptr, int(bool(pack)), handle=h.ptr)
+            h.conf_pack = int(bool(pack))                   # (what _Handle.set_conf_pack remembers)
             up, lat, upc, latc, slat = (part(t, lo, hi) for t in fields)
             pf, pg, pd = (part(t, lo, hi) for t in priors)
             cam, grav, info = (t[lo:hi] for t in outs)

@@ -48,7 +48,8 @@ extern "C" {
  * epilogue can write a plane of sin(latitude) that the solve reads, every existing entry point unchanged; gclm_undistort_image,
  * gclm_render_from_pano and gclm_perspective_fields added, also within 610; gclm_field_errors and
  * gclm_field_errors_workspace added, also within 610; gclm_hypothesis_scores and gclm_hypothesis_scores_workspace added, also
- * within 610).  gclm_create refuses a gclm_config whose first two fields do not
+ * within 610; gclm_set_conf_pack, gclm_plan_conf_pack, gclm_conf_pack_bytes and gclm_conf_pack_fallbacks added, also within 610: large pinhole
+ * batches keep their two confidence planes as one plane of 16-bit pairs, see gclm_set_conf_pack).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -148,7 +149,7 @@ const char* gclm_last_error(const gclm_handle* h);
 
 /* Bytes of device scratch the handle holds (grows on demand in gclm_solve, never per call after warm-up): the core
  * workspace (per-image states, parameter blocks, partial records: ~3 KB per image) plus the sin(latitude) scratch plane
- * where one is held (gclm_slat_plane_bytes: H x W x 4 bytes per image). */
+ * and the packed confidence plane where one is held (gclm_slat_plane_bytes, gclm_conf_pack_bytes: H x W x 4 bytes per image each). */
 size_t gclm_workspace_bytes(const gclm_handle* h);
 size_t gclm_slat_plane_bytes(const gclm_handle* h);
 /* Give the handle's device memory back (hipFree: waits for the device, so nothing of the handle is in flight after).  The
@@ -594,13 +595,43 @@ int gclm_plan_cut(const gclm_handle* h, int B, int H, int W, int aligned16, int*
  * fails, or when the plane would exceed the limit.  gclm_set_slat_plane_limit: max_bytes = 0 (default) = the built-in rule,
  * at most HALF of the device memory that is free when the plane is (re)allocated; otherwise a plane is only (re)allocated
  * while B x H x W x 4 <= max_bytes (1 = in effect never; a plane the handle already holds keeps serving the solves it is
- * large enough for -- gclm_release_workspace drops it).  A refused size is remembered until the limit or the mode is set again,
+ * large enough for -- gclm_release_workspace drops it; a larger plane replaces it only once that allocation has succeeded).  A
+ * refused size is remembered until the limit or the mode is set again, or 64 further solves have wanted it,
  * so a serving loop does not pay a failing allocation per call.  Only the core workspace failing to allocate is an error
  * (-10).  A batch solved as n parts by n handles (LMOptimizer.overlap_streams) holds n planes of B / n images each: one
  * plane's worth in total.
  * A solve handed the caller's plane (gclm_solve_ex ...) where its sweeps read it needs no scratch plane, in every mode. */
 int gclm_set_slat_plane(gclm_handle* h, int mode);
 int gclm_set_slat_plane_limit(gclm_handle* h, size_t max_bytes);
+
+/* Pinhole's batch sweep is bound by the bytes it reads: five float32 planes, 20 bytes per pixel, num_steps + 1 times.  The two
+ * confidence planes compress for free: as 16-bit fixed point they move a solve by what float32 rounding inside it does (focal
+ * 5e-7 relative, gravity 1e-7, final cost 5e-7 over 64 images of 48x64).  The first sweep of a pinhole solve can
+ * therefore pack them into a LIBRARY-owned plane of one 32-bit word per pixel and every later sweep reads that plane in
+ * their place: 16 bytes per pixel.  The caller's boundary (two float32 planes) does not change.  Format, on float32 values:
+ *   q = rint(c * 65535) (round half to even), word = q_up | q_lat << 16, c' = float(q) * (1.0f / 65535.0f).
+ * The first sweep evaluates every pixel with c' as well, so all sweeps of a solve see one objective, and a solve whose
+ * confidences are already c' of some q returns the bits of the unpacked solve.
+ * A confidence outside [0, 1], or a NaN, is never clamped: the first sweep evaluates that pixel with its own value and raises a
+ * per-image flag on the device; every later sweep of a flagged image reads the caller's two planes (no host round trip).  Such
+ * an image's first sweep uses c' for its in-range confidences and its later sweeps use c: a difference at the 1e-7 level.
+ * mode -1 (default): the library decides (pinhole with all five planes on the 16-byte-aligned path, not the
+ * one-launch-per-step path, no plane of sin(latitude) in use, at least 6 sweeps and B x H x W of at least 256 Mi pixels -- 874
+ * images of 640x480; the plane pays from the smallest size measured, 32 Mi pixels, but below the threshold the sweeps' launch
+ * time over the caller's five planes stays a true HBM rate, which the benchmark's records of such batches state); 0: never; 1: wherever the sweep has the instantiation (any batch size, 2 sweeps).
+ * Sessions of gclm_shared_begin never pack.
+ * The plane is B x H x W x 4 bytes, an optional allocation of its own under the rules of the sin(latitude) plane above
+ * (gclm_set_slat_plane_limit governs both; a solve that cannot have it runs unpacked, never an error), refilled by every solve.
+ * gclm_conf_pack_bytes: bytes of the plane the handle holds.  gclm_conf_pack_fallbacks: the number of flagged images of the
+ * handle's last solve (0 if it did not pack) -- it SYNCHRONISES the device: for tests and diagnosis only. */
+int gclm_set_conf_pack(gclm_handle* h, int mode);
+/* *pack = would this handle's next solve of B images of (H, W) with `sweeps` sweeps (num_steps + 1) pack its confidences (1)
+ * or not (0), memory permitting?  (`aligned16`: all field pointers 16-byte aligned; `five_planes`: a complete field set.)  For a caller that solves ONE batch in several parts and wants every part to take the
+ * whole batch's decision (LMOptimizer.overlap_streams asks here and sets the parts' mode, instead of mirroring the rule).  No
+ * device work, no error message: -1 for a NULL handle or pointer, -3 for a non-positive B, H or W. */
+int gclm_plan_conf_pack(const gclm_handle* h, int B, int H, int W, int aligned16, int five_planes, int sweeps, int* pack);
+size_t gclm_conf_pack_bytes(const gclm_handle* h);
+int gclm_conf_pack_fallbacks(gclm_handle* h, int* n);
 
 /* Row pairs (radial / simple_divisional).  Everything a radial camera model adds to the per-pixel work depends on
  * r2 = u^2 + v^2 only.  The principal point of every camera the library initialises is the image centre (camera.py:136-152),

@@ -1,12 +1,14 @@
 """Instruction statistics of the sweep kernel's main loop (run in the build container: hipcc cross-compiles).
 
-usage: python scripts/isa_stats.py [--json OUT] [--dump SYMBOL_SUBSTRING] [--slat 0|1|2] [--mirror 0|1] [MODEL ...]
+usage: python scripts/isa_stats.py [--json OUT] [--dump SYMBOL_SUBSTRING] [--slat 0|1|2] [--mirror 0|1] [--cpack 0|1|2] [MODEL ...]
        MODEL in {0 pinhole, 1 simple_radial, 2 radial, 3 simple_divisional}; default: all four.
 Looks at the instantiation sweep_kernel<MODEL, HAS_UP=1, HAS_UPC=1, HAS_LATC=1, LOGF=1, VEC=4> (the loop sweep of the
 default conf with both confidences: what bench.py runs) by its mangled template arguments, independent of how many
 template parameters precede / follow them; --slat picks the SLAT instantiation (0: sin(latitude) computed per sweep, 1: computed
 and stored into the scratch plane = the first sweep of a solve, 2: loaded from it = every later sweep; gclm_pass.hip: row_math).
 --mirror 1 picks the row-pair walker (radial / simple_divisional: one loop iteration = two rows = 8 pixels per lane).
+--cpack picks pinhole's packed-confidence instantiation (1: the first sweep, which fills the plane; 2: every later sweep, which
+reads it -- that kernel also holds the five-plane loop of the flagged images: the loop with fewer loads is counted).
 EXTRA="-D..." adds compile flags (A/B switches of gclm_pass.hip)."""
 import collections
 import json
@@ -34,7 +36,10 @@ def main():
     mirror = 0
     if "--mirror" in args:
         i = args.index("--mirror"); mirror = int(args[i + 1]); del args[i:i + 2]
-    models = [int(a) for a in args] or [0, 1, 2, 3]
+    cpack = 0
+    if "--cpack" in args:
+        i = args.index("--cpack"); cpack = int(args[i + 1]); del args[i:i + 2]
+    models = [int(a) for a in args] or ([0] if cpack else [0, 1, 2, 3])
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast-honor-pragmas",
                     "-fno-slp-vectorize", *os.environ.get("PASS_BASE_EXTRA", "-mllvm -disable-vector-combine").split(), *os.environ.get("EXTRA", "").split(), "-S", "--cuda-device-only", "-o", asm, src],
                    check=True, capture_output=True)
@@ -43,6 +48,8 @@ def main():
     for m_id in models:
         # sweep_kernel<MODEL, true, true, true, true(LOGF), 4(VEC)>
         pat = r"^(_ZN4gclm\S*sweep_kernelILi%dELb1ELb1ELb1ELb1ELi4ELi%dELb%dE\S*):\s*;.*?\n(.*?)\.amdhsa_kernel" % (m_id, slat, mirror)
+        if cpack:       # conf_pack_sweep_kernel<LOGF = true, CPACK>
+            pat = r"^(_ZN4gclm\S*conf_pack_sweep_kernelILb1ELi%dE\S*):\s*;.*?\n(.*?)\.amdhsa_kernel" % cpack
         m = re.search(pat, text, re.S | re.M)
         if not m:
             print(f"model {m_id}: instantiation not found (template signature changed?)")
@@ -58,6 +65,8 @@ def main():
         # common one is the loop with fewer v_cndmask; every other model has one big loop
         bigloops = [t for t in loops if t[1] - t[0] > 100] or loops
         a, b = min(bigloops, key=lambda t: sum("v_cndmask" in l for l in body[t[0]:t[1] + 1]))
+        if cpack == 2:  # two row loops: the five-plane one of a flagged image, and the hot one with four loads
+            a, b = min(bigloops, key=lambda t: sum(1 for l in body[t[0]:t[1] + 1] if l.startswith("\tglobal_load")))
         if mirror:      # three row loops (unshared first iteration is straight-line; unshared loop; shared loop): the hot one is the shortest
             a, b = min(bigloops, key=lambda t: sum(1 for l in body[t[0]:t[1] + 1] if l.startswith("\tv_")))
         other_loops = [sum(1 for l in body[t[0]:t[1] + 1] if l.startswith("\tv_")) for t in bigloops if t != (a, b)]
@@ -102,7 +111,7 @@ def main():
             print("\n".join(body[a:b + 1]))
     if out_json:
         with open(out_json, "w") as fh:
-            json.dump({"kernel": f"gclm::sweep_kernel<MODEL, up, up_conf, lat_conf, log-focal, float4, SLAT={slat}>", "flags": os.environ.get("EXTRA", ""),
+            json.dump({"kernel": f"gclm::sweep_kernel<MODEL, up, up_conf, lat_conf, log-focal, float4, SLAT={slat}, MIRROR={mirror}, CPACK={cpack}>", "flags": os.environ.get("EXTRA", ""),
                        "models": results}, fh, indent=1)
 
 
