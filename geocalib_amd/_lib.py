@@ -17,6 +17,8 @@ SHARED_PARTIAL_STRIDE = 32
 COMM_ID_BYTES = 128
 MAX_PARAMS = 5
 MAX_RECALL_THRESHOLDS = 8
+RPF_MAX_SAMPLES = 1 << 24     # GCLM_RPF_MAX_SAMPLES: samples per image of one gclm_rpf_hypotheses call
+RPF_DRAW_SALT = 0x5250465F44524157     # GCLM_RPF_DRAW_SALT: what the in-kernel draw of gclm_rpf_hypotheses mixes into the seed
 HYPOTHESIS_CHUNK = 16         # GCLM_HYPOTHESIS_CHUNK: hypotheses scored per read of an image's planes (gclm_hypothesis_scores)
 ABI_VERSION = 610          # GCLM_VERSION of include/gclm.h this binding was written against
 INFO = {"stop_at": 0, "initial_up_cost": 1, "initial_latitude_cost": 2, "initial_cost": 3,
@@ -96,6 +98,7 @@ _SIGNATURES = {
     "gclm_hypothesis_scores_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gclm_hypothesis_scores": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_float,
                                          C.c_float, C.c_float, _P, C.c_size_t, _P, _P, _P]),
+    "gclm_rpf_hypotheses": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gclm_pack_fields": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "gclm_pack_fields_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gclm_synth_fields": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,

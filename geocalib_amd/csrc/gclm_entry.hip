@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the three render kernels, the field errors, the hypothesis scores, the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the three render kernels, the field errors, the hypothesis scores, the minimal solver, the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -190,6 +190,25 @@ int gclm_hypothesis_scores(int camera_model, const float* d_cam, const float* d_
     return launched(launch_hypothesis_scores(camera_model, d_cam, d_grav, B, N, H, W, d_up, d_lat, d_up_conf, d_lat_conf, d_mask,
                                              up_threshold_deg, lat_threshold_deg, up_weight, lat_weight, d_workspace, d_scores,
                                              d_best, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_rpf_hypotheses(const float* d_up, const float* d_lat, const float* d_prior_focal, const int32_t* d_samples, uint64_t seed,
+                        int64_t first_index, int B, int N, int H, int W, float* d_cam, float* d_grav, int32_t* d_samples_out,
+                        void* stream) {
+    if (!d_up || !d_cam || !d_grav || (!d_lat && !d_prior_focal)) return -3;
+    if (B < 1 || B > kMaxCallImages || N < 1 || N > GCLM_RPF_MAX_SAMPLES || H < 1 || W < 1 || (int64_t)H * W > INT32_MAX) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W), rows = mul_sat((size_t)N, d_prior_focal ? 1 : 2);
+    a.writes(d_cam, floats(B, rows, 8), 4);
+    a.writes(d_grav, floats(B, rows, 3), 4);
+    a.writes(d_samples_out, floats(B, N, 6), 4);          // (int32: as wide as a float)
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_prior_focal, floats(B), 4);
+    a.reads(d_samples, floats(B, N, 6), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_rpf_hypotheses(d_up, d_lat, d_prior_focal, d_samples, seed, first_index, B, N, H, W, d_cam, d_grav,
+                                          d_samples_out, static_cast<hipStream_t>(stream)));
 }
 
 int gclm_render_from_pano(int camera_model, const float* d_cam, int cam_batch, const float* d_rot, const float* const* srcs,

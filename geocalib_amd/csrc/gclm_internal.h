@@ -6,7 +6,8 @@
 //  gclm_args.h, gclm_comm.hip: the communicator and its entry points; the render kernels over gclm_render.h --
 //  gclm_image.hip: image undistortion, gclm_pano.hip: panorama rendering, gclm_persp.hip: perspective fields; and
 //  gclm_metrics.hip: the errors of predicted fields against a calibration, gclm_hypotheses.hip: the scores of N candidate
-//  calibrations per image against its fields, both over the same header).  gfx950 only.
+//  calibrations per image against its fields, both over the same header; gclm_rpf.hip: the three-pixel minimal solver that
+//  makes such candidates).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -249,5 +250,10 @@ hipError_t launch_hypothesis_scores(int camera_model, const float* cam, const fl
                                     const float* up, const float* lat, const float* upc, const float* latc, const float* mask,
                                     float up_threshold, float lat_threshold, float up_weight, float lat_weight, void* workspace,
                                     float* scores, int* best /* or nullptr */, hipStream_t s);
+
+// gclm_rpf.hip
+hipError_t launch_rpf_hypotheses(const float* up, const float* lat /* or nullptr with a prior */, const float* prior_focal /* or nullptr */,
+                                 const int32_t* samples /* or nullptr: drawn */, uint64_t seed, int64_t first_index, int B, int N, int H,
+                                 int W, float* cam, float* grav, int32_t* samples_out /* or nullptr */, hipStream_t s);
 
 }  // namespace gclm

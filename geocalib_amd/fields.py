@@ -289,3 +289,37 @@ def hypothesis_scores(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, 
                    at(planes["mask"], b0), float(up_threshold), float(lat_threshold), float(up_weight), float(lat_weight),
                    ws.data_ptr(), ws_bytes, scores[b0].data_ptr(), best[b0].data_ptr(), _call.raw_stream(dev), device=dev)
     return scores, best
+
+
+def rpf_hypotheses(up: torch.Tensor, lat: Optional[torch.Tensor] = None, prior_focal: Optional[torch.Tensor] = None,
+                   samples: Optional[torch.Tensor] = None, n: int = 1000, seed: int = 0, first_index: int = 0):
+    """gclm_rpf_hypotheses: the three-pixel minimal solver on `up` (B, 2, H, W) and `lat` (B, 1, H, W) -- or `prior_focal`
+    (B,) in its place --, float32 on one HIP device, one launch per 65 535 images on torch's current stream.  `samples`
+    (B, N, 3, 2) int32 pixels (x, y) on the same device, or None: `n` per image are drawn in the kernel from (seed,
+    first_index + b, sample, pixel).  Returns (cam (B, N Rn, 8), grav (B, N Rn, 3), samples (B, N, 3, 2) as used), Rn = 1 with
+    a prior focal and 2 without; invalid rows are NaN.  ransac.solve_rpf is the public entry; not differentiable."""
+    if lat is None and prior_focal is None:
+        raise ValueError("the focal length needs the latitude field or a prior focal")
+    up = _call.dev_f32(up, "up")
+    dev, (B, _, H, W) = up.device, up.shape
+    lat = None if lat is None or prior_focal is not None else _call.dev_f32(lat, "lat")
+    prior = None if prior_focal is None else _call.dev_f32(prior_focal, "prior_focal").reshape(-1)
+    if up.shape[1] != 2 or (lat is not None and (lat.numel() != B * H * W or lat.device != dev)) or \
+            (prior is not None and (prior.numel() != B or prior.device != dev)):
+        raise ValueError(f"`up` {tuple(up.shape)} must be (B, 2, H, W), with `lat` of B H W or `prior_focal` of B values on {dev}")
+    if samples is not None:
+        _call.require_device(samples, "samples")
+        if samples.dtype != torch.int32 or samples.shape[0] != B or samples.shape[2:] != (3, 2) or samples.device != dev:
+            raise ValueError(f"`samples` {tuple(samples.shape)} {samples.dtype} must be (B, N, 3, 2) int32 on {dev}")
+        samples, n = samples.contiguous(), samples.shape[1]
+    n, Rn = int(n), 1 if prior is not None else 2
+    if not 1 <= n <= _lib.RPF_MAX_SAMPLES:
+        raise ValueError(f"samples per image must lie in 1..{_lib.RPF_MAX_SAMPLES} (got {n})")
+    cam, grav = up.new_empty((B, n * Rn, 8)), up.new_empty((B, n * Rn, 3))
+    drawn = torch.empty((B, n, 3, 2), dtype=torch.int32, device=dev) if samples is None else None
+    at = lambda t, b0: None if t is None else t[b0].data_ptr()  # noqa: E731
+    for b0, m in _call.slices(B):
+        _call.call("gclm_rpf_hypotheses", up[b0].data_ptr(), at(lat, b0), None if prior is None else prior[b0:].data_ptr(),
+                   at(samples, b0), int(seed) & (2 ** 64 - 1), int(first_index) + b0, m, n, H, W, cam[b0].data_ptr(), grav[b0].data_ptr(),
+                   at(drawn, b0), _call.raw_stream(dev), device=dev)
+    return cam, grav, samples if samples is not None else drawn

@@ -172,7 +172,9 @@ class LMOptimizer(nn.Module):
         "group_size": None,
         # knobs of the training-time optimiser (siclib/models/optimization/lm_optimizer.py:37-59)
         "loss_fn": "huber_loss",          # {"huber_loss", "squared_loss"}
-        "init_conf": {"name": "trivial"},  # {"trivial", "heuristic"} (siclib/models/optimization/utils.py:16-82)
+        # {"trivial", "heuristic"} (siclib/models/optimization/utils.py:16-82), or {"name": "ransac", ...RPFSolver conf}: the
+        # estimate of ransac.RPFSolver, which does not depend on a fixed starting point
+        "init_conf": {"name": "trivial"},
     }
 
     # squared_loss (siclib/models/optimization/losses.py:26) is the Huber loss with an unreachable threshold:
@@ -189,6 +191,10 @@ class LMOptimizer(nn.Module):
         self.num_steps = conf.num_steps
         self.set_camera_model(conf.camera_model)
         self.setup_optimization_and_priors(shared_intrinsics=conf.shared_intrinsics)
+        if self._init_name == "ransac":        # its conf errors (error_fn, n_iter, unknown keys) surface here
+            from .ransac import RPFSolver
+            c = conf.init_conf
+            self.ransac = RPFSolver({k: v for k, v in (c.items() if isinstance(c, dict) else vars(c).items()) if k != "name"})
         self._handles: Dict[Tuple[int, int], _Handle] = {}
         self._warned_training = False
         self._warned_chunked_stop = False
@@ -261,7 +267,7 @@ class LMOptimizer(nn.Module):
         squared = c.loss_fn == "squared_loss"
         cfg.up_loss_fn_scale = self._SQUARED_LOSS_SCALE if squared else float(c.up_loss_fn_scale)
         cfg.lat_loss_fn_scale = self._SQUARED_LOSS_SCALE if squared else float(c.lat_loss_fn_scale)
-        assert self._init_name in ("trivial", "heuristic"), f"Unknown initialisation: {self._init_name}"
+        assert self._init_name in ("trivial", "heuristic", "ransac"), f"Unknown initialisation: {self._init_name}"
         cfg.heuristic_init = int(self._init_name == "heuristic")
         cfg.estimate_gravity = int(self.estimate_gravity)
         cfg.estimate_focal = int(self.estimate_focal)
@@ -394,8 +400,34 @@ class LMOptimizer(nn.Module):
             self.setup_optimization_and_priors(data, shared_intrinsics=self.shared_intrinsics)
             if self.conf.verbose:
                 return self._forward_verbose(data)
-            camera_opt, gravity_opt, infos = self.calibrate_fields(data)
+            camera_opt, gravity_opt, infos = self._calibrate(data)
         return {"camera": camera_opt, "gravity": gravity_opt, **infos}
+
+    def _calibrate(self, data):
+        """The solve of `forward`: from the library's own initial estimate, or from the RANSAC estimate."""
+        return self._calibrate_from_ransac(data) if self._init_name == "ransac" else self.calibrate_fields(data)
+
+    def _calibrate_from_ransac(self, data: Dict[str, torch.Tensor]) -> Tuple[BaseCamera, Gravity, Dict[str, torch.Tensor]]:
+        """init_conf {"name": "ransac", ...}: ransac.RPFSolver's estimate (the other keys of init_conf are its conf) handed
+        to `optimize`.  Distortion starts at 0, fx takes the aspect of `scales` as the trivial estimate's does, a prior
+        focal length is the solver's too."""
+        for key, why in (("prior_gravity", "the minimal solver estimates the gravity itself"),
+                         ("prior_dist", "the minimal solver is a pinhole solver: its estimate has no distortion to hold fixed")):
+            if key in data:
+                raise ValueError(f"init_conf ransac cannot be combined with `{key}`: {why}")
+        if self.shared_intrinsics:
+            raise ValueError("init_conf ransac cannot be combined with shared_intrinsics: the minimal solver estimates one focal "
+                             "length per image")
+        if "up_field" not in data:
+            raise ValueError("init_conf ransac needs an `up_field`: two up vectors give the vanishing point")
+        if data["latitude_field"].shape[0] > self._MAX_CALL:
+            raise ValueError(f"init_conf ransac is limited to {self._MAX_CALL} images per call")
+        est = self.ransac(data)
+        cam = est["camera_opt"]._data.to(torch.float32).clone()
+        if "scales" in data:
+            s = torch.as_tensor(data["scales"], dtype=torch.float32, device=cam.device).reshape(-1)
+            cam[:, 2] = cam[:, 2] * s[0] / s[1]
+        return self.optimize(data, self.camera_model(cam), est["gravity_opt"])
 
     def _forward_verbose(self, data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """conf.verbose (lm_optimizer.py:652-662): the reference's five log lines.  Its timing is a host wall clock around
@@ -406,7 +438,7 @@ class LMOptimizer(nn.Module):
         camera_init, gravity_init = get_trivial_estimation(data, self.camera_model)
         torch.cuda.synchronize(device)
         start = time.time()
-        camera_opt, gravity_opt, infos = self.calibrate_fields(data)
+        camera_opt, gravity_opt, infos = self._calibrate(data)
         torch.cuda.synchronize(device)
         logger.info(f"Optimization took {(time.time() - start) * 1000:.2f} ms")
         logger.info(f"Initial camera:\n{rad2deg(camera_init.vfov)}")

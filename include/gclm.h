@@ -49,7 +49,8 @@ extern "C" {
  * gclm_render_from_pano and gclm_perspective_fields added, also within 610; gclm_field_errors and
  * gclm_field_errors_workspace added, also within 610; gclm_hypothesis_scores and gclm_hypothesis_scores_workspace added, also
  * within 610; gclm_set_conf_pack, gclm_plan_conf_pack, gclm_conf_pack_bytes and gclm_conf_pack_fallbacks added, also within 610: large pinhole
- * batches keep their two confidence planes as one plane of 16-bit pairs, see gclm_set_conf_pack).  gclm_create refuses a gclm_config whose first two fields do not
+ * batches keep their two confidence planes as one plane of 16-bit pairs, see gclm_set_conf_pack; gclm_rpf_hypotheses added, also
+ * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -67,6 +68,8 @@ enum gclm_camera_model {
 #ifndef GCLM_HYPOTHESIS_CHUNK
 #define GCLM_HYPOTHESIS_CHUNK 16         /* gclm_hypothesis_scores: hypotheses scored per read of an image's planes */
 #endif
+#define GCLM_RPF_MAX_SAMPLES (1 << 24)   /* gclm_rpf_hypotheses: most samples per image of one call */
+#define GCLM_RPF_DRAW_SALT 0x5250465F44524157ull   /* gclm_rpf_hypotheses: mixed into the seed of the in-kernel draw */
 #define GCLM_CAM_STRIDE 8     /* {w,h,fx,fy,cx,cy,k1,k2}: BaseCamera._data, camera.py:25-41 */
 #define GCLM_GRAV_STRIDE 3    /* unit gravity: Gravity._data, gravity.py:18-28 */
 
@@ -411,6 +414,46 @@ int gclm_hypothesis_scores(int camera_model, const float* d_cam, const float* d_
                            const float* d_mask, float up_threshold_deg, float lat_threshold_deg, float up_weight,
                            float lat_weight, void* d_workspace, size_t workspace_bytes, float* d_scores, int* d_best,
                            void* stream);
+
+/*
+ * The three-pixel minimal solver of the reference's RANSAC baseline (siclib/models/optimization/ransac.py: MinimalSolver,
+ * RPFSolver.solve_rpf), one lane per sample: N samples per image give the N Rn candidate calibrations that
+ * gclm_hypothesis_scores ranks.  Pinhole, square pixels, principal point (c_x, c_y) = (W / 2, H / 2); integer pixel centres.
+ * d_up (B, 2, H, W) planar and d_lat (B, 1, H, W) in radians as gclm_hypothesis_scores takes them; d_prior_focal (B) or NULL;
+ * d_lat may be NULL only with d_prior_focal (the latitude is then not read).  Rn = 2 without a prior focal, 1 with one.
+ * d_samples (B, N, 3, 2) int32 = (x_k, y_k), k = 0, 1, 2, or NULL: the pixels are then drawn in the kernel (below).
+ * Per sample, all in float32, no fused multiply-adds:
+ *   1. d_k = d_up[b, :, y_k, x_k], k = 0, 1.  l_k = (-d_ky, d_kx, x_k d_ky - y_k d_kx), V = l_0 x l_1 (homogeneous, never
+ *      divided by V_z), v = (V_x - c_x V_z, V_y - c_y V_z, V_z) / |.|.
+ *   2. U = x_2 - c_x, Vp = y_2 - c_y, L = sin(d_lat[b, y_2, x_2]), R = U^2 + Vp^2, S = v_x^2 + v_y^2, D = v_x U + v_y Vp.
+ *   3. a0 = (L^2 - 1) v_z^2, a1 = L^2 (R v_z^2 + S) - 2 D v_z, a2 = L^2 R S - D^2;  q = -(a1 + sgn(a1) sqrt(a1^2 - 4 a0 a2)) / 2
+ *      (sgn(0) = 1); F_0 = a2 / q, F_1 = q / a0.  With a prior focal: the one root F_0 = prior^2.
+ *   4. Per root r: f = sqrt(F_r), g = normalize(v_x / f, v_y / f, v_z), negated if
+ *      (g_x - g_z (x_0 - c_x) / f) d_0x + (g_y - g_z (y_0 - c_y) / f) d_0y < 0: the up direction at pixel 0 decides the sign.
+ *   5. The row is valid iff f and g are finite, H / 2 / tan 75 deg <= f <= H / 2 / tan 2.5 deg (the solve's own focal
+ *      clamp, as float32 constants: H 0.5 / 3.7320504, H 0.5 / 0.043660942) and, without a prior focal,
+ *      L (g_x U / f + g_y Vp / f + g_z) >= 0 (the root that squaring introduced fails this).
+ *   6. Row n Rn + r of image b: d_cam = {W, H, f, f, W / 2, H / 2, 0, 0}, d_grav = g; an invalid row holds eleven NaNs, which
+ *      gclm_hypothesis_scores scores exactly 0.  Identical pixels 0 and 1, parallel up vectors that meet nowhere finite in
+ *      float32, a NaN among the values read and a negative discriminant all end in an invalid row, never in an error.
+ * The draw (d_samples == NULL): with mix(z) the splitmix64 finaliser -- z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31, all modulo 2^64 -- and i = first_index + b,
+ *   base = mix((seed ^ GCLM_RPF_DRAW_SALT) ^ mix(i * 0xD1342543DE82EF95 + 1)),   h = mix(base + 4 n + k),
+ *   x_k = ((h >> 32) * W) >> 32,   y_k = ((h & 0xFFFFFFFF) * H) >> 32:
+ * a function of (seed, first_index + b, n, k), W and H alone, so image b alone with first_index advanced by b draws the
+ * same pixels.  Optional d_samples_out (B, N, 3, 2) int32 receives the pixels used, drawn or given.
+ * The samples live in device memory, so the host cannot check them: a sample with a coordinate outside [0, W) x [0, H) reads
+ * nothing and leaves invalid rows (the Python package refuses such samples before the call).
+ * One launch, grid (ceil(N / 256), B); no LDS, no atomics, no workspace: the rows of sample (b, n) depend on that sample's
+ * three pixels alone, and two calls give the same bits.
+ * Returns -3 (before any HIP call) for a NULL d_up, d_cam or d_grav, a NULL d_lat without d_prior_focal, B outside 1..65535,
+ * N outside 1..GCLM_RPF_MAX_SAMPLES, H or W < 1, H * W > 2^31 - 1, a pointer that is not 4-byte aligned, or an output (d_cam,
+ * d_grav, d_samples_out) that overlaps an input or another output; -10 if the launch fails.  Asynchronous on `stream`; no
+ * allocation.
+ */
+int gclm_rpf_hypotheses(const float* d_up, const float* d_lat, const float* d_prior_focal, const int32_t* d_samples,
+                        uint64_t seed, int64_t first_index, int B, int N, int H, int W, float* d_cam, float* d_grav,
+                        int32_t* d_samples_out, void* stream);
 
 /*
  * BaseCamera.get_img_from_pano (geocalib/camera.py:414-514) for n images, in one pass: d_dst (n, C, H, W) holds image i
