@@ -6,6 +6,9 @@
 (2) `GeoCalib.calibrate(img, camera_model=..., priors=..., shared_intrinsics=...)` (geocalib/extractor.py:72-127) with a
     caller-supplied field network.
 (3) `camera.undistort_image(image)` (geocalib/camera.py:396-412), which the reference's Gradio app calls right after calibrate().
+    Its general form, `camera.upright_image(image, gravity)` and `camera.reproject_image(image, target, rotation)`, shows the
+    image as another camera sees it: the horizon levelled with the estimated gravity, a wider pinhole camera (the interactive
+    demo's padded undistortion), a clean image distorted, a virtual pan or tilt -- one gclm_reproject_image launch.
 
 The CNN is out of scope of this package, so a stand-in "network" renders the perspective fields of a known camera
 (gclm_synth_fields) at the resolution the reference's network would see; with the upstream package installed, pass its
@@ -51,6 +54,8 @@ print("with a focal prior: focal", round(res["camera"].f[0, 1].item(), 1))
 res = model.calibrate(img, camera_model="radial")
 rect = res["camera"].undistort_image(img[None])                   # (1, 3, H, W): one gclm_undistort_image launch
 print("undistort_image(): k1, k2", [round(v, 4) for v in res["camera"].dist[0].tolist()], " output", tuple(rect.shape))
+level, seen = res["camera"].upright_image(img[None], res["gravity"], return_valid=True)       # undistorted and the roll removed
+print("upright_image()  : output", tuple(level.shape), " pixels that see the source", round(seen.float().mean().item(), 3))
 
 # (4) solve one batch from three starts -- the trivial and the heuristic initialisation, and the focal length held at a guess
 #     (a prior) -- and keep, per image, the calibration that explains the fields best: one gclm_hypothesis_scores pass

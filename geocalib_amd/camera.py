@@ -6,8 +6,8 @@ SimpleRadial :565, Radial :663, SimpleDivisional :789, camera_models :945): a `(
 (un)distortion maps.  Every model here is *radial*: distort(p) = p * s(r2) and
 undistort(p) = p * t(r2) with r2 = |p|^2, so a model only supplies s, t and their derivatives
 and all Jacobians follow in closed form (the reference falls back to torch.func.jacfwd for the
-generic cases).  Host-side torch code: the per-pixel hot paths are csrc/gclm_pass.hip and, for undistort_image
-and get_img_from_pano, csrc/gclm_image.hip and csrc/gclm_pano.hip.
+generic cases).  Host-side torch code: the per-pixel hot paths are csrc/gclm_pass.hip and, for undistort_image,
+get_img_from_pano and reproject_image / upright_image, csrc/gclm_image.hip, csrc/gclm_pano.hip and csrc/gclm_reproject.hip.
 """
 from typing import Dict, Tuple, Union
 
@@ -445,8 +445,140 @@ class BaseCamera(TensorWrapper):
             images.append(F.grid_sample(resized_pano, grid.to(resized_pano), align_corners=True))
         return torch.cat(images, 0)
 
+    def reproject_image(self, img: torch.Tensor, target: "BaseCamera" = None, rotation: torch.Tensor = None,
+                        return_valid: bool = False):
+        """`img` (B, C, Hin, Win), taken with this camera, as the camera `target` sees it after turning by `rotation`:
+        (B, C, H, W) with (W, H) the target's size truncated.  Levelling a horizon (upright_image), rendering into a wider
+        or longer camera, distorting a clean image (the inverse of undistort_image) and a virtual pan or tilt are all this
+        one operation.  `self` has batch 1 or B; `target` is a camera of any of the four models, batch 1 or B, all of one
+        size (default: this camera without its distortion); `rotation` is M (3, 3), (1, 3, 3) or (B, 3, 3), None for the
+        identity.  Output pixel (x, y), integer pixel centres:
+            b = target.image2world(x, y) = (u t, v t, 1),   q = b @ M,   visible = q_z > eps (1e-3, as project())
+            p = (q_x, q_y) / q_z,  r2 = |p|^2,  (s, s') = this model's distort scale at r2 and ds/dr2
+            inside_model = s + 2 r2 s' > 0          (r s(r^2) still increases: beyond, a polynomial model folds back)
+            ix = (p_x s fx + cx) (Win - 1) / (Ws - 1),   iy = (p_y s fy + cy) (Hin - 1) / (Hs - 1)
+        with (Ws, Hs) this camera's size truncated (the image may be stored at another resolution, as for
+        undistort_image), sampled bilinearly with zero padding (F.grid_sample(bilinear, zeros, align_corners=True)); exactly
+        0 where visible or inside_model fails or a coordinate is not finite.  With `return_valid` also the (B, H, W) bool
+        mask visible & inside_model & 0 <= ix <= Win - 1 & 0 <= iy <= Hin - 1.
+
+        A float32 image on a HIP device runs one gclm_reproject_image launch (not differentiable).  Every other input (CPU,
+        other dtypes) runs a torch composition of the same definition, simple_divisional's scales in the forms that do not
+        cancel (csrc/gclm_render.h).  The method reads the device once: the two cameras' sizes, in one .tolist()."""
+        if img.dim() != 4:
+            raise ValueError(f"expected a (B, C, H, W) image, got {tuple(img.shape)}")
+        B = img.shape[0]
+        src = self._data.reshape(-1, self._data.shape[-1])
+        if target is None:
+            tgt_name, tgt = "pinhole", torch.cat([src[:, :6], torch.zeros_like(src[:, 6:])], -1)
+        elif isinstance(target, BaseCamera):
+            tgt_name, tgt = target.name(), target._data.reshape(-1, target._data.shape[-1]).to(src)
+        else:
+            raise ValueError(f"`target` must be a camera of one of the four models, got {type(target).__name__}")
+        rot = None
+        if rotation is not None:
+            if rotation.dim() not in (2, 3) or rotation.shape[-2:] != (3, 3):
+                raise ValueError(f"`rotation` must be (3, 3), (1, 3, 3) or (B, 3, 3), got {tuple(rotation.shape)}")
+            rot = rotation.to(src).reshape(-1, 3, 3)
+        for what, n in (("source camera", src.shape[0]), ("target camera", tgt.shape[0]),
+                        ("rotation", 1 if rot is None else rot.shape[0])):
+            if n not in (1, B):
+                raise ValueError(f"{what} batch {n} must be 1 or the image batch {B}")
+        ns, nt = src.shape[0], tgt.shape[0]
+        host = torch.cat([src[:, :2].reshape(-1), tgt[:, :2].reshape(-1)]).tolist()      # the one device-to-host read
+        sizes_s, sizes_t = set(zip(host[0:2 * ns:2], host[1:2 * ns:2])), set(zip(host[2 * ns::2], host[2 * ns + 1::2]))
+        assert len(sizes_s) == 1, "All source cameras must have the same size."
+        assert len(sizes_t) == 1, "All target cameras must have the same size."
+        (Ws, Hs), (W, H) = (tuple(int(v) for v in s.pop()) for s in (sizes_s, sizes_t))
+        if min(Ws, Hs) < 2 or min(W, H) < 1:
+            raise ValueError(f"source camera size {Ws} x {Hs} must be at least 2 x 2, target size {W} x {H} at least 1 x 1")
+        if ns != nt:                                                      # one batch for both cameras
+            src, tgt = src.expand(B, -1), tgt.expand(B, -1)
+        if img.is_cuda and img.dtype == torch.float32:
+            from .fields import reproject_image
+            return reproject_image(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W), return_valid)
+        out, valid = _reproject_torch(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W))
+        return (out, valid) if return_valid else out
+
+    def upright_image(self, img: torch.Tensor, gravity, level_pitch: bool = False, target: "BaseCamera" = None,
+                      return_valid: bool = False):
+        """`img` (B, C, Hin, Win) with the roll that `gravity` says the camera had removed, and with `level_pitch` the pitch
+        too (the horizon then runs through the principal point): reproject_image with M = R_t @ R_s^T, R_s = gravity.R and
+        R_t = Gravity.from_rp(0, 0 if level_pitch else gravity.pitch).R.  The gravity batch is 1 or B; `target` and
+        `return_valid` as for reproject_image."""
+        from .gravity import Gravity
+        R_s = gravity.R.reshape(-1, 3, 3)
+        pitch = gravity.pitch.reshape(-1)
+        zero = torch.zeros_like(pitch)
+        R_t = Gravity.from_rp(zero, zero if level_pitch else pitch).R.reshape(-1, 3, 3)
+        return self.reproject_image(img, target, R_t @ R_s.transpose(-1, -2), return_valid)
+
     def __repr__(self):
         return f"{self.__class__.__name__} {self.shape} {self.dtype} {self.device}"
+
+
+def _render_scales(model: str, k1: torch.Tensor, k2: torch.Tensor, r2: torch.Tensor):
+    """(t, s, s') at r2 as the render kernels evaluate them (csrc/gclm_render.h): the undistort scale, the distort scale and
+    ds/dr2, simple_divisional's in the forms that do not cancel."""
+    one, zero = torch.ones_like(r2), torch.zeros_like(r2)
+    if model == "pinhole":
+        return one, one, zero
+    if model == "simple_radial":
+        return 1 - k1 * r2, 1 + k1 * r2, k1 + zero
+    if model == "radial":
+        return 1 - k1 * r2 + (3 * k1 * k1 - k2) * (r2 * r2), 1 + (k1 + k2 * r2) * r2, k1 + 2 * k2 * r2
+    den = 1 + k1 * r2
+    t = 1 / torch.where(den == 0, 1e6 * one, den)
+    kr = k1 * r2
+    tau = 1 - 4 * kr
+    rt = torch.sqrt(tau.clamp(min=0))
+    d = 1 + rt
+    s = torch.where(tau > 0, 2 / d, 1 / torch.where(kr == 0, one, 2 * kr))
+    tt = 1e-6 ** 0.5
+    den = 2 * k1 * (r2 * r2) * tt
+    sp = torch.where(tau >= 1e-6, 4 * k1 / torch.where(tau >= 1e-6, rt * d * d, one),
+                     (2 * kr - (1 - tt) * tt) / torch.where(den == 0, 1e6 * one, den))
+    return t, torch.where(kr == 0, one, s), torch.where(kr == 0, zero, sp)
+
+
+def _reproject_torch(src_model, src, tgt_model, tgt, rot, img, src_size, size):
+    """BaseCamera.reproject_image as a torch composition: cameras (n, 8) of one batch n in {1, B}, `rot` (1 or B, 3, 3) or
+    None; returns the (B, C, H, W) image and the (B, H, W) bool mask."""
+    grid, seen, valid = _reproject_grid(src_model, src, tgt_model, tgt, rot, img.shape, src_size, size)
+    out = F.grid_sample(img, grid.to(img), mode="bilinear", padding_mode="zeros", align_corners=True)
+    return torch.where(seen[:, None].to(img.device), out, torch.zeros_like(out)), valid
+
+
+def _reproject_grid(src_model, src, tgt_model, tgt, rot, img_shape, src_size, size):
+    """The sampling grid of _reproject_torch (B, H, W, 2) in F.grid_sample's normalised coordinates, the (B, H, W) mask of
+    the pixels that sample at all (visible, inside the model, finite) and the (B, H, W) valid mask."""
+    (Hs, Ws), (H, W) = src_size, size
+    B, _, Hin, Win = img_shape
+    assert min(Hin, Win) >= 2, "the torch composition needs a source image of at least 2 x 2"
+    fxs, fys, cxs, cys, k1s, k2s = (src[:, i, None, None] for i in range(2, 8))
+    fxt, fyt, cxt, cyt, k1t, k2t = (tgt[:, i, None, None] for i in range(2, 8))
+    x = torch.arange(W, device=src.device, dtype=src.dtype)[None, None, :]
+    y = torch.arange(H, device=src.device, dtype=src.dtype)[None, :, None]
+    u, v = (x - cxt) / fxt, (y - cyt) / fyt
+    t = _render_scales(tgt_model, k1t, k2t, u * u + v * v)[0]
+    qx, qy, qz = u * t, v * t, torch.ones_like(u * t)
+    if rot is not None:
+        M = rot[:, :, :, None, None]
+        qx, qy, qz = (qx * M[:, 0, j] + qy * M[:, 1, j] + M[:, 2, j] for j in range(3))
+    ok = (qz > BaseCamera.eps) & torch.isfinite(qz)
+    iz = 1 / torch.where(ok, qz, torch.ones_like(qz))
+    px, py = qx * iz, qy * iz
+    r2 = px * px + py * py
+    _, s, sp = _render_scales(src_model, k1s, k2s, r2)
+    ok = ok & (s + 2 * r2 * sp > 0)
+    ix, iy = (px * s * fxs + cxs) * ((Win - 1) / (Ws - 1)), (py * s * fys + cys) * ((Hin - 1) / (Hs - 1))
+    ok = ok.expand(B, -1, -1)
+    ix, iy = ix.expand(B, -1, -1), iy.expand(B, -1, -1)
+    valid = ok & (ix >= 0) & (ix <= Win - 1) & (iy >= 0) & (iy <= Hin - 1)
+    seen = ok & torch.isfinite(ix) & torch.isfinite(iy)
+    outside = torch.full_like(ix, -2.0)                 # where no tap lies inside the source
+    gx, gy = torch.where(seen, ix, outside).clamp(-2, Win + 1), torch.where(seen, iy, outside).clamp(-2, Hin + 1)
+    return torch.stack([2 * gx / (Win - 1) - 1, 2 * gy / (Hin - 1) - 1], -1), seen, valid
 
 
 class Pinhole(BaseCamera):

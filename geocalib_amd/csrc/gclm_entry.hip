@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the three render kernels, the field errors, the hypothesis scores, the minimal solver, the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the four render kernels, the field errors, the hypothesis scores, the minimal solver, the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -113,6 +113,24 @@ int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, co
     if (!a.pass()) return -3;
     return launched(launch_undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, d_dst,
                                            static_cast<hipStream_t>(stream)));
+}
+
+int gclm_reproject_image(int src_model, const float* d_src_cam, int dst_model, const float* d_dst_cam, int cam_batch,
+                         const float* d_rot, int rot_batch, const float* d_src, int B, int C, int Hin, int Win, int Hs, int Ws,
+                         int H, int W, float* d_dst, unsigned char* d_valid, void* stream) {
+    if (!d_src_cam || !d_dst_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1) return -3;
+    if (H < 1 || W < 1 || Hs < 2 || Ws < 2 || !tile_grid_fits(H, W) || !known_model(src_model) || !known_model(dst_model)) return -3;
+    if ((cam_batch != 1 && cam_batch != B) || (rot_batch != 1 && rot_batch != B)) return -3;
+    ArgCheck a;
+    a.writes(d_dst, floats(B, C, H, W), 4);
+    a.writes(d_valid, mul_sat(mul_sat((size_t)B, (size_t)H), (size_t)W));
+    a.reads(d_src_cam, floats(cam_batch, 8), 4);
+    a.reads(d_dst_cam, floats(cam_batch, 8), 4);
+    a.reads(d_rot, floats(rot_batch, 9), 4);
+    a.reads(d_src, floats(B, C, Hin, Win), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_reproject_image(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C,
+                                           Hin, Win, Hs, Ws, H, W, d_dst, d_valid, static_cast<hipStream_t>(stream)));
 }
 
 int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,

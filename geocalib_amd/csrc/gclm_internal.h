@@ -235,6 +235,10 @@ hipError_t launch_render_from_pano(int camera_model, const float* cam, int cam_b
                                    const int* src_hw, int n, int C, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_perspective_fields(int camera_model, const float* cam, const float* grav, int B, int H, int W, int normalize,
                                      float* up /* or nullptr */, float* lat /* or nullptr */, hipStream_t s);
+// gclm_reproject.hip
+hipError_t launch_reproject_image(int src_model, const float* src_cam, int dst_model, const float* dst_cam, int cam_batch,
+                                  const float* rot /* or nullptr */, int rot_batch, const float* src, int B, int C, int Hin, int Win,
+                                  int Hs, int Ws, int H, int W, float* dst, unsigned char* valid /* or nullptr */, hipStream_t s);
 
 
 // gclm_metrics.hip

@@ -1,6 +1,6 @@
-// gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_persp.hip) and of
+// gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_reproject.hip, gclm_persp.hip) and of
 // the kernels that score fields against one calibration (gclm_metrics.hip) or against many (gclm_hypotheses.hip); device
-// code, included by those five (and by gclm_entry.hip, for the bound on the tile grid) only: the
+// code, included by those six (and by gclm_entry.hip, for the bound on the tile grid) only: the
 // camera models' undistort and distort scales, the zero-padded bilinear sampler, the nontemporal store, the tile geometry
 // and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
 //

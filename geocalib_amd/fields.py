@@ -145,6 +145,38 @@ def undistort_image(camera_model: str, cam: torch.Tensor, img: torch.Tensor, siz
     return dst
 
 
+def reproject_image(src_model: str, src_cam: torch.Tensor, dst_model: str, dst_cam: torch.Tensor, rot: Optional[torch.Tensor],
+                    img: torch.Tensor, src_size, size, return_valid: bool = False):
+    """gclm_reproject_image: `img` (B, C, Hin, Win) float32 on a HIP device, taken with `src_cam` of nominal `src_size` =
+    (Hs, Ws), as `dst_cam` of `size` = (H, W) sees it after the rotation `rot` ((1 or B, 3, 3), or None for the identity), in
+    one launch per 65 535 images on torch's current stream.  The cameras are (1, 8) shared by the batch or (B, 8), both of
+    one batch.  Returns (B, C, H, W), and with `return_valid` the (B, H, W) bool mask of the pixels that see the source.
+    BaseCamera.reproject_image is the public entry; not differentiable."""
+    if img.dtype != torch.float32:
+        raise RuntimeError("geocalib_amd.reproject_image needs a float32 image")
+    (Hs, Ws), (H, W) = (int(v) for v in src_size), (int(v) for v in size)
+    src = _call.dev_f32(img, "img")
+    row = lambda t, k: t.detach().to(device=src.device, dtype=torch.float32).reshape(-1, k).contiguous()  # noqa: E731
+    src_cam, dst_cam, rot = row(src_cam, 8), row(dst_cam, 8), None if rot is None else row(rot, 9)
+    B, C, Hin, Win = src.shape
+    if src_cam.shape[0] != dst_cam.shape[0] or src_cam.shape[0] not in (1, B) or (rot is not None and rot.shape[0] not in (1, B)):
+        raise ValueError(f"camera batches {src_cam.shape[0]} and {dst_cam.shape[0]} must be equal and, as the rotation batch "
+                         f"{None if rot is None else rot.shape[0]}, 1 or {B}")
+    dst = src.new_empty((B, C, H, W))
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=src.device) if return_valid else None
+    if dst.numel() > 0:
+        at = lambda t, b0, n: None if t is None else (t if t.shape[0] == 1 else t[b0:b0 + n]).data_ptr()  # noqa: E731
+        for b0, n in _call.slices(B):
+            _call.call("gclm_reproject_image", _lib.CAMERA_MODEL_IDS[src_model], at(src_cam, b0, n), _lib.CAMERA_MODEL_IDS[dst_model],
+                       at(dst_cam, b0, n), 1 if src_cam.shape[0] == 1 else n, at(rot, b0, n),
+                       1 if rot is None or rot.shape[0] == 1 else n, src[b0].data_ptr(), n, C, Hin, Win, Hs, Ws, H, W,
+                       dst[b0].data_ptr(), None if valid is None else valid[b0].data_ptr(), _call.raw_stream(src.device),
+                       device=src.device)
+    elif valid is not None:
+        valid.zero_()
+    return (dst, valid.bool()) if return_valid else dst
+
+
 def render_from_pano(camera_model: str, cam: torch.Tensor, rot: torch.Tensor, panos, size) -> torch.Tensor:
     """gclm_render_from_pano: n images of `size` = (H, W) rendered from equirectangular panoramas, on torch's current stream.
 

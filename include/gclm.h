@@ -50,7 +50,7 @@ extern "C" {
  * gclm_field_errors_workspace added, also within 610; gclm_hypothesis_scores and gclm_hypothesis_scores_workspace added, also
  * within 610; gclm_set_conf_pack, gclm_plan_conf_pack, gclm_conf_pack_bytes and gclm_conf_pack_fallbacks added, also within 610: large pinhole
  * batches keep their two confidence planes as one plane of 16-bit pairs, see gclm_set_conf_pack; gclm_rpf_hypotheses added, also
- * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks).  gclm_create refuses a gclm_config whose first two fields do not
+ * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks; gclm_reproject_image added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -307,6 +307,37 @@ int gclm_upsample_fields_multi(const float* const* d_srcs, float* const* d_dsts,
  */
 int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin,
                          int Win, int H, int W, float* d_dst, void* stream);
+
+/*
+ * BaseCamera.reproject_image / upright_image for a batch, in one pass: d_dst (B, C, H, W) is d_src (B, C, Hin, Win) as a
+ * target camera, turned by a rotation, sees it; float32 NCHW.  d_src_cam and d_dst_cam are (cam_batch, 8)
+ * {w, h, fx, fy, cx, cy, k1, k2} in device memory, the camera the image was taken with and the camera to render (the w, h
+ * entries are not read: H, W are the output size, Hs, Ws the nominal size of the source camera, whose image may be stored at
+ * another resolution Hin x Win, as for gclm_undistort_image); cam_batch applies to both: 1 shares one pair over the batch, B
+ * gives each image its own.  d_rot is (rot_batch, 3, 3) row-major in device memory, rot_batch 1 or B, or NULL for the
+ * identity (then rot_batch is still 1 or B).  For output pixel (x, y), integer pixel centres, no half-pixel offset:
+ *   u = (x - cx_t) / fx_t,  v = (y - cy_t) / fy_t,  r2 = u^2 + v^2,  t = the TARGET model's undistort scale t(r2)
+ *   q = (u t, v t, 1) M          (row vector times M, the convention of gclm_render_from_pano; M NULL: q = (u t, v t, 1))
+ *   visible = q_z > 1e-3         (BaseCamera.eps, the reference's project())
+ *   p = (q_x, q_y) / q_z,  r2s = |p|^2,  (s, s') = the SOURCE model's distort scale s(r2s) and ds/dr2
+ *   inside_model = s + 2 r2s s' > 0
+ *   ix = (p_x s fx_s + cx_s) (Win - 1) / (Ws - 1),   iy = (p_y s fy_s + cy_s) (Hin - 1) / (Hs - 1)
+ * t as for gclm_render_from_pano, s as for gclm_undistort_image (the forms that do not cancel in float32); s': pinhole 0,
+ * simple_radial k1, radial k1 + 2 k2 r2, simple_divisional 4 k1 / (sqrt(tau) (1 + sqrt(tau))^2) with tau = 1 - 4 k1 r2
+ * (tau < 1e-6: the reference's expression at its clamp sqrt(1e-6)).  inside_model says that r s(r^2) still increases: beyond
+ * that radius a polynomial model folds far rays back into the image.  Bilinear with zero padding, as
+ * F.grid_sample(bilinear, zeros, align_corners=True); the output is exactly 0 where visible or inside_model fails and
+ * where a coordinate is not finite.  A NaN or inf in a camera or in the rotation zeroes its whole image (an infinite q_z
+ * counts as invisible).  d_valid (B, H, W) uint8, or NULL: 1 iff visible && inside_model && 0 <= ix <= Win - 1 &&
+ * 0 <= iy <= Hin - 1.  With M the identity and the target the source's pinhole() this is gclm_undistort_image up to rounding.
+ * Returns -3 (before any HIP call) for a NULL required pointer, a model outside 0..3, B outside 1..65535, C, Hin, Win, H or
+ * W < 1, Hs or Ws < 2, H * W > 2^31 - 1 (or a tile grid of more than 2^32 threads), cam_batch or rot_batch not 1 or B, a
+ * float pointer off a 4-byte boundary, or a destination or mask that overlaps any input or the other output; -10 if the
+ * launch fails.  Asynchronous on `stream`; no allocation.
+ */
+int gclm_reproject_image(int src_model, const float* d_src_cam, int dst_model, const float* d_dst_cam, int cam_batch,
+                         const float* d_rot, int rot_batch, const float* d_src, int B, int C, int Hin, int Win, int Hs, int Ws,
+                         int H, int W, float* d_dst, unsigned char* d_valid, void* stream);
 
 /*
  * get_up_field / get_latitude_field / get_perspective_field (geocalib/perspective_fields.py:47-74, 185-211, 278-320) for a
