@@ -45,6 +45,21 @@ def dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
+def dev_u8(t: torch.Tensor, name: str):
+    """A (B, C, H, W) byte image as the kernels read it, and its layout flag: on a HIP device, uint8, detached; planar
+    (contiguous, 0) or interleaved (channels_last with C <= 4, 1) as it lies in memory, without a copy.  Any other stride
+    pattern, or channels_last with C > 4, is copied to planar."""
+    require_device(t, name)
+    if t.dtype is not torch.uint8 or t.dim() != 4:
+        raise RuntimeError(f"geocalib_amd: `{name}` must be a (B, C, H, W) uint8 image, got {t.dtype} {tuple(t.shape)}")
+    t = t.detach()
+    if t.is_contiguous():
+        return t, 0
+    if t.shape[1] <= 4 and t.is_contiguous(memory_format=torch.channels_last):
+        return t, 1
+    return t.contiguous(), 0
+
+
 def call(name: str, *args, handle=None, comm=None, device=None) -> None:
     """`name(*args)` of the library (looked up through _lib.load() at call time); a non-zero return raises GclmError.
 

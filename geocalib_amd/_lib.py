@@ -93,6 +93,10 @@ _SIGNATURES = {
                                         C.c_int, _P, _P]),
     "gclm_reproject_image": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "gclm_undistort_image_u8": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                          _P]),
+    "gclm_reproject_image_u8": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gclm_perspective_fields": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gclm_field_errors_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gclm_field_errors": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float), _P,

@@ -327,7 +327,12 @@ class BaseCamera(TensorWrapper):
         A float32 image on a HIP device runs one gclm_undistort_image launch (not differentiable); a non-finite
         coordinate gives 0 there.  Every other input (CPU, other dtypes) runs the reference's torch composition.  The two
         differ for simple_divisional at small |k1 r2|: the torch path keeps the reference's cancelling float32 form of the
-        distort scale, the HIP path evaluates the identical 2 / (1 + sqrt(1 - 4 k1 r2)), held to float64."""
+        distort scale, the HIP path evaluates the identical 2 / (1 + sqrt(1 - 4 k1 r2)), held to float64.
+
+        A uint8 image gives a uint8 image in its memory format: the float32 sample rounded to nearest, ties to even, saturated
+        to 0..255.  On a HIP device that is one gclm_undistort_image_u8 launch, which reads a contiguous image, or a
+        channels_last one of up to 4 channels (a decoded frame, H x W x C in memory), as it lies; elsewhere the composition
+        runs on img.float()."""
         assert img.dim() == 4, f"expected a (B, C, H, W) image, got {tuple(img.shape)}"
         data = self._data.reshape(-1, self._data.shape[-1])
         n, B = data.shape[0], img.shape[0]
@@ -339,6 +344,11 @@ class BaseCamera(TensorWrapper):
         if img.is_cuda and img.dtype == torch.float32:
             from .fields import undistort_image
             return undistort_image(self.name(), data, img, (H, W))
+        if img.dtype == torch.uint8:
+            if img.is_cuda:
+                from .fields import undistort_image_u8
+                return undistort_image_u8(self.name(), data, img, (H, W))
+            return _to_u8(self.undistort_image(img.float()), img)
         cam = self.__class__(data)
         x, y = torch.meshgrid(torch.arange(0, W), torch.arange(0, H), indexing="xy")
         coords = torch.stack((x, y), dim=-1).reshape(-1, 2).to(device=self.device, dtype=self.dtype)
@@ -464,7 +474,9 @@ class BaseCamera(TensorWrapper):
 
         A float32 image on a HIP device runs one gclm_reproject_image launch (not differentiable).  Every other input (CPU,
         other dtypes) runs a torch composition of the same definition, simple_divisional's scales in the forms that do not
-        cancel (csrc/gclm_render.h).  The method reads the device once: the two cameras' sizes, in one .tolist()."""
+        cancel (csrc/gclm_render.h).  A uint8 image gives a uint8 image in its memory format, as for undistort_image
+        (gclm_reproject_image_u8 on a HIP device).  The method reads the device once: the two cameras' sizes, in one
+        .tolist()."""
         if img.dim() != 4:
             raise ValueError(f"expected a (B, C, H, W) image, got {tuple(img.shape)}")
         B = img.shape[0]
@@ -497,7 +509,14 @@ class BaseCamera(TensorWrapper):
         if img.is_cuda and img.dtype == torch.float32:
             from .fields import reproject_image
             return reproject_image(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W), return_valid)
-        out, valid = _reproject_torch(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W))
+        if img.is_cuda and img.dtype == torch.uint8:
+            from .fields import reproject_image_u8
+            return reproject_image_u8(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W), return_valid)
+        if img.dtype == torch.uint8:
+            out, valid = _reproject_torch(self.name(), src, tgt_name, tgt, rot, img.float(), (Hs, Ws), (H, W))
+            out = _to_u8(out, img)
+        else:
+            out, valid = _reproject_torch(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W))
         return (out, valid) if return_valid else out
 
     def upright_image(self, img: torch.Tensor, gravity, level_pitch: bool = False, target: "BaseCamera" = None,
@@ -515,6 +534,15 @@ class BaseCamera(TensorWrapper):
 
     def __repr__(self):
         return f"{self.__class__.__name__} {self.shape} {self.dtype} {self.device}"
+
+
+def _to_u8(out: torch.Tensor, img: torch.Tensor) -> torch.Tensor:
+    """The float32 composition of a uint8 image `img` as bytes: rounded to nearest, ties to even (torch.round), saturated to
+    0..255, in the memory format of `img` -- the definition of the HIP path (include/gclm.h: gclm_undistort_image_u8)."""
+    out = out.round().clamp(0, 255).to(torch.uint8)
+    if not img.is_contiguous() and img.is_contiguous(memory_format=torch.channels_last):
+        return out.contiguous(memory_format=torch.channels_last)
+    return out.contiguous()
 
 
 def _render_scales(model: str, k1: torch.Tensor, k2: torch.Tensor, r2: torch.Tensor):

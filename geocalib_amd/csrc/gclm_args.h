@@ -34,6 +34,14 @@ size_t floats(N... n) {
     return r;
 }
 
+// Bytes of n0 * n1 * ... one-byte elements (the byte images), saturating alike.
+template <typename... N>
+size_t bytes(N... n) {
+    size_t r = 1;
+    ((r = mul_sat(r, (size_t)n)), ...);
+    return r;
+}
+
 // (GCLM_ARGS_INLINE: left to itself the compiler keeps writes() out of line, and the ranges then live in memory -- three times
 // the cost of a call's checks)
 #define GCLM_ARGS_INLINE __attribute__((always_inline))

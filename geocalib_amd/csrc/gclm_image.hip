@@ -47,6 +47,28 @@ __global__ __launch_bounds__(kBlock) void undistort_image_kernel(const float* __
     for (int c = 0; c < C; ++c, p += plane_in, d += plane_out) store_nt(bilinear_sample(p, a, Win), d);
 }
 
+// gclm_undistort_image_u8: the same pixel of a byte image, planar or interleaved (gclm_render.h: sample_store_u8).  The
+// coordinate code is undistort_image_kernel's, restated word for word, as in gclm_reproject.hip: the float kernels' text and
+// instruction streams are left as they were.
+template <int MODEL, bool INTERLEAVED>
+__global__ __launch_bounds__(kBlock) void undistort_u8_kernel(const float* __restrict__ cam, int cam_stride,
+                                                              const unsigned char* __restrict__ src, int C, int Hin, int Win,
+                                                              int H, int W, int tiles_x, int dwords, unsigned char* __restrict__ dst) {
+    int x, y;
+    if (!tile_pixel(tiles_x, H, W, x, y)) return;
+    const int b = blockIdx.y;
+    const float* cb = cam + (size_t)b * cam_stride;
+    const float fx = cb[2], fy = cb[3], cx = cb[4], cy = cb[5], k1 = cb[6], k2 = cb[7];
+    const float ifx = 1.f / fx, ify = 1.f / fy;
+    const float sx = (float)(Win - 1) / (float)(W - 1), sy = (float)(Hin - 1) / (float)(H - 1);
+    const float dx = (float)x - cx, dy = (float)y - cy;
+    const float u = dx * ifx, v = dy * ify;
+    float s, sp;
+    distort_scale<MODEL>(u * u + v * v, k1, k2, s, sp);
+    const Taps a = bilinear_taps((dx * s + cx) * sx, (dy * s + cy) * sy, Hin, Win);
+    sample_store_u8<INTERLEAVED>(src, dst, a, b, C, Hin, Win, (size_t)H * W, y * W + x, dwords != 0);
+}
+
 }  // namespace
 
 hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,
@@ -55,6 +77,19 @@ hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_ba
         hipLaunchKernelGGL(undistort_image_kernel<decltype(m)::value>, dim3(tile_count(H, W), B), dim3(kBlock), 0, st, cam,
                            cam_batch == 1 ? 0 : 8, src, C, Hin, Win, H, W, tile_columns(W), dst);
         return hipGetLastError();
+    });
+}
+
+hipError_t launch_undistort_image_u8(int camera_model, const float* cam, int cam_batch, const unsigned char* src, int B, int C,
+                                     int Hin, int Win, int H, int W, bool interleaved, bool dwords, unsigned char* dst,
+                                     hipStream_t st) {
+    return with_camera_model(camera_model, [&](auto m) {
+        auto launch = [&](auto il) {
+            hipLaunchKernelGGL((undistort_u8_kernel<decltype(m)::value, decltype(il)::value>), dim3(tile_count(H, W), B), dim3(kBlock),
+                               0, st, cam, cam_batch == 1 ? 0 : 8, src, C, Hin, Win, H, W, tile_columns(W), (int)dwords, dst);
+            return hipGetLastError();
+        };
+        return interleaved ? launch(std::true_type{}) : launch(std::false_type{});
     });
 }
 

@@ -1,8 +1,8 @@
 // gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_reproject.hip, gclm_persp.hip) and of
 // the kernels that score fields against one calibration (gclm_metrics.hip) or against many (gclm_hypotheses.hip); device
 // code, included by those six (and by gclm_entry.hip, for the bound on the tile grid) only: the
-// camera models' undistort and distort scales, the zero-padded bilinear sampler, the nontemporal store, the tile geometry
-// and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
+// camera models' undistort and distort scales, the zero-padded bilinear sampler (float32 images, and uint8 images planar or
+// interleaved with their rounding store), the nontemporal store, the tile geometry and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
 //
 // Nothing here is shared with the LM sweep (gclm_pass.hip) or with synth_kernel (gclm_synth.hip), on purpose: the sweep
 // keeps the reference's float32 forms so that the solve rounds like the reference, and the synthetic fields' bits define
@@ -121,6 +121,57 @@ __device__ __forceinline__ float bilinear_sample(const float* __restrict__ p, co
     const float v00 = t.m00 ? p[t.o] : 0.f, v01 = t.m01 ? p[t.o + 1] : 0.f;
     const float v10 = t.m10 ? p[t.o + Win] : 0.f, v11 = t.m11 ? p[t.o + Win + 1] : 0.f;
     return v00 * t.w00 + v01 * t.w01 + v10 * t.w10 + v11 * t.w11;
+}
+
+// Byte images (gclm_undistort_image_u8, gclm_reproject_image_u8).  A tap's byte is converted to float32
+// exactly, the sample is the float sampler's sum, and the byte written is that sum rounded to nearest, ties to even, saturated
+// to 0..255 (the sum of four weighted bytes is finite, so the clamp sees no NaN).
+__device__ __forceinline__ unsigned char to_u8(float v) {
+    return (unsigned char)(int)fminf(fmaxf(__builtin_rintf(v), 0.f), 255.f);
+}
+
+// One channel's sample of a byte image: p + o is the top-left tap's byte, dx the bytes to its right neighbour (1 planar, C
+// interleaved), dy the bytes to the row below.
+__device__ __forceinline__ float bilinear_sample_u8(const unsigned char* __restrict__ p, const Taps& t, int64_t o, int dx, int64_t dy) {
+    const float v00 = t.m00 ? (float)p[o] : 0.f, v01 = t.m01 ? (float)p[o + dx] : 0.f;
+    const float v10 = t.m10 ? (float)p[o + dy] : 0.f, v11 = t.m11 ? (float)p[o + dy + dx] : 0.f;
+    return v00 * t.w00 + v01 * t.w01 + v10 * t.w10 + v11 * t.w11;
+}
+
+// All four channels of an interleaved C = 4 pixel whose image starts on a dword: a tap is one dword, the pixel one dword store.
+__device__ __forceinline__ unsigned bilinear_sample_4xu8(const unsigned* __restrict__ p, const Taps& t, int Win) {
+    const unsigned v00 = t.m00 ? p[t.o] : 0u, v01 = t.m01 ? p[t.o + 1] : 0u;
+    const unsigned v10 = t.m10 ? p[t.o + Win] : 0u, v11 = t.m11 ? p[t.o + Win + 1] : 0u;
+    unsigned out = 0;
+#pragma unroll
+    for (int k = 0; k < 32; k += 8) {
+        const float v = (float)((v00 >> k) & 255u) * t.w00 + (float)((v01 >> k) & 255u) * t.w01 +
+                        (float)((v10 >> k) & 255u) * t.w10 + (float)((v11 >> k) & 255u) * t.w11;
+        out |= (unsigned)to_u8(v) << k;
+    }
+    return out;
+}
+
+// Every channel of one output pixel of image b, sampled at `a` and stored: o is the pixel's offset in its (H, W) plane.
+// Planar: source (B, C, Hin, Win), destination (B, C, H, W).  Interleaved: (B, Hin, Win, C) and (B, H, W, C), C <= 4;
+// `dwords` (host: C = 4 and both images on a 4-byte boundary) takes the dword path, which writes the same bytes.
+template <bool INTERLEAVED>
+__device__ __forceinline__ void sample_store_u8(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, const Taps& a,
+                                                int b, int C, int Hin, int Win, size_t plane_out, int o, bool dwords) {
+    const size_t plane_in = (size_t)Hin * Win;
+    const unsigned char* p = src + (size_t)b * C * plane_in;
+    if constexpr (INTERLEAVED) {
+        unsigned char* d = dst + ((size_t)b * plane_out + o) * C;
+        if (dwords) {
+            store_nt(bilinear_sample_4xu8(reinterpret_cast<const unsigned*>(p), a, Win), reinterpret_cast<unsigned*>(d));
+            return;
+        }
+        const int64_t o00 = a.o * C, dy = (int64_t)Win * C;
+        for (int c = 0; c < C; ++c) store_nt(to_u8(bilinear_sample_u8(p, a, o00 + c, C, dy)), d + c);
+    } else {
+        unsigned char* d = dst + (size_t)b * C * plane_out + o;
+        for (int c = 0; c < C; ++c, p += plane_in, d += plane_out) store_nt(to_u8(bilinear_sample_u8(p, a, a.o, 1, Win)), d);
+    }
 }
 
 // The perspective fields of one pixel (gclm_persp.hip renders them, gclm_metrics.hip scores predictions against them; the

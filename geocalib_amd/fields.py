@@ -177,6 +177,63 @@ def reproject_image(src_model: str, src_cam: torch.Tensor, dst_model: str, dst_c
     return (dst, valid.bool()) if return_valid else dst
 
 
+def _u8_image(img: torch.Tensor, size):
+    """What the two byte wrappers share: the image as the kernels read it, its layout flag, the empty output of `size` in that
+    layout, and what turns the output into the input's memory format (a channels_last image of more than 4 channels runs
+    planar)."""
+    src, interleaved = _call.dev_u8(img, "img")
+    fmt = torch.channels_last if interleaved else torch.contiguous_format
+    dst = torch.empty((src.shape[0], src.shape[1], int(size[0]), int(size[1])), dtype=torch.uint8, device=src.device,
+                      memory_format=fmt)
+    if not img.is_contiguous() and img.is_contiguous(memory_format=torch.channels_last):
+        return src, interleaved, dst, lambda t: t.contiguous(memory_format=torch.channels_last)
+    return src, interleaved, dst, lambda t: t
+
+
+def undistort_image_u8(camera_model: str, cam: torch.Tensor, img: torch.Tensor, size) -> torch.Tensor:
+    """gclm_undistort_image_u8: undistort_image for a (B, C, Hin, Win) uint8 image on a HIP device, contiguous or
+    channels_last (read as it lies for C <= 4); the uint8 output has the input's memory format."""
+    H, W = int(size[0]), int(size[1])
+    src, interleaved, dst, like_input = _u8_image(img, (H, W))
+    cam = cam.detach().to(device=src.device, dtype=torch.float32).reshape(-1, 8).contiguous()
+    B, C, Hin, Win = src.shape
+    if dst.numel() == 0:
+        return dst
+    for b0, n in _call.slices(B):
+        c = cam if cam.shape[0] == 1 else cam[b0:b0 + n]
+        _call.call("gclm_undistort_image_u8", _lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], src[b0].data_ptr(), n,
+                   C, Hin, Win, H, W, interleaved, dst[b0].data_ptr(), _call.raw_stream(src.device), device=src.device)
+    return like_input(dst)
+
+
+def reproject_image_u8(src_model: str, src_cam: torch.Tensor, dst_model: str, dst_cam: torch.Tensor, rot: Optional[torch.Tensor],
+                       img: torch.Tensor, src_size, size, return_valid: bool = False):
+    """gclm_reproject_image_u8: reproject_image for a (B, C, Hin, Win) uint8 image on a HIP device, contiguous or
+    channels_last (read as it lies for C <= 4); the uint8 output has the input's memory format, the mask is as
+    reproject_image's."""
+    (Hs, Ws), (H, W) = (int(v) for v in src_size), (int(v) for v in size)
+    src, interleaved, dst, like_input = _u8_image(img, (H, W))
+    row = lambda t, k: t.detach().to(device=src.device, dtype=torch.float32).reshape(-1, k).contiguous()  # noqa: E731
+    src_cam, dst_cam, rot = row(src_cam, 8), row(dst_cam, 8), None if rot is None else row(rot, 9)
+    B, C, Hin, Win = src.shape
+    if src_cam.shape[0] != dst_cam.shape[0] or src_cam.shape[0] not in (1, B) or (rot is not None and rot.shape[0] not in (1, B)):
+        raise ValueError(f"camera batches {src_cam.shape[0]} and {dst_cam.shape[0]} must be equal and, as the rotation batch "
+                         f"{None if rot is None else rot.shape[0]}, 1 or {B}")
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=src.device) if return_valid else None
+    if dst.numel() > 0:
+        at = lambda t, b0, n: None if t is None else (t if t.shape[0] == 1 else t[b0:b0 + n]).data_ptr()  # noqa: E731
+        for b0, n in _call.slices(B):
+            _call.call("gclm_reproject_image_u8", _lib.CAMERA_MODEL_IDS[src_model], at(src_cam, b0, n),
+                       _lib.CAMERA_MODEL_IDS[dst_model], at(dst_cam, b0, n), 1 if src_cam.shape[0] == 1 else n, at(rot, b0, n),
+                       1 if rot is None or rot.shape[0] == 1 else n, src[b0].data_ptr(), n, C, Hin, Win, Hs, Ws, H, W, interleaved,
+                       dst[b0].data_ptr(), None if valid is None else valid[b0].data_ptr(), _call.raw_stream(src.device),
+                       device=src.device)
+    elif valid is not None:
+        valid.zero_()
+    dst = like_input(dst)
+    return (dst, valid.bool()) if return_valid else dst
+
+
 def render_from_pano(camera_model: str, cam: torch.Tensor, rot: torch.Tensor, panos, size) -> torch.Tensor:
     """gclm_render_from_pano: n images of `size` = (H, W) rendered from equirectangular panoramas, on torch's current stream.
 

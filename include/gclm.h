@@ -50,7 +50,8 @@ extern "C" {
  * gclm_field_errors_workspace added, also within 610; gclm_hypothesis_scores and gclm_hypothesis_scores_workspace added, also
  * within 610; gclm_set_conf_pack, gclm_plan_conf_pack, gclm_conf_pack_bytes and gclm_conf_pack_fallbacks added, also within 610: large pinhole
  * batches keep their two confidence planes as one plane of 16-bit pairs, see gclm_set_conf_pack; gclm_rpf_hypotheses added, also
- * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks; gclm_reproject_image added, also within 610).  gclm_create refuses a gclm_config whose first two fields do not
+ * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks; gclm_reproject_image added, also within 610;
+ * gclm_undistort_image_u8 and gclm_reproject_image_u8 added, also within 610: the two image calls for uint8 images).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -338,6 +339,28 @@ int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, co
 int gclm_reproject_image(int src_model, const float* d_src_cam, int dst_model, const float* d_dst_cam, int cam_batch,
                          const float* d_rot, int rot_batch, const float* d_src, int B, int C, int Hin, int Win, int Hs, int Ws,
                          int H, int W, float* d_dst, unsigned char* d_valid, void* stream);
+
+/*
+ * gclm_undistort_image and gclm_reproject_image for uint8 images, planar or interleaved, in one pass: nothing is converted
+ * before or after.  interleaved = 0: d_src (B, C, Hin, Win) and d_dst (B, C, H, W), one byte per element; interleaved = 1:
+ * d_src (B, Hin, Win, C) and d_dst (B, H, W, C), C in 1..4 (torch: a channels_last (B, C, H, W) tensor).  Source and
+ * destination share the layout; d_valid is (B, H, W) as for the float call.  Every other argument, the coordinates, the
+ * visible and inside_model tests, the zero padding and the mask are those of gclm_undistort_image / gclm_reproject_image.  A
+ * tap's byte is converted to float32 exactly, the sample is the float call's sum v00 w00 + v01 w01 + v10 w10 + v11 w11, and
+ * the output byte is that sum rounded to nearest, ties to even, saturated to 0..255: 0 where the float call writes exactly
+ * 0, and a byte-exact copy where the float call copies bit-exactly.
+ * The byte pointers carry no alignment requirement (a frame cropped out of a larger buffer starts anywhere): interleaved
+ * C = 4 images that both start on a 4-byte boundary are read and written as dwords, all others byte by byte, and the result
+ * is the same bytes either way.
+ * Returns -3 (before any HIP call) for everything the float call refuses -- its ranges counted in bytes, the image pointers
+ * free of its 4-byte condition -- and for interleaved not 0 or 1, or interleaved = 1 with C > 4; -10 if the launch fails.
+ * Asynchronous on `stream`; no allocation.
+ */
+int gclm_undistort_image_u8(int camera_model, const float* d_cam, int cam_batch, const unsigned char* d_src, int B, int C, int Hin,
+                            int Win, int H, int W, int interleaved, unsigned char* d_dst, void* stream);
+int gclm_reproject_image_u8(int src_model, const float* d_src_cam, int dst_model, const float* d_dst_cam, int cam_batch,
+                            const float* d_rot, int rot_batch, const unsigned char* d_src, int B, int C, int Hin, int Win, int Hs,
+                            int Ws, int H, int W, int interleaved, unsigned char* d_dst, unsigned char* d_valid, void* stream);
 
 /*
  * get_up_field / get_latitude_field / get_perspective_field (geocalib/perspective_fields.py:47-74, 185-211, 278-320) for a
