@@ -20,6 +20,11 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def ptr_at(t, b0: int):
+    """... of image `b0` onwards of a batch tensor: what a sliced call (slices) hands its entry."""
+    return None if t is None else t[b0].data_ptr()
+
+
 def raw_stream(device: torch.device) -> int:
     """The current HIP stream of `device` as the integer the C ABI takes (torch.cuda.current_stream(...).cuda_stream builds a
     Stream object first: 4.5 us per call on the single-image path)."""

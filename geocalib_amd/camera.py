@@ -341,13 +341,10 @@ class BaseCamera(TensorWrapper):
             assert data[:, 0].unique().shape[0] == 1, "All images must have the same width."
             assert data[:, 1].unique().shape[0] == 1, "All images must have the same height."
         W, H = (int(v) for v in data[0, :2].int().tolist())
-        if img.is_cuda and img.dtype == torch.float32:
+        if img.is_cuda and img.dtype in (torch.float32, torch.uint8):
             from .fields import undistort_image
             return undistort_image(self.name(), data, img, (H, W))
         if img.dtype == torch.uint8:
-            if img.is_cuda:
-                from .fields import undistort_image_u8
-                return undistort_image_u8(self.name(), data, img, (H, W))
             return _to_u8(self.undistort_image(img.float()), img)
         cam = self.__class__(data)
         x, y = torch.meshgrid(torch.arange(0, W), torch.arange(0, H), indexing="xy")
@@ -506,12 +503,9 @@ class BaseCamera(TensorWrapper):
             raise ValueError(f"source camera size {Ws} x {Hs} must be at least 2 x 2, target size {W} x {H} at least 1 x 1")
         if ns != nt:                                                      # one batch for both cameras
             src, tgt = src.expand(B, -1), tgt.expand(B, -1)
-        if img.is_cuda and img.dtype == torch.float32:
+        if img.is_cuda and img.dtype in (torch.float32, torch.uint8):
             from .fields import reproject_image
             return reproject_image(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W), return_valid)
-        if img.is_cuda and img.dtype == torch.uint8:
-            from .fields import reproject_image_u8
-            return reproject_image_u8(self.name(), src, tgt_name, tgt, rot, img, (Hs, Ws), (H, W), return_valid)
         if img.dtype == torch.uint8:
             out, valid = _reproject_torch(self.name(), src, tgt_name, tgt, rot, img.float(), (Hs, Ws), (H, W))
             out = _to_u8(out, img)

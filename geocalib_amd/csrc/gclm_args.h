@@ -26,20 +26,19 @@ inline size_t mul_sat(size_t a, size_t b) {
     return __builtin_mul_overflow(a, b, &r) ? SIZE_MAX : r;
 }
 
-// Bytes of n0 * n1 * ... floats.  A negative factor counts as a huge one: the entry refuses it by a condition of its own.
-template <typename... N>
-size_t floats(N... n) {
-    size_t r = sizeof(float);
+// Bytes of n0 * n1 * ... elements of type T.  A negative factor counts as a huge one: the entry refuses it by a condition of
+// its own.
+template <typename T, typename... N>
+size_t elements(N... n) {
+    size_t r = sizeof(T);
     ((r = mul_sat(r, (size_t)n)), ...);
     return r;
 }
 
-// Bytes of n0 * n1 * ... one-byte elements (the byte images), saturating alike.
+// ... of floats, which is what nearly every range holds.
 template <typename... N>
-size_t bytes(N... n) {
-    size_t r = 1;
-    ((r = mul_sat(r, (size_t)n)), ...);
-    return r;
+size_t floats(N... n) {
+    return elements<float>(n...);
 }
 
 // (GCLM_ARGS_INLINE: left to itself the compiler keeps writes() out of line, and the ranges then live in memory -- three times

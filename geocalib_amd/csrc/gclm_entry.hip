@@ -12,6 +12,47 @@ using namespace gclm;
 
 namespace {
 int launched(hipError_t e) { return e == hipSuccess ? 0 : -10; }
+
+// The two image warps, for float32 (T = float) and byte (T = unsigned char) images alike.  `interleaved` is the byte calls'
+// layout flag -- an interleaved image has at most 4 channels -- and the float calls pass 0, so neither its refusal nor the
+// dword path can reach them.  The dword path of C = 4 is taken where both images allow it (the same bytes either way).
+// Undistort states no alignment and no camera range; reproject holds an image to its element's alignment.
+template <typename T>
+int undistort_image(int camera_model, const float* d_cam, int cam_batch, const T* d_src, int B, int C, int Hin, int Win, int H, int W,
+                    int interleaved, T* d_dst, void* stream) {
+    if (!d_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1 || H < 2 || W < 2) return -3;
+    if ((cam_batch != 1 && cam_batch != B) || !known_model(camera_model) || (int64_t)H * W > INT32_MAX) return -3;
+    if ((interleaved != 0 && interleaved != 1) || (interleaved && C > 4)) return -3;
+    ArgCheck a;
+    a.writes(d_dst, elements<T>(B, C, H, W));
+    a.reads(d_src, elements<T>(B, C, Hin, Win));
+    if (!a.pass()) return -3;
+    const bool dwords = interleaved && C == 4 && is_aligned(d_src, 4) && is_aligned(d_dst, 4);
+    return launched(launch_undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, interleaved != 0, dwords,
+                                           d_dst, static_cast<hipStream_t>(stream)));
+}
+
+template <typename T>
+int reproject_image(int src_model, const float* d_src_cam, int dst_model, const float* d_dst_cam, int cam_batch, const float* d_rot,
+                    int rot_batch, const T* d_src, int B, int C, int Hin, int Win, int Hs, int Ws, int H, int W, int interleaved,
+                    T* d_dst, unsigned char* d_valid, void* stream) {
+    if (!d_src_cam || !d_dst_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1) return -3;
+    if (H < 1 || W < 1 || Hs < 2 || Ws < 2 || !tile_grid_fits(H, W) || !known_model(src_model) || !known_model(dst_model)) return -3;
+    if ((cam_batch != 1 && cam_batch != B) || (rot_batch != 1 && rot_batch != B)) return -3;
+    if ((interleaved != 0 && interleaved != 1) || (interleaved && C > 4)) return -3;
+    ArgCheck a;
+    a.writes(d_dst, elements<T>(B, C, H, W), alignof(T));
+    a.writes(d_valid, elements<unsigned char>(B, H, W));
+    a.reads(d_src_cam, floats(cam_batch, 8), 4);
+    a.reads(d_dst_cam, floats(cam_batch, 8), 4);
+    a.reads(d_rot, floats(rot_batch, 9), 4);
+    a.reads(d_src, elements<T>(B, C, Hin, Win), alignof(T));
+    if (!a.pass()) return -3;
+    const bool dwords = interleaved && C == 4 && is_aligned(d_src, 4) && is_aligned(d_dst, 4);
+    return launched(launch_reproject_image(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C, Hin,
+                                           Win, Hs, Ws, H, W, interleaved != 0, dwords, d_dst, d_valid,
+                                           static_cast<hipStream_t>(stream)));
+}
 }  // namespace
 
 extern "C" {
@@ -105,69 +146,26 @@ int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const flo
 
 int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin, int Win,
                          int H, int W, float* d_dst, void* stream) {
-    if (!d_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1 || H < 2 || W < 2) return -3;
-    if ((cam_batch != 1 && cam_batch != B) || !known_model(camera_model) || (int64_t)H * W > INT32_MAX) return -3;
-    ArgCheck a;
-    a.writes(d_dst, floats(B, C, H, W));
-    a.reads(d_src, floats(B, C, Hin, Win));
-    if (!a.pass()) return -3;
-    return launched(launch_undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, d_dst,
-                                           static_cast<hipStream_t>(stream)));
+    return undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, 0, d_dst, stream);
+}
+
+int gclm_undistort_image_u8(int camera_model, const float* d_cam, int cam_batch, const unsigned char* d_src, int B, int C, int Hin,
+                            int Win, int H, int W, int interleaved, unsigned char* d_dst, void* stream) {
+    return undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, interleaved, d_dst, stream);
 }
 
 int gclm_reproject_image(int src_model, const float* d_src_cam, int dst_model, const float* d_dst_cam, int cam_batch,
                          const float* d_rot, int rot_batch, const float* d_src, int B, int C, int Hin, int Win, int Hs, int Ws,
                          int H, int W, float* d_dst, unsigned char* d_valid, void* stream) {
-    if (!d_src_cam || !d_dst_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1) return -3;
-    if (H < 1 || W < 1 || Hs < 2 || Ws < 2 || !tile_grid_fits(H, W) || !known_model(src_model) || !known_model(dst_model)) return -3;
-    if ((cam_batch != 1 && cam_batch != B) || (rot_batch != 1 && rot_batch != B)) return -3;
-    ArgCheck a;
-    a.writes(d_dst, floats(B, C, H, W), 4);
-    a.writes(d_valid, mul_sat(mul_sat((size_t)B, (size_t)H), (size_t)W));
-    a.reads(d_src_cam, floats(cam_batch, 8), 4);
-    a.reads(d_dst_cam, floats(cam_batch, 8), 4);
-    a.reads(d_rot, floats(rot_batch, 9), 4);
-    a.reads(d_src, floats(B, C, Hin, Win), 4);
-    if (!a.pass()) return -3;
-    return launched(launch_reproject_image(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C,
-                                           Hin, Win, Hs, Ws, H, W, d_dst, d_valid, static_cast<hipStream_t>(stream)));
-}
-
-// The byte images: the float calls' conditions, the image ranges in bytes and free of any alignment; an interleaved image has
-// at most 4 channels.  The dword path of C = 4 is taken where both images allow it (the same bytes either way).
-int gclm_undistort_image_u8(int camera_model, const float* d_cam, int cam_batch, const unsigned char* d_src, int B, int C, int Hin,
-                            int Win, int H, int W, int interleaved, unsigned char* d_dst, void* stream) {
-    if (!d_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1 || H < 2 || W < 2) return -3;
-    if ((cam_batch != 1 && cam_batch != B) || !known_model(camera_model) || (int64_t)H * W > INT32_MAX) return -3;
-    if ((interleaved != 0 && interleaved != 1) || (interleaved && C > 4)) return -3;
-    ArgCheck a;
-    a.writes(d_dst, bytes(B, C, H, W));
-    a.reads(d_src, bytes(B, C, Hin, Win));
-    if (!a.pass()) return -3;
-    const bool dwords = interleaved && C == 4 && is_aligned(d_src, 4) && is_aligned(d_dst, 4);
-    return launched(launch_undistort_image_u8(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, interleaved != 0, dwords,
-                                              d_dst, static_cast<hipStream_t>(stream)));
+    return reproject_image(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C, Hin, Win, Hs, Ws,
+                           H, W, 0, d_dst, d_valid, stream);
 }
 
 int gclm_reproject_image_u8(int src_model, const float* d_src_cam, int dst_model, const float* d_dst_cam, int cam_batch,
                             const float* d_rot, int rot_batch, const unsigned char* d_src, int B, int C, int Hin, int Win, int Hs,
                             int Ws, int H, int W, int interleaved, unsigned char* d_dst, unsigned char* d_valid, void* stream) {
-    if (!d_src_cam || !d_dst_cam || !d_src || !d_dst || B < 1 || B > kMaxCallImages || C < 1 || Hin < 1 || Win < 1) return -3;
-    if (H < 1 || W < 1 || Hs < 2 || Ws < 2 || !tile_grid_fits(H, W) || !known_model(src_model) || !known_model(dst_model)) return -3;
-    if ((cam_batch != 1 && cam_batch != B) || (rot_batch != 1 && rot_batch != B)) return -3;
-    if ((interleaved != 0 && interleaved != 1) || (interleaved && C > 4)) return -3;
-    ArgCheck a;
-    a.writes(d_dst, bytes(B, C, H, W));
-    a.writes(d_valid, bytes(B, H, W));
-    a.reads(d_src_cam, floats(cam_batch, 8), 4);
-    a.reads(d_dst_cam, floats(cam_batch, 8), 4);
-    a.reads(d_rot, floats(rot_batch, 9), 4);
-    a.reads(d_src, bytes(B, C, Hin, Win));
-    if (!a.pass()) return -3;
-    const bool dwords = interleaved && C == 4 && is_aligned(d_src, 4) && is_aligned(d_dst, 4);
-    return launched(launch_reproject_image_u8(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C,
-                                              Hin, Win, Hs, Ws, H, W, interleaved != 0, dwords, d_dst, d_valid,
-                                              static_cast<hipStream_t>(stream)));
+    return reproject_image(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C, Hin, Win, Hs, Ws,
+                           H, W, interleaved, d_dst, d_valid, stream);
 }
 
 int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,

@@ -1,4 +1,5 @@
-// gclm_image.hip -- gclm_undistort_image: BaseCamera.undistort_image (reference geocalib/camera.py:396-412) in one pass.
+// gclm_image.hip -- gclm_undistort_image, gclm_undistort_image_u8: BaseCamera.undistort_image (reference
+// geocalib/camera.py:396-412) in one pass, over float32 or byte images: one kernel template, one launcher template.
 //
 // The reference builds a (1, H, W, 2) sampling grid from ten torch ops (meshgrid, normalize, Pinhole.undistort, the
 // projection of (u, v, 1), the model's distort, denormalize, the align_corners normalisation) and resamples with
@@ -23,10 +24,14 @@
 namespace gclm {
 namespace {
 
-template <int MODEL>
+// One kernel for both element types: T = float reads and writes planar float32 images (INTERLEAVED = false only), T =
+// unsigned char byte images, planar or interleaved (gclm_render.h: sample_store_u8).  The coordinate code stands once; the
+// tail alone depends on T.  `dwords` (the byte images' dword path, decided by the entry point) comes last, behind every
+// argument the float instantiations read: their instruction streams are those of the float-only kernel.
+template <int MODEL, typename T, bool INTERLEAVED>
 __global__ __launch_bounds__(kBlock) void undistort_image_kernel(const float* __restrict__ cam, int cam_stride,
-                                                                 const float* __restrict__ src, int C, int Hin, int Win,
-                                                                 int H, int W, int tiles_x, float* __restrict__ dst) {
+                                                                 const T* __restrict__ src, int C, int Hin, int Win, int H,
+                                                                 int W, int tiles_x, T* __restrict__ dst, int dwords) {
     int x, y;
     if (!tile_pixel(tiles_x, H, W, x, y)) return;
     const int b = blockIdx.y;
@@ -39,58 +44,37 @@ __global__ __launch_bounds__(kBlock) void undistort_image_kernel(const float* __
     float s, sp;
     distort_scale<MODEL>(u * u + v * v, k1, k2, s, sp);
     const Taps a = bilinear_taps((dx * s + cx) * sx, (dy * s + cy) * sy, Hin, Win);
-    const size_t plane_in = (size_t)Hin * Win, plane_out = (size_t)H * W;
-    const float* p = src + (size_t)b * C * plane_in;
-    // the pixel's offset in its plane fits 32 bits (gclm_undistort_image refuses H W > INT32_MAX); widened before the
-    // multiply, the compiler factors W out of image base and row and multiplies a 64-bit vector by it (+8 VALU per lane)
-    float* d = dst + (size_t)b * C * plane_out + (y * W + x);
-    for (int c = 0; c < C; ++c, p += plane_in, d += plane_out) store_nt(bilinear_sample(p, a, Win), d);
-}
-
-// gclm_undistort_image_u8: the same pixel of a byte image, planar or interleaved (gclm_render.h: sample_store_u8).  The
-// coordinate code is undistort_image_kernel's, restated word for word, as in gclm_reproject.hip: the float kernels' text and
-// instruction streams are left as they were.
-template <int MODEL, bool INTERLEAVED>
-__global__ __launch_bounds__(kBlock) void undistort_u8_kernel(const float* __restrict__ cam, int cam_stride,
-                                                              const unsigned char* __restrict__ src, int C, int Hin, int Win,
-                                                              int H, int W, int tiles_x, int dwords, unsigned char* __restrict__ dst) {
-    int x, y;
-    if (!tile_pixel(tiles_x, H, W, x, y)) return;
-    const int b = blockIdx.y;
-    const float* cb = cam + (size_t)b * cam_stride;
-    const float fx = cb[2], fy = cb[3], cx = cb[4], cy = cb[5], k1 = cb[6], k2 = cb[7];
-    const float ifx = 1.f / fx, ify = 1.f / fy;
-    const float sx = (float)(Win - 1) / (float)(W - 1), sy = (float)(Hin - 1) / (float)(H - 1);
-    const float dx = (float)x - cx, dy = (float)y - cy;
-    const float u = dx * ifx, v = dy * ify;
-    float s, sp;
-    distort_scale<MODEL>(u * u + v * v, k1, k2, s, sp);
-    const Taps a = bilinear_taps((dx * s + cx) * sx, (dy * s + cy) * sy, Hin, Win);
-    sample_store_u8<INTERLEAVED>(src, dst, a, b, C, Hin, Win, (size_t)H * W, y * W + x, dwords != 0);
+    if constexpr (std::is_same_v<T, float>) {
+        const size_t plane_in = (size_t)Hin * Win, plane_out = (size_t)H * W;
+        const float* p = src + (size_t)b * C * plane_in;
+        // the pixel's offset in its plane fits 32 bits (gclm_undistort_image refuses H W > INT32_MAX); widened before the
+        // multiply, the compiler factors W out of image base and row and multiplies a 64-bit vector by it (+8 VALU per lane)
+        float* d = dst + (size_t)b * C * plane_out + (y * W + x);
+        for (int c = 0; c < C; ++c, p += plane_in, d += plane_out) store_nt(bilinear_sample(p, a, Win), d);
+    } else {
+        sample_store_u8<INTERLEAVED>(src, dst, a, b, C, Hin, Win, (size_t)H * W, y * W + x, dwords != 0);
+    }
 }
 
 }  // namespace
 
-hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,
-                                  int Win, int H, int W, float* dst, hipStream_t st) {
-    return with_camera_model(camera_model, [&](auto m) {
-        hipLaunchKernelGGL(undistort_image_kernel<decltype(m)::value>, dim3(tile_count(H, W), B), dim3(kBlock), 0, st, cam,
-                           cam_batch == 1 ? 0 : 8, src, C, Hin, Win, H, W, tile_columns(W), dst);
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_undistort_image_u8(int camera_model, const float* cam, int cam_batch, const unsigned char* src, int B, int C,
-                                     int Hin, int Win, int H, int W, bool interleaved, bool dwords, unsigned char* dst,
-                                     hipStream_t st) {
+template <typename T>
+hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const T* src, int B, int C, int Hin, int Win,
+                                  int H, int W, bool interleaved, bool dwords, T* dst, hipStream_t st) {
     return with_camera_model(camera_model, [&](auto m) {
         auto launch = [&](auto il) {
-            hipLaunchKernelGGL((undistort_u8_kernel<decltype(m)::value, decltype(il)::value>), dim3(tile_count(H, W), B), dim3(kBlock),
-                               0, st, cam, cam_batch == 1 ? 0 : 8, src, C, Hin, Win, H, W, tile_columns(W), (int)dwords, dst);
+            hipLaunchKernelGGL((undistort_image_kernel<decltype(m)::value, T, decltype(il)::value>), dim3(tile_count(H, W), B),
+                               dim3(kBlock), 0, st, cam, cam_batch == 1 ? 0 : 8, src, C, Hin, Win, H, W, tile_columns(W), dst,
+                               (int)dwords);
             return hipGetLastError();
         };
-        return interleaved ? launch(std::true_type{}) : launch(std::false_type{});
+        if constexpr (std::is_same_v<T, float>) return launch(std::false_type{});      // (float images are planar)
+        else return interleaved ? launch(std::true_type{}) : launch(std::false_type{});
     });
 }
+template hipError_t launch_undistort_image(int, const float*, int, const float*, int, int, int, int, int, int, bool, bool, float*,
+                                           hipStream_t);
+template hipError_t launch_undistort_image(int, const float*, int, const unsigned char*, int, int, int, int, int, int, bool, bool,
+                                           unsigned char*, hipStream_t);
 
 }  // namespace gclm

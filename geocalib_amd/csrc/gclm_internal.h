@@ -229,25 +229,21 @@ hipError_t launch_synth(int camera_model, uint64_t seed, int64_t first_index, in
                         float* gt_grav, hipStream_t s);
 
 // gclm_image.hip, gclm_pano.hip, gclm_persp.hip
-hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const float* src, int B, int C, int Hin,
-                                  int Win, int H, int W, float* dst, hipStream_t s);
-// (the byte images: `dwords` = interleaved, C = 4 and both images on a 4-byte boundary, decided by the entry point)
-hipError_t launch_undistort_image_u8(int camera_model, const float* cam, int cam_batch, const unsigned char* src, int B, int C,
-                                     int Hin, int Win, int H, int W, bool interleaved, bool dwords, unsigned char* dst,
-                                     hipStream_t s);
+// (T = float or unsigned char, instantiated in their units; `interleaved` and `dwords` = interleaved, C = 4 and both images on
+//  a 4-byte boundary, decided by the entry point, are for the byte images: the float entries pass false, false)
+template <typename T>
+hipError_t launch_undistort_image(int camera_model, const float* cam, int cam_batch, const T* src, int B, int C, int Hin, int Win,
+                                  int H, int W, bool interleaved, bool dwords, T* dst, hipStream_t s);
 hipError_t launch_render_from_pano(int camera_model, const float* cam, int cam_batch, const float* rot, const float* const* srcs,
                                    const int* src_hw, int n, int C, int H, int W, float* dst, hipStream_t s);
 hipError_t launch_perspective_fields(int camera_model, const float* cam, const float* grav, int B, int H, int W, int normalize,
                                      float* up /* or nullptr */, float* lat /* or nullptr */, hipStream_t s);
 // gclm_reproject.hip
+template <typename T>
 hipError_t launch_reproject_image(int src_model, const float* src_cam, int dst_model, const float* dst_cam, int cam_batch,
-                                  const float* rot /* or nullptr */, int rot_batch, const float* src, int B, int C, int Hin, int Win,
-                                  int Hs, int Ws, int H, int W, float* dst, unsigned char* valid /* or nullptr */, hipStream_t s);
-hipError_t launch_reproject_image_u8(int src_model, const float* src_cam, int dst_model, const float* dst_cam, int cam_batch,
-                                     const float* rot /* or nullptr */, int rot_batch, const unsigned char* src, int B, int C,
-                                     int Hin, int Win, int Hs, int Ws, int H, int W, bool interleaved, bool dwords,
-                                     unsigned char* dst, unsigned char* valid /* or nullptr */, hipStream_t s);
-
+                                  const float* rot /* or nullptr */, int rot_batch, const T* src, int B, int C, int Hin, int Win,
+                                  int Hs, int Ws, int H, int W, bool interleaved, bool dwords, T* dst,
+                                  unsigned char* valid /* or nullptr */, hipStream_t s);
 
 // gclm_metrics.hip
 size_t field_errors_workspace(int B, int H, int W, int n_thresholds);     // bytes of one call's partial records; 0: sizes out of range

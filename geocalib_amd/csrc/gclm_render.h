@@ -123,7 +123,8 @@ __device__ __forceinline__ float bilinear_sample(const float* __restrict__ p, co
     return v00 * t.w00 + v01 * t.w01 + v10 * t.w10 + v11 * t.w11;
 }
 
-// Byte images (gclm_undistort_image_u8, gclm_reproject_image_u8).  A tap's byte is converted to float32
+// Byte images (gclm_undistort_image_u8, gclm_reproject_image_u8: the unsigned char instantiations of undistort_image_kernel and
+// reproject_kernel, whose tail is sample_store_u8).  A tap's byte is converted to float32
 // exactly, the sample is the float sampler's sum, and the byte written is that sum rounded to nearest, ties to even, saturated
 // to 0..255 (the sum of four weighted bytes is finite, so the clamp sees no NaN).
 __device__ __forceinline__ unsigned char to_u8(float v) {

@@ -1,5 +1,6 @@
-// gclm_reproject.hip -- gclm_reproject_image: BaseCamera.reproject_image / upright_image in one pass: an image as another
-// camera, turned by a rotation, sees it.  It joins the halves its siblings use: the target pixel's ray as
+// gclm_reproject.hip -- gclm_reproject_image, gclm_reproject_image_u8: BaseCamera.reproject_image / upright_image in one pass,
+// over float32 or byte images (one kernel template, one launcher template): an image as another camera, turned by a rotation,
+// sees it.  It joins the halves its siblings use: the target pixel's ray as
 // gclm_render_from_pano takes it (the undistort form), the source pixel of that ray as gclm_undistort_image takes it (the
 // distort form).
 //
@@ -38,12 +39,17 @@ namespace {
 
 constexpr float kVisibleEps = 1e-3f;       // BaseCamera.eps
 
-template <int SRC_MODEL, int DST_MODEL, bool HAS_ROT>
+// One kernel for both element types: T = float reads and writes planar float32 images (INTERLEAVED = false only), T =
+// unsigned char byte images, planar or interleaved (gclm_render.h: sample_store_u8).  The coordinate code, the visibility and
+// fold-back rules and the mask stand once; the tail alone depends on T.  `dwords` (the byte images' dword path, decided by
+// the entry point) comes last, behind every argument the float instantiations read: their instruction streams are those of
+// the float-only kernel.
+template <int SRC_MODEL, int DST_MODEL, bool HAS_ROT, typename T, bool INTERLEAVED>
 __global__ __launch_bounds__(kBlock) void reproject_kernel(const float* __restrict__ src_cam, const float* __restrict__ dst_cam,
                                                            int cam_stride, const float* __restrict__ rot, int rot_stride,
-                                                           const float* __restrict__ src, int C, int Hin, int Win, int Hs, int Ws,
-                                                           int H, int W, int tiles_x, float* __restrict__ dst,
-                                                           unsigned char* __restrict__ valid) {
+                                                           const T* __restrict__ src, int C, int Hin, int Win, int Hs, int Ws,
+                                                           int H, int W, int tiles_x, T* __restrict__ dst,
+                                                           unsigned char* __restrict__ valid, int dwords) {
     int x, y;
     if (!tile_pixel(tiles_x, H, W, x, y)) return;
     const int b = blockIdx.y;
@@ -74,98 +80,48 @@ __global__ __launch_bounds__(kBlock) void reproject_kernel(const float* __restri
     // an invisible or folded pixel samples where no tap lies inside the source
     const Taps a = bilinear_taps(ok ? ix : -2.f, ok ? iy : -2.f, Hin, Win);
 
-    const size_t plane_in = (size_t)Hin * Win, plane_out = (size_t)H * W;
+    const size_t plane_out = (size_t)H * W;
     const int o = y * W + x;                  // fits 32 bits: gclm_reproject_image refuses H W > INT32_MAX
     if (valid) {
         const bool in = ok && ix >= 0.f && ix <= (float)(Win - 1) && iy >= 0.f && iy <= (float)(Hin - 1);
         store_nt((unsigned char)in, valid + (size_t)b * plane_out + o);
     }
-    const float* p = src + (size_t)b * C * plane_in;
-    float* d = dst + (size_t)b * C * plane_out + o;
-    for (int c = 0; c < C; ++c, p += plane_in, d += plane_out) store_nt(bilinear_sample(p, a, Win), d);
-}
-
-// gclm_reproject_image_u8: the same pixel of a byte image, planar or interleaved (gclm_render.h: sample_store_u8).  The
-// coordinate code is reproject_kernel's, restated word for word: moved into a function that both kernels call, it compiled
-// the float kernels to other instruction streams, and those are held to what they were.
-template <int SRC_MODEL, int DST_MODEL, bool HAS_ROT, bool INTERLEAVED>
-__global__ __launch_bounds__(kBlock) void reproject_u8_kernel(const float* __restrict__ src_cam, const float* __restrict__ dst_cam,
-                                                              int cam_stride, const float* __restrict__ rot, int rot_stride,
-                                                              const unsigned char* __restrict__ src, int C, int Hin, int Win, int Hs,
-                                                              int Ws, int H, int W, int tiles_x, int dwords,
-                                                              unsigned char* __restrict__ dst, unsigned char* __restrict__ valid) {
-    int x, y;
-    if (!tile_pixel(tiles_x, H, W, x, y)) return;
-    const int b = blockIdx.y;
-    const float* ct = dst_cam + (size_t)b * cam_stride;
-    const float* cs = src_cam + (size_t)b * cam_stride;
-    const float fxt = ct[2], fyt = ct[3], cxt = ct[4], cyt = ct[5];
-    const float fxs = cs[2], fys = cs[3], cxs = cs[4], cys = cs[5];
-    const float ifx = 1.f / fxt + 0.f * fxt, ify = 1.f / fyt + 0.f * fyt;
-    const float sx = (float)(Win - 1) / (float)(Ws - 1), sy = (float)(Hin - 1) / (float)(Hs - 1);
-
-    const float u = ((float)x - cxt) * ifx, v = ((float)y - cyt) * ify;
-    const float t = undistort_scale<DST_MODEL>(u * u + v * v, ct[6], ct[7]);
-    const float bu = u * t, bv = v * t;
-    float qx = bu, qy = bv, qz = 1.f;
-    if constexpr (HAS_ROT) {
-        const float* M = rot + (size_t)b * rot_stride;
-        qx = bu * M[0] + bv * M[3] + M[6];
-        qy = bu * M[1] + bv * M[4] + M[7];
-        qz = bu * M[2] + bv * M[5] + M[8];
+    if constexpr (std::is_same_v<T, float>) {
+        const size_t plane_in = (size_t)Hin * Win;
+        const float* p = src + (size_t)b * C * plane_in;
+        float* d = dst + (size_t)b * C * plane_out + o;
+        for (int c = 0; c < C; ++c, p += plane_in, d += plane_out) store_nt(bilinear_sample(p, a, Win), d);
+    } else {
+        sample_store_u8<INTERLEAVED>(src, dst, a, b, C, Hin, Win, plane_out, o, dwords != 0);
     }
-    bool ok = qz > kVisibleEps && qz <= FLT_MAX;
-    const float iz = 1.f / qz, px = qx * iz, py = qy * iz, r2s = px * px + py * py;
-    float s, sp;
-    distort_scale<SRC_MODEL>(r2s, cs[6], cs[7], s, sp);
-    if constexpr (SRC_MODEL != GCLM_PINHOLE) ok = ok && s + 2.f * r2s * sp > 0.f;
-    const float ix = (px * s * fxs + cxs) * sx, iy = (py * s * fys + cys) * sy;
-    const Taps a = bilinear_taps(ok ? ix : -2.f, ok ? iy : -2.f, Hin, Win);
-
-    const size_t plane_out = (size_t)H * W;
-    const int o = y * W + x;
-    if (valid) {
-        const bool in = ok && ix >= 0.f && ix <= (float)(Win - 1) && iy >= 0.f && iy <= (float)(Hin - 1);
-        store_nt((unsigned char)in, valid + (size_t)b * plane_out + o);
-    }
-    sample_store_u8<INTERLEAVED>(src, dst, a, b, C, Hin, Win, plane_out, o, dwords != 0);
 }
 
 }  // namespace
 
+template <typename T>
 hipError_t launch_reproject_image(int src_model, const float* src_cam, int dst_model, const float* dst_cam, int cam_batch,
-                                  const float* rot, int rot_batch, const float* src, int B, int C, int Hin, int Win, int Hs,
-                                  int Ws, int H, int W, float* dst, unsigned char* valid, hipStream_t st) {
-    return with_camera_model(src_model, [&](auto ms) {
-        return with_camera_model(dst_model, [&](auto mt) {
-            auto launch = [&](auto has_rot) {
-                hipLaunchKernelGGL((reproject_kernel<decltype(ms)::value, decltype(mt)::value, decltype(has_rot)::value>),
-                                   dim3(tile_count(H, W), B), dim3(kBlock), 0, st, src_cam, dst_cam, cam_batch == 1 ? 0 : 8, rot,
-                                   rot_batch == 1 ? 0 : 9, src, C, Hin, Win, Hs, Ws, H, W, tile_columns(W), dst, valid);
-                return hipGetLastError();
-            };
-            return rot ? launch(std::true_type{}) : launch(std::false_type{});
-        });
-    });
-}
-
-hipError_t launch_reproject_image_u8(int src_model, const float* src_cam, int dst_model, const float* dst_cam, int cam_batch,
-                                     const float* rot, int rot_batch, const unsigned char* src, int B, int C, int Hin, int Win,
-                                     int Hs, int Ws, int H, int W, bool interleaved, bool dwords, unsigned char* dst,
-                                     unsigned char* valid, hipStream_t st) {
+                                  const float* rot, int rot_batch, const T* src, int B, int C, int Hin, int Win, int Hs, int Ws,
+                                  int H, int W, bool interleaved, bool dwords, T* dst, unsigned char* valid, hipStream_t st) {
     return with_camera_model(src_model, [&](auto ms) {
         return with_camera_model(dst_model, [&](auto mt) {
             auto launch = [&](auto has_rot, auto il) {
-                hipLaunchKernelGGL((reproject_u8_kernel<decltype(ms)::value, decltype(mt)::value, decltype(has_rot)::value,
-                                                        decltype(il)::value>),
+                hipLaunchKernelGGL((reproject_kernel<decltype(ms)::value, decltype(mt)::value, decltype(has_rot)::value, T,
+                                                     decltype(il)::value>),
                                    dim3(tile_count(H, W), B), dim3(kBlock), 0, st, src_cam, dst_cam, cam_batch == 1 ? 0 : 8, rot,
-                                   rot_batch == 1 ? 0 : 9, src, C, Hin, Win, Hs, Ws, H, W, tile_columns(W), (int)dwords, dst, valid);
+                                   rot_batch == 1 ? 0 : 9, src, C, Hin, Win, Hs, Ws, H, W, tile_columns(W), dst, valid, (int)dwords);
                 return hipGetLastError();
             };
-            if (interleaved) return rot ? launch(std::true_type{}, std::true_type{}) : launch(std::false_type{}, std::true_type{});
-            return rot ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
+            auto layout = [&](auto has_rot) {
+                if constexpr (std::is_same_v<T, float>) return launch(has_rot, std::false_type{});     // (float images are planar)
+                else return interleaved ? launch(has_rot, std::true_type{}) : launch(has_rot, std::false_type{});
+            };
+            return rot ? layout(std::true_type{}) : layout(std::false_type{});
         });
     });
 }
+template hipError_t launch_reproject_image(int, const float*, int, const float*, int, const float*, int, const float*, int, int, int,
+                                           int, int, int, int, int, bool, bool, float*, unsigned char*, hipStream_t);
+template hipError_t launch_reproject_image(int, const float*, int, const float*, int, const float*, int, const unsigned char*, int,
+                                           int, int, int, int, int, int, int, bool, bool, unsigned char*, unsigned char*, hipStream_t);
 
 }  // namespace gclm

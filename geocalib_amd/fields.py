@@ -125,109 +125,79 @@ def fastest_placement(allocate, solve, tries: int = 3, keep_first: bool = False)
     return (cands[best], times, cands[0]) if keep_first else (cands[best], times)
 
 
+def _rows(t: torch.Tensor, k: int, device) -> torch.Tensor:
+    """`t` as the render calls read their cameras (k = 8) and rotations (k = 9): (n, k) float32 rows on `device`, contiguous,
+    detached."""
+    return t.detach().to(device=device, dtype=torch.float32).reshape(-1, k).contiguous()
+
+
+def _rows_at(t: Optional[torch.Tensor], b0: int, n: int):
+    """(pointer, batch) of rows `t` for the images [b0, b0 + n) of a call: one row shared by them all, or their slice of one
+    row per image; None is (NULL, 1)."""
+    if t is None:
+        return None, 1
+    rows = t if t.shape[0] == 1 else t[b0:b0 + n]
+    return rows.data_ptr(), rows.shape[0]         # (the rows behind the pointer: a batch of neither kind is the entry's to refuse)
+
+
+def _warp_image(img: torch.Tensor, size, who: str):
+    """What the two image warps share, and the one place that knows dtypes and memory formats: the image as the kernels read
+    it, the arguments its entry takes before the destination (the byte calls' layout flag; none for float32), the empty
+    output of `size` in the kernels' layout, and what turns that output into the input's memory format (a channels_last byte
+    image of more than 4 channels runs planar)."""
+    if img.dtype == torch.float32:
+        src = _call.dev_f32(img, "img")
+        return src, (), src.new_empty(tuple(src.shape[:2]) + size), lambda t: t
+    if img.dtype != torch.uint8:
+        raise RuntimeError(f"geocalib_amd.{who} needs a float32 or uint8 image")
+    src, interleaved = _call.dev_u8(img, "img")
+    dst = torch.empty(tuple(src.shape[:2]) + size, dtype=torch.uint8, device=src.device,
+                      memory_format=torch.channels_last if interleaved else torch.contiguous_format)
+    if not img.is_contiguous() and img.is_contiguous(memory_format=torch.channels_last):
+        return src, (interleaved,), dst, lambda t: t.contiguous(memory_format=torch.channels_last)
+    return src, (interleaved,), dst, lambda t: t
+
+
 def undistort_image(camera_model: str, cam: torch.Tensor, img: torch.Tensor, size) -> torch.Tensor:
-    """gclm_undistort_image: `img` (B, C, Hin, Win) float32 on a HIP device, resampled to `size` = (H, W) at the distorted
-    position of every output pixel of `cam` ((1, 8) shared by the batch, or (B, 8)), in one launch per 65 535 images on
-    torch's current stream.  BaseCamera.undistort_image is the public entry; not differentiable."""
-    if img.dtype != torch.float32:
-        raise RuntimeError("geocalib_amd.undistort_image needs a float32 image")
+    """gclm_undistort_image / gclm_undistort_image_u8: `img` (B, C, Hin, Win) float32 or uint8 on a HIP device, resampled to
+    `size` = (H, W) at the distorted position of every output pixel of `cam` ((1, 8) shared by the batch, or (B, 8)), in one
+    launch per 65 535 images on torch's current stream.  A uint8 image is contiguous or channels_last (read as it lies for
+    C <= 4), and its uint8 output has its memory format.  BaseCamera.undistort_image is the public entry; not differentiable."""
     H, W = int(size[0]), int(size[1])
-    src = _call.dev_f32(img, "img")
-    cam = cam.detach().to(device=src.device, dtype=torch.float32).reshape(-1, 8).contiguous()
+    src, layout, dst, like_input = _warp_image(img, (H, W), "undistort_image")
+    cam = _rows(cam, 8, src.device)
     B, C, Hin, Win = src.shape
-    dst = src.new_empty((B, C, H, W))
     if dst.numel() == 0:
         return dst
     for b0, n in _call.slices(B):
-        c = cam if cam.shape[0] == 1 else cam[b0:b0 + n]
-        _call.call("gclm_undistort_image", _lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], src[b0].data_ptr(), n, C,
-                   Hin, Win, H, W, dst[b0].data_ptr(), _call.raw_stream(src.device), device=src.device)
-    return dst
+        _call.call("gclm_undistort_image_u8" if src.dtype == torch.uint8 else "gclm_undistort_image",
+                   _lib.CAMERA_MODEL_IDS[camera_model], *_rows_at(cam, b0, n), src[b0].data_ptr(), n, C, Hin, Win, H, W, *layout,
+                   dst[b0].data_ptr(), _call.raw_stream(src.device), device=src.device)
+    return like_input(dst)
 
 
 def reproject_image(src_model: str, src_cam: torch.Tensor, dst_model: str, dst_cam: torch.Tensor, rot: Optional[torch.Tensor],
                     img: torch.Tensor, src_size, size, return_valid: bool = False):
-    """gclm_reproject_image: `img` (B, C, Hin, Win) float32 on a HIP device, taken with `src_cam` of nominal `src_size` =
-    (Hs, Ws), as `dst_cam` of `size` = (H, W) sees it after the rotation `rot` ((1 or B, 3, 3), or None for the identity), in
-    one launch per 65 535 images on torch's current stream.  The cameras are (1, 8) shared by the batch or (B, 8), both of
-    one batch.  Returns (B, C, H, W), and with `return_valid` the (B, H, W) bool mask of the pixels that see the source.
-    BaseCamera.reproject_image is the public entry; not differentiable."""
-    if img.dtype != torch.float32:
-        raise RuntimeError("geocalib_amd.reproject_image needs a float32 image")
+    """gclm_reproject_image / gclm_reproject_image_u8: `img` (B, C, Hin, Win) float32 or uint8 on a HIP device, taken with
+    `src_cam` of nominal `src_size` = (Hs, Ws), as `dst_cam` of `size` = (H, W) sees it after the rotation `rot` ((1 or B, 3,
+    3), or None for the identity), in one launch per 65 535 images on torch's current stream.  The cameras are (1, 8) shared
+    by the batch or (B, 8), both of one batch.  Returns (B, C, H, W), and with `return_valid` the (B, H, W) bool mask of the
+    pixels that see the source.  A uint8 image is contiguous or channels_last (read as it lies for C <= 4), and its uint8
+    output has its memory format.  BaseCamera.reproject_image is the public entry; not differentiable."""
     (Hs, Ws), (H, W) = (int(v) for v in src_size), (int(v) for v in size)
-    src = _call.dev_f32(img, "img")
-    row = lambda t, k: t.detach().to(device=src.device, dtype=torch.float32).reshape(-1, k).contiguous()  # noqa: E731
-    src_cam, dst_cam, rot = row(src_cam, 8), row(dst_cam, 8), None if rot is None else row(rot, 9)
-    B, C, Hin, Win = src.shape
-    if src_cam.shape[0] != dst_cam.shape[0] or src_cam.shape[0] not in (1, B) or (rot is not None and rot.shape[0] not in (1, B)):
-        raise ValueError(f"camera batches {src_cam.shape[0]} and {dst_cam.shape[0]} must be equal and, as the rotation batch "
-                         f"{None if rot is None else rot.shape[0]}, 1 or {B}")
-    dst = src.new_empty((B, C, H, W))
-    valid = torch.empty((B, H, W), dtype=torch.uint8, device=src.device) if return_valid else None
-    if dst.numel() > 0:
-        at = lambda t, b0, n: None if t is None else (t if t.shape[0] == 1 else t[b0:b0 + n]).data_ptr()  # noqa: E731
-        for b0, n in _call.slices(B):
-            _call.call("gclm_reproject_image", _lib.CAMERA_MODEL_IDS[src_model], at(src_cam, b0, n), _lib.CAMERA_MODEL_IDS[dst_model],
-                       at(dst_cam, b0, n), 1 if src_cam.shape[0] == 1 else n, at(rot, b0, n),
-                       1 if rot is None or rot.shape[0] == 1 else n, src[b0].data_ptr(), n, C, Hin, Win, Hs, Ws, H, W,
-                       dst[b0].data_ptr(), None if valid is None else valid[b0].data_ptr(), _call.raw_stream(src.device),
-                       device=src.device)
-    elif valid is not None:
-        valid.zero_()
-    return (dst, valid.bool()) if return_valid else dst
-
-
-def _u8_image(img: torch.Tensor, size):
-    """What the two byte wrappers share: the image as the kernels read it, its layout flag, the empty output of `size` in that
-    layout, and what turns the output into the input's memory format (a channels_last image of more than 4 channels runs
-    planar)."""
-    src, interleaved = _call.dev_u8(img, "img")
-    fmt = torch.channels_last if interleaved else torch.contiguous_format
-    dst = torch.empty((src.shape[0], src.shape[1], int(size[0]), int(size[1])), dtype=torch.uint8, device=src.device,
-                      memory_format=fmt)
-    if not img.is_contiguous() and img.is_contiguous(memory_format=torch.channels_last):
-        return src, interleaved, dst, lambda t: t.contiguous(memory_format=torch.channels_last)
-    return src, interleaved, dst, lambda t: t
-
-
-def undistort_image_u8(camera_model: str, cam: torch.Tensor, img: torch.Tensor, size) -> torch.Tensor:
-    """gclm_undistort_image_u8: undistort_image for a (B, C, Hin, Win) uint8 image on a HIP device, contiguous or
-    channels_last (read as it lies for C <= 4); the uint8 output has the input's memory format."""
-    H, W = int(size[0]), int(size[1])
-    src, interleaved, dst, like_input = _u8_image(img, (H, W))
-    cam = cam.detach().to(device=src.device, dtype=torch.float32).reshape(-1, 8).contiguous()
-    B, C, Hin, Win = src.shape
-    if dst.numel() == 0:
-        return dst
-    for b0, n in _call.slices(B):
-        c = cam if cam.shape[0] == 1 else cam[b0:b0 + n]
-        _call.call("gclm_undistort_image_u8", _lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], src[b0].data_ptr(), n,
-                   C, Hin, Win, H, W, interleaved, dst[b0].data_ptr(), _call.raw_stream(src.device), device=src.device)
-    return like_input(dst)
-
-
-def reproject_image_u8(src_model: str, src_cam: torch.Tensor, dst_model: str, dst_cam: torch.Tensor, rot: Optional[torch.Tensor],
-                       img: torch.Tensor, src_size, size, return_valid: bool = False):
-    """gclm_reproject_image_u8: reproject_image for a (B, C, Hin, Win) uint8 image on a HIP device, contiguous or
-    channels_last (read as it lies for C <= 4); the uint8 output has the input's memory format, the mask is as
-    reproject_image's."""
-    (Hs, Ws), (H, W) = (int(v) for v in src_size), (int(v) for v in size)
-    src, interleaved, dst, like_input = _u8_image(img, (H, W))
-    row = lambda t, k: t.detach().to(device=src.device, dtype=torch.float32).reshape(-1, k).contiguous()  # noqa: E731
-    src_cam, dst_cam, rot = row(src_cam, 8), row(dst_cam, 8), None if rot is None else row(rot, 9)
-    B, C, Hin, Win = src.shape
+    src, layout, dst, like_input = _warp_image(img, (H, W), "reproject_image")
+    dev, (B, C, Hin, Win) = src.device, src.shape
+    src_cam, dst_cam, rot = _rows(src_cam, 8, dev), _rows(dst_cam, 8, dev), None if rot is None else _rows(rot, 9, dev)
     if src_cam.shape[0] != dst_cam.shape[0] or src_cam.shape[0] not in (1, B) or (rot is not None and rot.shape[0] not in (1, B)):
         raise ValueError(f"camera batches {src_cam.shape[0]} and {dst_cam.shape[0]} must be equal and, as the rotation batch "
                          f"{None if rot is None else rot.shape[0]}, 1 or {B}")
     valid = torch.empty((B, H, W), dtype=torch.uint8, device=src.device) if return_valid else None
     if dst.numel() > 0:
-        at = lambda t, b0, n: None if t is None else (t if t.shape[0] == 1 else t[b0:b0 + n]).data_ptr()  # noqa: E731
         for b0, n in _call.slices(B):
-            _call.call("gclm_reproject_image_u8", _lib.CAMERA_MODEL_IDS[src_model], at(src_cam, b0, n),
-                       _lib.CAMERA_MODEL_IDS[dst_model], at(dst_cam, b0, n), 1 if src_cam.shape[0] == 1 else n, at(rot, b0, n),
-                       1 if rot is None or rot.shape[0] == 1 else n, src[b0].data_ptr(), n, C, Hin, Win, Hs, Ws, H, W, interleaved,
-                       dst[b0].data_ptr(), None if valid is None else valid[b0].data_ptr(), _call.raw_stream(src.device),
-                       device=src.device)
+            _call.call("gclm_reproject_image_u8" if src.dtype == torch.uint8 else "gclm_reproject_image",
+                       _lib.CAMERA_MODEL_IDS[src_model], _rows_at(src_cam, b0, n)[0], _lib.CAMERA_MODEL_IDS[dst_model],
+                       *_rows_at(dst_cam, b0, n), *_rows_at(rot, b0, n), src[b0].data_ptr(), n, C, Hin, Win, Hs, Ws, H, W, *layout,
+                       dst[b0].data_ptr(), _call.ptr_at(valid, b0), _call.raw_stream(src.device), device=src.device)
     elif valid is not None:
         valid.zero_()
     dst = like_input(dst)
@@ -248,18 +218,16 @@ def render_from_pano(camera_model: str, cam: torch.Tensor, rot: torch.Tensor, pa
     if any(p.device != dev or p.shape[0] != C for p in panos):
         raise ValueError("every panorama must live on one device and carry the same number of channels")
     H, W = int(size[0]), int(size[1])
-    cam = cam.detach().to(device=dev, dtype=torch.float32).reshape(-1, 8).contiguous()
-    rot = rot.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3, 3).contiguous()
+    cam, rot = _rows(cam, 8, dev), _rows(rot, 9, dev)
     if cam.shape[0] not in (1, n) or rot.shape[0] != n:
         raise ValueError(f"camera batch {cam.shape[0]} must be 1 or {n}, rotations {rot.shape[0]} must be {n}")
     dst = torch.empty((n, C, H, W), device=dev, dtype=torch.float32)
     if dst.numel() == 0:
         return dst
     for i0, m in _call.slices(n):
-        c = cam if cam.shape[0] == 1 else cam[i0:i0 + m]
         srcs = (ctypes.c_void_p * m)(*(p.data_ptr() for p in panos[i0:i0 + m]))
         hw = (ctypes.c_int * (2 * m))(*(v for p in panos[i0:i0 + m] for v in p.shape[1:]))
-        _call.call("gclm_render_from_pano", _lib.CAMERA_MODEL_IDS[camera_model], c.data_ptr(), c.shape[0], rot[i0].data_ptr(),
+        _call.call("gclm_render_from_pano", _lib.CAMERA_MODEL_IDS[camera_model], *_rows_at(cam, i0, m), rot[i0].data_ptr(),
                    srcs, hw, m, C, H, W, dst[i0].data_ptr(), _call.raw_stream(dev), device=dev)
     return dst
 
@@ -289,6 +257,19 @@ def perspective_fields(camera_model: str, cam: torch.Tensor, grav: torch.Tensor,
     return u, lat
 
 
+def _field_planes(planes, B: int, dev):
+    """The predicted planes of a scoring call as its kernel reads them (None stays None; kept in the order given, which is
+    the order of the C arguments), and their (H, W): "up" holds two
+    planes per image, every other one, and all lie on `dev` at the size of the latitude field (of the up field without it)."""
+    planes = {k: None if t is None else _call.dev_f32(t, k) for k, t in planes.items()}
+    H, W = (planes["up"] if planes["lat"] is None else planes["lat"]).shape[-2:]
+    for k, t in planes.items():
+        want = B * H * W * (2 if k == "up" else 1)
+        if t is not None and (t.numel() != want or t.shape[-2:] != (H, W) or t.device != dev):
+            raise ValueError(f"`{k}` {tuple(t.shape)} on {t.device} does not fit {B} images of {H} x {W} on {dev}")
+    return planes, H, W
+
+
 def field_errors(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: Optional[torch.Tensor] = None,
                  lat: Optional[torch.Tensor] = None, up_conf: Optional[torch.Tensor] = None,
                  lat_conf: Optional[torch.Tensor] = None, thresholds=(1.0, 3.0, 5.0, 10.0), return_errors: bool = False):
@@ -304,13 +285,7 @@ def field_errors(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: O
         raise ValueError("a confidence needs its field")
     cam, grav = _call.dev_f32(cam, "cam").reshape(-1, 8), _call.dev_f32(grav, "grav").reshape(-1, 3)
     dev, B = cam.device, cam.shape[0]
-    planes = {"up": up, "lat": lat, "up_conf": up_conf, "lat_conf": lat_conf}
-    planes = {k: None if t is None else _call.dev_f32(t, k) for k, t in planes.items()}
-    H, W = (planes["up"] if lat is None else planes["lat"]).shape[-2:]
-    for k, t in planes.items():
-        want = B * H * W * (2 if k == "up" else 1)
-        if t is not None and (t.numel() != want or t.shape[-2:] != (H, W) or t.device != dev):
-            raise ValueError(f"`{k}` {tuple(t.shape)} on {t.device} does not fit {B} images of {H} x {W} on {dev}")
+    planes, H, W = _field_planes({"up": up, "lat": lat, "up_conf": up_conf, "lat_conf": lat_conf}, B, dev)
     if grav.shape[0] != B or grav.device != dev:
         raise ValueError(f"camera batch {B} and gravity batch {grav.shape[0]} must be equal and on one device")
     thr = [float(t) for t in thresholds]
@@ -324,12 +299,10 @@ def field_errors(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: O
     ws_bytes = int(lib.gclm_field_errors_workspace(min(B, _call.MAX_CALL), H, W, len(thr)))
     ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=dev)
     c_thr = (_lib.C.c_float * len(thr))(*thr)
-    at = lambda t, b0: None if t is None else t[b0].data_ptr()  # noqa: E731
     for b0, n in _call.slices(B):
         _call.call("gclm_field_errors", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, H, W,
-                   at(planes["up"], b0), at(planes["lat"], b0), at(planes["up_conf"], b0), at(planes["lat_conf"], b0), len(thr),
-                   c_thr, ws.data_ptr(), ws_bytes, stats[b0].data_ptr(), at(up_err, b0), at(lat_err, b0), _call.raw_stream(dev),
-                   device=dev)
+                   *(_call.ptr_at(t, b0) for t in planes.values()), len(thr), c_thr, ws.data_ptr(), ws_bytes, stats[b0].data_ptr(),
+                   _call.ptr_at(up_err, b0), _call.ptr_at(lat_err, b0), _call.raw_stream(dev), device=dev)
     return stats, up_err, lat_err
 
 
@@ -355,13 +328,7 @@ def hypothesis_scores(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, 
             or grav.device != cam.device:
         raise ValueError(f"cameras {tuple(cam.shape)} and gravities {tuple(grav.shape)} must be (B, N, 8) and (B, N, 3) on one device")
     dev, (B, N) = cam.device, cam.shape[:2]
-    planes = {"up": up, "lat": lat, "up_conf": up_conf, "lat_conf": lat_conf, "mask": mask}
-    planes = {k: None if t is None else _call.dev_f32(t, k) for k, t in planes.items()}
-    H, W = (planes["up"] if lat is None else planes["lat"]).shape[-2:]
-    for k, t in planes.items():
-        want = B * H * W * (2 if k == "up" else 1)
-        if t is not None and (t.numel() != want or t.shape[-2:] != (H, W) or t.device != dev):
-            raise ValueError(f"`{k}` {tuple(t.shape)} on {t.device} does not fit {B} images of {H} x {W} on {dev}")
+    planes, H, W = _field_planes({"up": up, "lat": lat, "up_conf": up_conf, "lat_conf": lat_conf, "mask": mask}, B, dev)
     scores = cam.new_empty((B, N, 3))
     best = torch.empty((B,), dtype=torch.int32, device=dev)
     if B * N == 0 or H * W == 0:
@@ -371,12 +338,11 @@ def hypothesis_scores(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, 
     lib = _lib.load()
     ws_bytes = int(lib.gclm_hypothesis_scores_workspace(min(B, _call.MAX_CALL), N, H, W))
     ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=dev)
-    at = lambda t, b0: None if t is None else t[b0].data_ptr()  # noqa: E731
     for b0, n in _call.slices(B):
         _call.call("gclm_hypothesis_scores", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, N, H, W,
-                   at(planes["up"], b0), at(planes["lat"], b0), at(planes["up_conf"], b0), at(planes["lat_conf"], b0),
-                   at(planes["mask"], b0), float(up_threshold), float(lat_threshold), float(up_weight), float(lat_weight),
-                   ws.data_ptr(), ws_bytes, scores[b0].data_ptr(), best[b0].data_ptr(), _call.raw_stream(dev), device=dev)
+                   *(_call.ptr_at(t, b0) for t in planes.values()), float(up_threshold), float(lat_threshold), float(up_weight),
+                   float(lat_weight), ws.data_ptr(), ws_bytes, scores[b0].data_ptr(), best[b0].data_ptr(), _call.raw_stream(dev),
+                   device=dev)
     return scores, best
 
 
@@ -406,9 +372,8 @@ def rpf_hypotheses(up: torch.Tensor, lat: Optional[torch.Tensor] = None, prior_f
         raise ValueError(f"samples per image must lie in 1..{_lib.RPF_MAX_SAMPLES} (got {n})")
     cam, grav = up.new_empty((B, n * Rn, 8)), up.new_empty((B, n * Rn, 3))
     drawn = torch.empty((B, n, 3, 2), dtype=torch.int32, device=dev) if samples is None else None
-    at = lambda t, b0: None if t is None else t[b0].data_ptr()  # noqa: E731
     for b0, m in _call.slices(B):
-        _call.call("gclm_rpf_hypotheses", up[b0].data_ptr(), at(lat, b0), None if prior is None else prior[b0:].data_ptr(),
-                   at(samples, b0), int(seed) & (2 ** 64 - 1), int(first_index) + b0, m, n, H, W, cam[b0].data_ptr(), grav[b0].data_ptr(),
-                   at(drawn, b0), _call.raw_stream(dev), device=dev)
+        _call.call("gclm_rpf_hypotheses", up[b0].data_ptr(), _call.ptr_at(lat, b0), _call.ptr_at(prior, b0),
+                   _call.ptr_at(samples, b0), int(seed) & (2 ** 64 - 1), int(first_index) + b0, m, n, H, W, cam[b0].data_ptr(),
+                   grav[b0].data_ptr(), _call.ptr_at(drawn, b0), _call.raw_stream(dev), device=dev)
     return cam, grav, samples if samples is not None else drawn

@@ -2,11 +2,13 @@
 working tree?  (Round 6 pruned the closed A/B switches from the hot file; identical device assembly means identical bits and
 identical speed by construction -- stronger than the ISA statistics and than any measured A/B.)
 
-usage: python scripts/asm_equal.py [-v] REV [FILE=gclm_pass.hip ...] [-- FILE ...]
+usage: python scripts/asm_equal.py [-v] [--rename REGEX=REPLACEMENT ...] REV [FILE=gclm_pass.hip ...] [-- FILE ...]
 The files before `--` are taken at REV, those after it from the working tree (none: the same names), so code that moved
 between files is followed: `asm_equal.py REV gclm_update.hip -- gclm_update.hip gclm_fields.hip gclm_synth.hip`.  Several
 files are always compared symbol by symbol over the union of their symbols, and the report names every symbol that differs
 or exists on one side only (-v: with the first lines of its diff); exit status 0 when there is none.
+--rename (any number): re.sub(REGEX, REPLACEMENT) on every assembly line of REV before the comparison, for a kernel whose
+symbol changed (a new template argument, a new trailing kernel argument) and whose code should not have.
 Compiles each file of both trees with the Makefile's flags to gfx950 assembly (-S --cuda-device-only), drops comments, debug /
 file directives and the compilation-unit id symbol (a hash of the source text), and compares the rest line by line.
 Where the two trees emit the same kernels in another order (the host's dispatcher decides the order of instantiation), the
@@ -25,13 +27,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 PASS = ["-fno-slp-vectorize", "-mllvm", "-disable-vector-combine"]
 
 
-def assembly(tree, name):
+def assembly(tree, name, renames=()):
     out = tempfile.mktemp(suffix=".s")
     flags = FLAGS + (PASS if name == "gclm_pass.hip" else [])
     subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-o", out, os.path.join(tree, "geocalib_amd", "csrc", name)], check=True,
                    capture_output=True)
     lines = []
     for ln in open(out):
+        for pattern, replacement in renames:
+            ln = re.sub(pattern, replacement, ln)
         directive = ln.lstrip().startswith(".") and not re.match(r"\.L\w+:", ln)      # (a local label's comment names its loop)
         ln = ln.rstrip() if directive else ln.split(";")[0].rstrip()
         if not ln.strip() or re.match(r"\s*\.(file|loc|ident|cfi|section\s+\.debug)", ln) or "__hip_cuid_" in ln:
@@ -71,11 +75,11 @@ def blocks(lines):
     return out
 
 
-def union(tree, names):
+def union(tree, names, renames=()):
     """({symbol: lines} over the files, {file-level block: lines}, assembly lines, kernels, source lines) of `names` in `tree`."""
     syms, per_file, n_asm, kernels, n_src = {}, {}, 0, 0, 0
     for name in names:
-        lines = assembly(tree, name)
+        lines = assembly(tree, name, renames)
         n_asm += len(lines)
         kernels += sum(1 for ln in lines if ln.strip().startswith(".amdhsa_kernel"))
         n_src += sum(1 for _ in open(os.path.join(tree, "geocalib_amd", "csrc", name)))
@@ -94,6 +98,11 @@ def main():
     args = sys.argv[1:]
     verbose = "-v" in args
     args = [x for x in args if x != "-v"]
+    renames = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
     rev, rest = args[0], args[1:]
     old_names = rest[:rest.index("--")] if "--" in rest else rest
     old_names = old_names or ["gclm_pass.hip"]
@@ -102,7 +111,7 @@ def main():
         for path in ("geocalib_amd/csrc", "include"):
             tar = subprocess.run(["git", "-C", ROOT, "archive", rev, path], check=True, capture_output=True).stdout
             subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
-        sa, fa, asm_a, kernels, src_a = union(old, old_names)
+        sa, fa, asm_a, kernels, src_a = union(old, old_names, renames)
     sb, fb, asm_b, _, src_b = union(ROOT, new_names)
     if old_names == new_names:                     # the same files: their heads and tails must agree as well
         sa.update(fa)
@@ -113,6 +122,8 @@ def main():
     print(f"{' '.join(old_names)} at {rev} ({src_a} source lines) vs {' '.join(new_names)} in the working tree ({src_b} source "
           f"lines): {asm_a} / {asm_b} assembly lines, {kernels} kernels, {len(sa)} / {len(sb)} blocks compared by name: "
           f"{'IDENTICAL' if same else f'{len(sa) - len(differ) - sum(k in sa for k in only)} IDENTICAL, {len(differ)} DIFFERENT'}")
+    for pattern, replacement in renames:           # (a report says what it compared: its renames can be given again as printed)
+        print(f"    --rename '{pattern}={replacement}'")
     for k in only:
         print("    only in", rev if k in sa else "the working tree", ":", k)
     import difflib

@@ -116,6 +116,56 @@ def test_undistort_image(rec):
     assert rec.calls == [("gclm_undistort_image", (2, p(cam), 2, p(img), 2, 1, 2, 2, 2, 2, p(dst), STREAM))]
 
 
+def _byte_images():
+    """(image, layout flag): a contiguous uint8 image and a channels_last one of C = 3, which the wrappers read as it lies."""
+    planar = torch.randint(0, 256, (2, 3, 2, 2), dtype=torch.uint8)
+    return [(planar, 0), (planar.contiguous(memory_format=torch.channels_last), 1)]
+
+
+def test_undistort_image_picks_the_byte_entry_and_its_layout_flag(rec):
+    cam, _ = _cameras(2)
+    for img, interleaved in _byte_images():
+        del rec.calls[:]
+        dst = fields.undistort_image("radial", cam, img, (2, 2))
+        assert rec.calls == [("gclm_undistort_image_u8", (2, p(cam), 2, p(img), 2, 3, 2, 2, 2, 2, interleaved, p(dst), STREAM))]
+        assert dst.dtype == torch.uint8 and dst.shape == (2, 3, 2, 2) and dst.stride() == img.stride()
+    with pytest.raises(RuntimeError):
+        fields.undistort_image("radial", cam, torch.zeros(2, 3, 2, 2, dtype=torch.float64), (2, 2))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.uint8])
+def test_undistort_image_hands_over_the_camera_rows_it_has_for_the_entry_to_refuse(rec, dtype):
+    """A camera batch that is neither 1 nor B reaches the entry as the number of rows behind the pointer, never as the image
+    count: the entry refuses cam_batch != 1, B (tests/test_undistort_abi.py, test_u8_image_abi.py), and the refusal surfaces."""
+    cam, _ = _cameras(2)
+    img = torch.zeros(4, 1, 2, 2, dtype=dtype)
+    rec.rc = -3
+    with pytest.raises(_lib.GclmError, match=r"gclm_undistort_image\w* failed \(-3\)"):
+        fields.undistort_image("radial", cam, img, (2, 2))
+    (_, args), = rec.calls
+    assert args[:5] == (2, p(cam), 2, p(img), 4)
+
+
+def test_reproject_image_picks_the_entry_of_the_dtype_and_its_layout_flag(rec):
+    cam, _ = _cameras(2)
+    rot = torch.eye(3).repeat(2, 1, 1)
+    img = torch.rand(2, 3, 2, 2)
+    dst, valid = fields.reproject_image("radial", cam, "pinhole", cam[:, :], rot[:1], img, (2, 2), (2, 2), return_valid=True)
+    (name, args), = rec.calls
+    assert name == "gclm_reproject_image" and args[:7] == (2, p(cam), 0, p(cam), 2, p(rot), 1)
+    assert args[7:] == (p(img), 2, 3, 2, 2, 2, 2, 2, 2, p(dst), args[-2], STREAM) and valid.dtype == torch.bool
+    for img, interleaved in _byte_images():
+        del rec.calls[:]
+        dst = fields.reproject_image("radial", cam[:1], "pinhole", cam[:1], None, img, (2, 2), (2, 2))
+        assert rec.calls == [("gclm_reproject_image_u8", (2, p(cam), 0, p(cam), 1, None, 1, p(img), 2, 3, 2, 2, 2, 2, 2, 2,
+                                                          interleaved, p(dst), None, STREAM))]
+        assert dst.dtype == torch.uint8 and dst.stride() == img.stride()
+    with pytest.raises(RuntimeError):
+        fields.reproject_image("radial", cam, "pinhole", cam, None, torch.zeros(2, 3, 2, 2, dtype=torch.int16), (2, 2), (2, 2))
+    with pytest.raises(ValueError, match="camera batches 2 and 1 must be equal and, as the rotation batch None, 1 or 2"):
+        fields.reproject_image("radial", cam, "pinhole", cam[:1], None, img, (2, 2), (2, 2))
+
+
 def test_render_from_pano(rec):
     cam, _ = _cameras(2)
     rot, pano = torch.eye(3).repeat(2, 1, 1), torch.rand(1, 2, 2)

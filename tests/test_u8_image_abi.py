@@ -6,6 +6,7 @@ uint8 CPU image are the rounded, clamped float32 composition in the input's memo
 every model and layout without scratch or LDS, beside an unchanged set of float kernels."""
 import ctypes as C
 import os
+import re
 
 import pytest
 import torch
@@ -240,21 +241,24 @@ VGPR_MAX = {("undistort", 0): 24, ("undistort", 1): 28, ("reproject", 0): 24, ("
 def test_byte_kernels_exist_for_every_model_and_layout_without_scratch(tmp_path):
     from test_kernel_audit import kernel_metadata
     k = kernel_metadata(tmp_path)
-    und = {n: v for n, v in k.items() if "undistort_u8_kernel" in n}
-    rep = {n: v for n, v in k.items() if "reproject_u8_kernel" in n}
+    # the byte instantiations of the one kernel template per warp: element type `h` (unsigned char), then the layout
+    und = {n: v for n, v in k.items() if re.search(r"undistort_image_kernelILi\dEhLb\dEEEv", n)}
+    rep = {n: v for n, v in k.items() if re.search(r"reproject_kernelILi\dELi\dELb\dEhLb\dEEEv", n)}
     assert len(und) == 8 and len(rep) == 64, (sorted(und), sorted(rep))
     for il in range(2):
         for m in range(4):
-            v = [v for n, v in und.items() if f"undistort_u8_kernelILi{m}ELb{il}E" in n]
+            v = [v for n, v in und.items() if f"undistort_image_kernelILi{m}EhLb{il}E" in n]
             assert len(v) == 1 and v[0]["vgpr"] <= VGPR_MAX[("undistort", il)], (m, il, v)
             for t in range(4):
                 for r in range(2):
-                    v = [v for n, v in rep.items() if f"reproject_u8_kernelILi{m}ELi{t}ELb{r}ELb{il}E" in n]
+                    v = [v for n, v in rep.items() if f"reproject_kernelILi{m}ELi{t}ELb{r}EhLb{il}E" in n]
                     assert len(v) == 1 and v[0]["vgpr"] <= VGPR_MAX[("reproject", il)], (m, t, r, il, v)
     assert all(v["scratch"] == 0 and v["lds"] == 0 for v in {**und, **rep}.values()), {**und, **rep}
-    print("most VGPRs:", {(name, il): max(v["vgpr"] for n, v in group.items() if f"ELb{il}EEEv" in n)
+    print("most VGPRs:", {(name, il): max(v["vgpr"] for n, v in group.items() if f"EhLb{il}EEEv" in n)
                           for name, group in (("undistort", und), ("reproject", rep)) for il in range(2)})
     # the symbol counts the existing audits pin are what they were
     count = lambda s: sum(s in n for n in k)  # noqa: E731
-    assert count("reproject_kernel") == 32 and count("undistort_image_kernel") == 4
+    float_count = lambda s: sum(bool(re.search(s + r"\w*EfLb0EEEv", n)) for n in k)  # noqa: E731
+    assert float_count("reproject_kernelILi") == 32 and float_count("undistort_image_kernelILi") == 4
+    assert count("reproject_kernel") == 32 + 64 and count("undistort_image_kernel") == 4 + 8
     assert count("sweep_kernelILi") == 100 and count("fused_step_kernelILi") == 56
