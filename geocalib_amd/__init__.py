@@ -8,6 +8,7 @@ Public surface (mirrors the reference's geocalib package for this path):
     metrics                             siclib/models/utils/metrics.py  (+ perspective_field_metrics: fields against a calibration,
                                         rank_calibrations: N candidate calibrations per image against its fields)
     RPFSolver, solve_rpf                siclib/models/optimization/ransac.py  (the three-pixel minimal solver and RANSAC over it)
+    viz                                 geocalib/interactive_demo.py: render_frame  (draw_perspective_fields: the fields drawn over an image)
 """
 from .camera import BaseCamera, Pinhole, Radial, SimpleDivisional, SimpleRadial, camera_models  # noqa: F401
 from .gravity import Gravity  # noqa: F401
@@ -15,5 +16,6 @@ from .lm_optimizer import LMOptimizer, get_trivial_estimation  # noqa: F401
 from .extractor import GeoCalib  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402
 from .ransac import RPFSolver, solve_rpf  # noqa: F401,E402
+from . import viz  # noqa: F401,E402
 
 __version__ = "0.1.0"

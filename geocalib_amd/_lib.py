@@ -53,6 +53,19 @@ class GclmConfig(C.Structure):
         return cfg
 
 
+OVERLAY_LAYERS = {"heat": 1, "tint": 2, "contours": 4, "horizon": 8, "arrows": 16}     # enum gclm_overlay_layer
+
+
+class GclmOverlayStyle(C.Structure):
+    """struct gclm_overlay_style (include/gclm.h)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("layers", C.c_uint32), ("heat_alpha", C.c_float), ("tint_alpha", C.c_float),
+                ("heat_lo", C.c_float), ("heat_hi", C.c_float), ("levels", C.c_int32), ("line_halfwidth", C.c_float),
+                ("arrow_step", C.c_int32), ("arrow_x0", C.c_int32), ("arrow_y0", C.c_int32), ("arrow_length", C.c_float),
+                ("arrow_halfwidth", C.c_float), ("arrow_tip", C.c_float), ("horizon_rgba", C.c_ubyte * 4),
+                ("arrow_rgba", C.c_ubyte * 4)]
+
+
 class GclmError(RuntimeError):
     """A gclm_* entry point returned a non-zero code."""
 
@@ -97,6 +110,10 @@ _SIGNATURES = {
                                           _P]),
     "gclm_reproject_image_u8": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "gclm_draw_fields": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                   C.POINTER(GclmOverlayStyle), _P, _P]),
+    "gclm_draw_fields_u8": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                      C.POINTER(GclmOverlayStyle), _P, _P]),
     "gclm_perspective_fields": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gclm_field_errors_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gclm_field_errors": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float), _P,

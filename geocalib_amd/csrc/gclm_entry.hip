@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the four render kernels, the field errors, the hypothesis scores, the minimal solver, the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the five render kernels, the field errors, the hypothesis scores, the minimal solver, the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -52,6 +52,46 @@ int reproject_image(int src_model, const float* d_src_cam, int dst_model, const 
     return launched(launch_reproject_image(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C, Hin,
                                            Win, Hs, Ws, H, W, interleaved != 0, dwords, d_dst, d_valid,
                                            static_cast<hipStream_t>(stream)));
+}
+
+// gclm_draw_fields / gclm_draw_fields_u8: the one check of both, plain conditions first (the style among them), then the
+// ranges.  The arrow geometry is held to its conditions only where the arrow layer is on: the demo's defaults violate the
+// reach condition on portrait frames, and a caller who draws no arrows must not be refused for them.
+constexpr uint32_t kOverlayLayers = GCLM_OVERLAY_HEAT | GCLM_OVERLAY_TINT | GCLM_OVERLAY_CONTOURS | GCLM_OVERLAY_HORIZON | GCLM_OVERLAY_ARROWS;
+bool unit_interval(float v) { return v >= 0.f && v <= 1.f; }                 // (false for NaN)
+bool finite_nonneg(float v) { return v >= 0.f && v <= FLT_MAX; }
+
+template <typename T>
+int draw_fields(int camera_model, const float* d_cam, const float* d_grav, int cal_batch, const T* d_src, int B, int C, int H, int W,
+                int interleaved, const float* d_conf, const unsigned char* d_palette, const unsigned char* d_heat_palette,
+                const gclm_overlay_style* style, T* d_dst, void* stream) {
+    if (!d_cam || !d_grav || !d_src || !d_dst || !style || !known_model(camera_model) || B < 1 || B > kMaxCallImages) return -3;
+    if ((C != 3 && C != 4) || H < 1 || W < 1 || !tile_grid_fits(H, W) || (cal_batch != 1 && cal_batch != B)) return -3;
+    if (interleaved != 0 && interleaved != 1) return -3;
+    const gclm_overlay_style st = *style;
+    if (st.struct_size != (int32_t)sizeof(gclm_overlay_style) || (st.layers & ~kOverlayLayers)) return -3;
+    if (!unit_interval(st.heat_alpha) || !unit_interval(st.tint_alpha)) return -3;
+    if (!(fabsf(st.heat_lo) <= FLT_MAX) || !(fabsf(st.heat_hi) <= FLT_MAX) || !(st.heat_hi > st.heat_lo)) return -3;
+    if (st.levels < 2 || ((st.layers & GCLM_OVERLAY_HORIZON) && st.levels % 2 == 0)) return -3;
+    if (!finite_nonneg(st.line_halfwidth) || !finite_nonneg(st.arrow_halfwidth) || !finite_nonneg(st.arrow_length)) return -3;
+    if (st.layers & GCLM_OVERLAY_ARROWS) {
+        if (st.arrow_step < 1 || st.arrow_x0 < 0 || st.arrow_y0 < 0 || !unit_interval(st.arrow_tip)) return -3;
+        if (!((double)st.arrow_length + st.arrow_halfwidth + 0.5 <= (double)st.arrow_step)) return -3;
+    }
+    if ((st.layers & GCLM_OVERLAY_HEAT) && (!d_conf || !d_heat_palette)) return -3;
+    if ((st.layers & (GCLM_OVERLAY_TINT | GCLM_OVERLAY_CONTOURS)) && !d_palette) return -3;
+    ArgCheck a;
+    a.writes(d_dst, elements<T>(B, C, H, W), alignof(T));
+    a.reads(d_cam, floats(cal_batch, 8), 4);
+    a.reads(d_grav, floats(cal_batch, 3), 4);
+    a.reads(d_src, elements<T>(B, C, H, W), alignof(T));
+    a.reads(d_conf, floats(B, H, W), 4);
+    a.reads(d_palette, 768);
+    a.reads(d_heat_palette, 768);
+    if (!a.pass()) return -3;
+    const bool dwords = interleaved && C == 4 && is_aligned(d_src, 4) && is_aligned(d_dst, 4);
+    return launched(launch_draw_fields(camera_model, d_cam, d_grav, cal_batch, d_src, B, C, H, W, interleaved != 0, dwords, d_conf,
+                                       d_palette, d_heat_palette, st, d_dst, static_cast<hipStream_t>(stream)));
 }
 }  // namespace
 
@@ -166,6 +206,20 @@ int gclm_reproject_image_u8(int src_model, const float* d_src_cam, int dst_model
                             int Ws, int H, int W, int interleaved, unsigned char* d_dst, unsigned char* d_valid, void* stream) {
     return reproject_image(src_model, d_src_cam, dst_model, d_dst_cam, cam_batch, d_rot, rot_batch, d_src, B, C, Hin, Win, Hs, Ws,
                            H, W, interleaved, d_dst, d_valid, stream);
+}
+
+int gclm_draw_fields(int camera_model, const float* d_cam, const float* d_grav, int cal_batch, const float* d_src, int B, int C,
+                     int H, int W, const float* d_conf, const unsigned char* d_palette, const unsigned char* d_heat_palette,
+                     const gclm_overlay_style* style, float* d_dst, void* stream) {
+    return draw_fields(camera_model, d_cam, d_grav, cal_batch, d_src, B, C, H, W, 0, d_conf, d_palette, d_heat_palette, style, d_dst,
+                       stream);
+}
+
+int gclm_draw_fields_u8(int camera_model, const float* d_cam, const float* d_grav, int cal_batch, const unsigned char* d_src, int B,
+                        int C, int H, int W, int interleaved, const float* d_conf, const unsigned char* d_palette,
+                        const unsigned char* d_heat_palette, const gclm_overlay_style* style, unsigned char* d_dst, void* stream) {
+    return draw_fields(camera_model, d_cam, d_grav, cal_batch, d_src, B, C, H, W, interleaved, d_conf, d_palette, d_heat_palette,
+                       style, d_dst, stream);
 }
 
 int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,

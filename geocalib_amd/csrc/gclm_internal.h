@@ -245,6 +245,13 @@ hipError_t launch_reproject_image(int src_model, const float* src_cam, int dst_m
                                   int Hs, int Ws, int H, int W, bool interleaved, bool dwords, T* dst,
                                   unsigned char* valid /* or nullptr */, hipStream_t s);
 
+// gclm_overlay.hip
+template <typename T>
+hipError_t launch_draw_fields(int camera_model, const float* cam, const float* grav, int cal_batch, const T* src, int B, int C, int H,
+                              int W, bool interleaved, bool dwords, const float* conf /* or nullptr */,
+                              const unsigned char* palette /* or nullptr */, const unsigned char* heat_palette /* or nullptr */,
+                              const gclm_overlay_style& style, T* dst, hipStream_t s);
+
 // gclm_metrics.hip
 size_t field_errors_workspace(int B, int H, int W, int n_thresholds);     // bytes of one call's partial records; 0: sizes out of range
 hipError_t launch_field_errors(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,

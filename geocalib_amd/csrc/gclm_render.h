@@ -214,6 +214,43 @@ __device__ __forceinline__ float persp_lat(const PerspRow& r, float u, float r2)
     return asinf(sl);
 }
 
+// t' = dt/dr2 of undistort_scale (gclm_overlay.hip: the latitude's gradient): pinhole 0; simple_radial -k1; radial
+// -k1 + 2 (3 k1^2 - k2) r2; simple_divisional -k1 t^2 with t as undistort_scale gives it.
+template <int MODEL>
+__device__ __forceinline__ float undistort_scale_dr2(float r2, float k1, float k2) {
+    if constexpr (MODEL == GCLM_PINHOLE) {
+        return 0.f;
+    } else if constexpr (MODEL == GCLM_SIMPLE_RADIAL) {
+        return -k1;
+    } else if constexpr (MODEL == GCLM_RADIAL) {
+        return -k1 + 2.f * (3.f * k1 * k1 - k2) * r2;
+    } else {
+        const float t = undistort_scale<MODEL>(r2, k1, k2);
+        return -k1 * t * t;
+    }
+}
+
+// Degrees of latitude per pixel at the pixel persp_lat is taken at: |grad_xy s| (180 / pi) / sqrt(1 - s_c^2), with s the sine
+// persp_lat takes asin of, s_c its clamped value, and grad s in closed form (include/gclm.h: gclm_draw_fields): grad_P s =
+// (g_xy - s P / n) / n for P = (u t, v t), n = |(P, 1)|;  dP/d(u, v) = t I + 2 t' (u, v)(u, v)^T;  d/dx = ifx d/du, d/dy = ify d/dv.
+// The first lines repeat persp_lat's, so that a kernel calling both evaluates them once.  A NaN stays NaN.
+template <int MODEL>
+__device__ __forceinline__ float persp_lat_slope(const PerspRow& r, float u, float r2, float ify) {
+    const float t = undistort_scale<MODEL>(r2, r.k1, r.k2), tp = undistort_scale_dr2<MODEL>(r2, r.k1, r.k2);
+    const float X = u * t, Y = r.v * t;
+    const float n = sqrtf(X * X + Y * Y + 1.f), in = 1.f / n;
+    const float sl = (X * r.a + Y * r.b + r.c) / n;
+    const float gX = (r.a - sl * X * in) * in, gY = (r.b - sl * Y * in) * in;
+    float du = t * gX, dv = t * gY;
+    if constexpr (MODEL != GCLM_PINHOLE) {
+        const float w = 2.f * tp * (u * gX + r.v * gY);
+        du += w * u, dv += w * r.v;
+    }
+    const float sx = du * r.ifx, sy = dv * ify;
+    const float sc = sl < -kLatHi ? -kLatHi : (sl > kLatHi ? kLatHi : sl);
+    return sqrtf(sx * sx + sy * sy) * 57.29577951308232f / sqrtf((1.f - sc) * (1.f + sc));
+}
+
 // What the kernels that score predicted fields share (gclm_metrics.hip: one calibration per image, gclm_hypotheses.hip: N
 // per image), so that both compile the same per-pixel functions: the vector load of a lane's pixels, the wave sum and the
 // masked up error (its formula is in gclm_metrics.hip's header).

@@ -51,7 +51,8 @@ extern "C" {
  * within 610; gclm_set_conf_pack, gclm_plan_conf_pack, gclm_conf_pack_bytes and gclm_conf_pack_fallbacks added, also within 610: large pinhole
  * batches keep their two confidence planes as one plane of 16-bit pairs, see gclm_set_conf_pack; gclm_rpf_hypotheses added, also
  * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks; gclm_reproject_image added, also within 610;
- * gclm_undistort_image_u8 and gclm_reproject_image_u8 added, also within 610: the two image calls for uint8 images).  gclm_create refuses a gclm_config whose first two fields do not
+ * gclm_undistort_image_u8 and gclm_reproject_image_u8 added, also within 610: the two image calls for uint8 images;
+ * gclm_draw_fields and gclm_draw_fields_u8 added, also within 610: the perspective fields drawn over an image).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -386,6 +387,70 @@ int gclm_reproject_image_u8(int src_model, const float* d_src_cam, int dst_model
  */
 int gclm_perspective_fields(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W,
                             int normalize_up, float* d_up, float* d_lat, void* stream);
+
+/*
+ * The perspective fields of a calibration drawn over a batch of images, in one pass that reads a frame once and writes it
+ * once: what the reference's demo shows (interactive_demo.py: plot_confidence, plot_latitude, draw_horizon_line,
+ * plot_vector_field; viz2d.plot_perspective_fields), stated per output pixel and antialiased.  It is NOT cv2's rasteriser bit
+ * for bit: end points are not truncated to integers, and the polylines of cv2.findContours are replaced by the distance to
+ * the isoline.
+ * gclm_draw_fields: d_src, d_dst (B, C, H, W) float32 planar, nominal range 0..1.  gclm_draw_fields_u8: bytes, interleaved = 0:
+ * (B, C, H, W), interleaved = 1: (B, H, W, C) (torch: channels_last).  C is 3 or 4; channel 3 is copied.  d_cam (cal_batch, 8)
+ * and d_grav (cal_batch, 3) as for gclm_perspective_fields, at the image's resolution, cal_batch 1 (shared) or B.  d_conf
+ * (B, H, W) float32 or NULL.  d_palette, d_heat_palette: (256, 3) bytes in the image's channel order, or NULL where no layer
+ * reads them.  `style` is host memory, read at call time.
+ * One pixel at integer centre (x, y), float32 throughout; colours are 0..255 for byte images and bytes / 255 for float images.
+ *   u, v, r2, t as for gclm_perspective_fields;  P = (u t, v t),  n = |(P, 1)|,  s = (P . (a, b) + c) / n,
+ *   s_c = clamp(s, -1 + 1e-6, 1 - 1e-6),  lat = asin(s_c) 180 / pi                                    (degrees)
+ *   grad_P s = ((a, b) - s P / n) / n,   dP/d(u, v) = t I + 2 t' (u, v)(u, v)^T,   d/dx = (d/du) / fx,  d/dy = (d/dv) / fy
+ *   g = |grad_xy s| (180 / pi) / sqrt((1 - s_c)(1 + s_c))                                 (degrees of latitude per pixel)
+ *   t' = dt/dr2: pinhole 0; simple_radial -k1; radial -k1 + 2 (3 k1^2 - k2) r2; simple_divisional -k1 t^2
+ *   pal(L, tau), tau in [0, 1]: with i = min(floor(255 tau), 254) and f = 255 tau - i, L[i] + (L[i + 1] - L[i]) f
+ * Layers, in this order, each out = out (1 - a) + colour a on channels 0..2:
+ *   heat     (needs d_conf, d_heat_palette): tau = (clamp(log10(max(conf, 1e-6)), lo, hi) - lo) / (hi - lo), a = heat_alpha
+ *   tint     (d_palette): tau = (lat + 90) / 180, a = tint_alpha
+ *   contours (d_palette): step = 180 / (levels - 1), k = rint((lat + 90) / step), d = |lat - (-90 + k step)| / max(g, 1e-4),
+ *            a = clamp(line_halfwidth + 0.5 - d, 0, 1), colour pal(palette, k / (levels - 1)); the level is evaluated as
+ *            (2 k - (levels - 1)) 90 / (levels - 1), one rounding relative to the level and exact at the horizon
+ *   horizon: a = clamp(line_halfwidth + 0.5 - |lat| / max(g, 1e-4), 0, 1), colour horizon_rgba
+ *   arrows:  anchors (arrow_x0 + i S, arrow_y0 + j S), i, j >= 0, inside the image, S = arrow_step; q = the unnormalised up
+ *            vector of gclm_perspective_fields at the anchor, e = q / |q|; the shaft runs from the anchor P0 to P1 = P0 + L e,
+ *            two tip segments of length arrow_tip L from P1 along (-e +- e_perp) / sqrt 2 (45 degrees back towards P0); d = the
+ *            distance from (x, y) to the nearest of the three segments, a = clamp(arrow_halfwidth + 0.5 - d, 0, 1), the largest
+ *            over the anchors, colour arrow_rgba.  L + arrow_halfwidth + 0.5 <= S is a condition of the call, so only the four
+ *            anchors of a pixel's cell can reach it.  An anchor with |q| < 1e-6 or a non-finite q draws nothing.
+ * A non-finite lat (tint), lat or g (contours, horizon) or confidence (heat) skips that layer for that pixel: a NaN
+ * calibration leaves the image unchanged.  With no layer on, the output is a byte-exact (float: bit-exact) copy.  The byte
+ * written is the float rounded to nearest, ties to even, saturated to 0..255.
+ * Returns -3 (before any HIP call) for a NULL d_cam, d_grav, d_src, d_dst or style, a model outside 0..3, B outside 1..65535,
+ * C not 3 or 4, H or W < 1, H * W > 2^31 - 1 (or a tile grid over 2^32 threads), cal_batch not 1 or B, interleaved not 0 or 1,
+ * a struct_size other than sizeof(gclm_overlay_style), unknown layer bits, an alpha outside [0, 1] or not finite, heat_hi <=
+ * heat_lo or either not finite, levels < 2 (or even with the horizon layer on), a negative or non-finite half-width or arrow
+ * length; with the arrow layer on: arrow_step < 1, a negative arrow_x0 or arrow_y0, arrow_tip outside [0, 1], or a violated
+ * reach condition; a layer whose palette or confidence plane is NULL; a float pointer off a 4-byte boundary (byte images
+ * carry no alignment requirement); or a destination that shares a byte with any range the call reads (drawing in place is
+ * not supported).  -10 if the launch fails.  Asynchronous on `stream`; no allocation; one launch.
+ */
+enum gclm_overlay_layer {
+    GCLM_OVERLAY_HEAT = 1, GCLM_OVERLAY_TINT = 2, GCLM_OVERLAY_CONTOURS = 4, GCLM_OVERLAY_HORIZON = 8, GCLM_OVERLAY_ARROWS = 16
+};
+typedef struct gclm_overlay_style {
+    int32_t struct_size;             /* sizeof(gclm_overlay_style) of the CALLER's header */
+    uint32_t layers;                 /* bit set of gclm_overlay_layer */
+    float heat_alpha, tint_alpha;    /* in [0, 1] */
+    float heat_lo, heat_hi;          /* range of log10(confidence) the heat palette spans */
+    int32_t levels;                  /* latitude levels from -90 to 90 degrees, >= 2 */
+    float line_halfwidth;            /* contours and horizon, pixels */
+    int32_t arrow_step, arrow_x0, arrow_y0;
+    float arrow_length, arrow_halfwidth, arrow_tip;
+    unsigned char horizon_rgba[4], arrow_rgba[4];     /* channels 0..2 in the image's channel order; [3] is not read */
+} gclm_overlay_style;
+int gclm_draw_fields(int camera_model, const float* d_cam, const float* d_grav, int cal_batch, const float* d_src, int B, int C,
+                     int H, int W, const float* d_conf, const unsigned char* d_palette, const unsigned char* d_heat_palette,
+                     const gclm_overlay_style* style, float* d_dst, void* stream);
+int gclm_draw_fields_u8(int camera_model, const float* d_cam, const float* d_grav, int cal_batch, const unsigned char* d_src, int B,
+                        int C, int H, int W, int interleaved, const float* d_conf, const unsigned char* d_palette,
+                        const unsigned char* d_heat_palette, const gclm_overlay_style* style, unsigned char* d_dst, void* stream);
 
 /*
  * How well predicted perspective fields agree with a calibration, per image, in one pass over the planes: the reference's
