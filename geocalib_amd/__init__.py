@@ -9,6 +9,8 @@ Public surface (mirrors the reference's geocalib package for this path):
                                         rank_calibrations: N candidate calibrations per image against its fields)
     RPFSolver, solve_rpf                siclib/models/optimization/ransac.py  (the three-pixel minimal solver and RANSAC over it)
     viz                                 geocalib/interactive_demo.py: render_frame  (draw_perspective_fields: the fields drawn over an image)
+    perspective_encoding                siclib/models/utils/perspective_encoding.py  (fields as classification bins; with
+                                        fields.pack_fields_from_logits: classification heads to fields in one pass)
 """
 from .camera import BaseCamera, Pinhole, Radial, SimpleDivisional, SimpleRadial, camera_models  # noqa: F401
 from .gravity import Gravity  # noqa: F401
@@ -17,5 +19,6 @@ from .extractor import GeoCalib  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402
 from .ransac import RPFSolver, solve_rpf  # noqa: F401,E402
 from . import viz  # noqa: F401,E402
+from . import perspective_encoding  # noqa: F401,E402
 
 __version__ = "0.1.0"

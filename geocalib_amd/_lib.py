@@ -20,7 +20,9 @@ MAX_RECALL_THRESHOLDS = 8
 RPF_MAX_SAMPLES = 1 << 24     # GCLM_RPF_MAX_SAMPLES: samples per image of one gclm_rpf_hypotheses call
 RPF_DRAW_SALT = 0x5250465F44524157     # GCLM_RPF_DRAW_SALT: what the in-kernel draw of gclm_rpf_hypotheses mixes into the seed
 HYPOTHESIS_CHUNK = 16         # GCLM_HYPOTHESIS_CHUNK: hypotheses scored per read of an image's planes (gclm_hypothesis_scores)
-ABI_VERSION = 610          # GCLM_VERSION of include/gclm.h this binding was written against
+LOGIT_DTYPE_IDS = {"float32": 0, "float16": 1, "bfloat16": 2}     # enum gclm_logit_dtype (gclm_pack_fields_bins)
+MAX_BINS = 2048               # GCLM_MAX_BINS: most bins of one head (gclm_pack_fields_bins)
+ABI_VERSION = 610         # GCLM_VERSION of include/gclm.h this binding was written against
 INFO = {"stop_at": 0, "initial_up_cost": 1, "initial_latitude_cost": 2, "initial_cost": 3,
         "final_up_cost": 4, "final_latitude_cost": 5, "final_cost": 6, "roll_uncertainty": 7,
         "pitch_uncertainty": 8, "gravity_uncertainty": 9, "focal_uncertainty": 10,
@@ -124,6 +126,8 @@ _SIGNATURES = {
     "gclm_rpf_hypotheses": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gclm_pack_fields": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "gclm_pack_fields_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gclm_pack_fields_bins": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                        _P, _P]),
     "gclm_synth_fields": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,
                                     _P, _P, _P, _P, _P, _P, _P]),
     "gclm_synth_fields_grouped": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,

@@ -71,7 +71,7 @@ private:
         uintptr_t lo, hi;
         bool hits(const Range& o) const { return lo < o.hi && o.lo < hi; }
     };
-    static constexpr int kMaxWrites = 4;      // gclm_field_errors: statistics, workspace and two maps
+    static constexpr int kMaxWrites = 5;      // gclm_pack_fields_bins: up, latitude, two confidences and sin(latitude)
     Range w_[kMaxWrites];
     int n_ = 0;
     bool ok_ = true, sealed_ = false;

@@ -184,6 +184,44 @@ int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const flo
                                nullptr, stream);
 }
 
+int gclm_pack_fields_bins(const void* d_up_logits, int up_bins, const void* d_lat_logits, int lat_bins, int logit_dtype,
+                          const float* d_up_table, const float* d_lat_table, const float* d_up_logconf,
+                          const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
+                          float* d_lat_conf, float* d_sin_lat, void* stream) {
+    if (!d_up_logits || !d_lat_logits || !d_up_table || !d_lat_table || !d_up || !d_lat || B < 0 || H <= 0 || W <= 0) return -3;
+    if (up_bins < 2 || up_bins > GCLM_MAX_BINS || lat_bins < 1 || lat_bins > GCLM_MAX_BINS) return -3;
+    if (logit_dtype != GCLM_LOGITS_F32 && logit_dtype != GCLM_LOGITS_F16 && logit_dtype != GCLM_LOGITS_BF16) return -3;
+    if ((d_up_logconf && !d_up_conf) || (d_lat_logconf && !d_lat_conf)) return -3;
+    // Every output keeps off every other plane of the call, with one exception: a log-confidence that IS its output is
+    // converted in place, lane by lane, and is not stated a second time as a range read.  A confidence output without its
+    // log-confidence is not written and names no range.
+    const size_t esize = logit_dtype == GCLM_LOGITS_F32 ? 4 : 2, px = floats(B, H, W);
+    float* const up_conf = d_up_logconf ? d_up_conf : nullptr;
+    float* const lat_conf = d_lat_logconf ? d_lat_conf : nullptr;
+    const float* const up_lc = d_up_logconf == up_conf ? nullptr : d_up_logconf;
+    const float* const lat_lc = d_lat_logconf == lat_conf ? nullptr : d_lat_logconf;
+    ArgCheck a;
+    a.writes(d_sin_lat, px, 4);
+    a.writes(d_up, mul_sat(px, 2), 4);
+    a.writes(d_lat, px, 4);
+    a.writes(up_conf, px, 4);
+    a.writes(lat_conf, px, 4);
+    a.reads(d_up_logits, mul_sat(elements<char>(B, up_bins, H, W), esize), esize);
+    a.reads(d_lat_logits, mul_sat(elements<char>(B, lat_bins, H, W), esize), esize);
+    a.reads(d_up_table, floats(up_bins, 2), 4);
+    a.reads(d_lat_table, floats(lat_bins), 4);
+    a.reads(up_lc, px, 4);
+    a.reads(lat_lc, px, 4);
+    if (!a.pass()) return -3;
+    bool vec = ((size_t)H * W) % (esize == 4 ? 4 : 8) == 0;
+    for (const void* p : {d_up_logits, d_lat_logits, (const void*)d_up_logconf, (const void*)d_lat_logconf, (const void*)d_up,
+                          (const void*)up_conf, (const void*)d_lat, (const void*)lat_conf, (const void*)d_sin_lat})
+        vec = vec && is_aligned(p, 16);
+    return launched(launch_pack_fields_bins(d_up_logits, up_bins, d_lat_logits, lat_bins, logit_dtype, d_up_table, d_lat_table,
+                                            d_up_logconf, d_lat_logconf, B, H, W, vec, d_up, up_conf, d_lat, lat_conf, d_sin_lat,
+                                            static_cast<hipStream_t>(stream)));
+}
+
 int gclm_undistort_image(int camera_model, const float* d_cam, int cam_batch, const float* d_src, int B, int C, int Hin, int Win,
                          int H, int W, float* d_dst, void* stream) {
     return undistort_image(camera_model, d_cam, cam_batch, d_src, B, C, Hin, Win, H, W, 0, d_dst, stream);

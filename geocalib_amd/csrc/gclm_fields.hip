@@ -1,5 +1,5 @@
 // gclm_fields.hip -- the steps before and after the path: the CNN-head epilogue that packs the planes a sweep reads
-// (gclm_pack_fields) and the bilinear upsampler of GeoCalib._post_process (gclm_upsample_fields).  Per-pixel streaming
+// (gclm_pack_fields; gclm_pack_fields_bins for classification heads) and the bilinear upsampler of GeoCalib._post_process (gclm_upsample_fields).  Per-pixel streaming
 // kernels; nothing here knows about the solve.
 #include "gclm_device.h"
 
@@ -67,6 +67,149 @@ __global__ void pack_fields_kernel(const float* __restrict__ up_raw, const float
                 if (up_lc) upc[(size_t)b * N + i] = c1[0];
                 if (lat_lc) latc[(size_t)b * N + i] = c2[0];
                 if (slat) slat[(size_t)b * N + i] = sl[0];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- classification heads (the same step, the other format)
+// UpDecoder / LatitudeDecoder with loss_type == "classification" (the original PerspectiveFields weights): the heads emit
+// Ku and Kl logits per pixel, the fields are the decodes of the per-pixel argmax.  ONE pass reads the Ku + Kl logit planes
+// once and writes the planes the sweep reads; a decode has one value per bin, so it is a gather from the caller's tables
+// (include/gclm.h: gclm_pack_fields_bins), staged in LDS once per workgroup -- no device cos or sin, the reference's bits.
+// Lanes run along pixels and the channel loop runs inside the lane: every channel read is a row of consecutive pixels, the
+// running maximum and its index never leave registers.  DT = the logits' type (gclm_logit_dtype); VEC = pixels per lane:
+// one 16-byte load per channel (4 floats, 8 halves) where the planes allow it, else 1.
+// slat: sin of the latitude just written, by the sweep's polynomial, as in pack_fields_kernel; a bin centre lies strictly
+// inside +-pi/2, so no range fold here either.
+typedef uint32_t bins_u4 __attribute__((ext_vector_type(4)));
+typedef float bins_f4 __attribute__((ext_vector_type(4)));
+template <int DT>
+using bins_elem = std::conditional_t<DT == GCLM_LOGITS_F32, float, uint16_t>;
+constexpr int bins_vec(int dt) { return dt == GCLM_LOGITS_F32 ? 4 : 8; }
+constexpr int kBinsUnroll = 8;      // channel loads in flight per lane
+
+// 16-bit logits widen to float exactly, so one comparison serves the three types
+template <int DT>
+__device__ __forceinline__ float bins_widen(uint32_t bits) {      // a float's 32 bits, or a half's 16 in the low half
+    if constexpr (DT == GCLM_LOGITS_F32) return __builtin_bit_cast(float, bits);
+    else if constexpr (DT == GCLM_LOGITS_BF16) return __builtin_bit_cast(float, bits << 16);
+    else return (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
+}
+// the values of one channel at the VEC pixels of unit i
+template <int DT, int VEC>
+__device__ __forceinline__ void bins_load(const bins_elem<DT>* __restrict__ plane, size_t i, float (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        v[0] = bins_widen<DT>((uint32_t)__builtin_bit_cast(std::conditional_t<DT == GCLM_LOGITS_F32, uint32_t, uint16_t>,
+                                                           __builtin_nontemporal_load(plane + i)));
+    } else {
+        const bins_u4 q = __builtin_nontemporal_load(reinterpret_cast<const bins_u4*>(plane) + i);
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            if constexpr (DT == GCLM_LOGITS_F32) v[k] = bins_widen<DT>(w[k]);
+            else v[k] = bins_widen<DT>((k & 1) ? w[k >> 1] >> 16 : w[k >> 1] & 0xffffu);
+        }
+    }
+}
+// torch.argmax's rule over the K planes of one image: the first index of the greatest value; a NaN is greater than everything
+// and the first NaN wins; all -inf gives 0.  A later x replaces the best only if the best is no NaN and x <= best is false.
+template <int DT, int VEC>
+__device__ __forceinline__ void bins_argmax(const bins_elem<DT>* __restrict__ logits, int K, size_t N, size_t i, int (&idx)[VEC]) {
+    float best[VEC], v[kBinsUnroll][VEC];
+    bins_load<DT, VEC>(logits, i, best);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) idx[k] = 0;
+    auto take = [&](const float (&x)[VEC], int c) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const bool t = !(x[k] <= best[k]) && best[k] == best[k];
+            best[k] = t ? x[k] : best[k];
+            idx[k] = t ? c : idx[k];
+        }
+    };
+    int c = 1;
+    for (; c + kBinsUnroll <= K; c += kBinsUnroll) {
+#pragma unroll
+        for (int u = 0; u < kBinsUnroll; ++u) bins_load<DT, VEC>(logits + (size_t)(c + u) * N, i, v[u]);
+#pragma unroll
+        for (int u = 0; u < kBinsUnroll; ++u) take(v[u], c + u);
+    }
+    for (; c < K; ++c) {
+        bins_load<DT, VEC>(logits + (size_t)c * N, i, v[0]);
+        take(v[0], c);
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void bins_load_f32(const float* p, size_t i, float (&v)[VEC]) {
+    if constexpr (VEC == 1) v[0] = p[i];
+    else {
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q) {
+            const bins_f4 t = __builtin_nontemporal_load(reinterpret_cast<const bins_f4*>(p) + i * (VEC / 4) + q);
+            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        }
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void bins_store_f32(float* p, size_t i, const float (&v)[VEC]) {
+    if constexpr (VEC == 1) p[i] = v[0];
+    else {
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q)
+            __builtin_nontemporal_store(bins_f4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]},
+                                        reinterpret_cast<bins_f4*>(p) + i * (VEC / 4) + q);
+    }
+}
+// (the log-confidences may be their own outputs, lane by lane: no __restrict__ on those four)
+template <int DT, int VEC>
+__global__ __launch_bounds__(256) void pack_bins_kernel(const bins_elem<DT>* __restrict__ up_logits, int Ku,
+                                                        const bins_elem<DT>* __restrict__ lat_logits, int Kl,
+                                                        const float* __restrict__ up_table, const float* __restrict__ lat_table,
+                                                        const float* up_lc, const float* lat_lc, int B, size_t N,
+                                                        float* __restrict__ up, float* upc, float* __restrict__ lat, float* latc,
+                                                        float* __restrict__ slat) {
+    extern __shared__ float bins_tab[];      // (Ku, 2) then (Kl)
+    float* const ltab = bins_tab + 2 * Ku;
+    for (int t = threadIdx.x; t < 2 * Ku; t += blockDim.x) bins_tab[t] = up_table[t];
+    for (int t = threadIdx.x; t < Kl; t += blockDim.x) ltab[t] = lat_table[t];
+    __syncthreads();
+    const size_t units = N / VEC;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const bins_elem<DT>* ul = up_logits + (size_t)b * Ku * N;
+        const bins_elem<DT>* ll = lat_logits + (size_t)b * Kl * N;
+        float* ox = up + (size_t)b * 2 * N;
+        const size_t plane = (size_t)b * N / VEC;      // in units: N is a multiple of VEC
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < units; i += (size_t)gridDim.x * blockDim.x) {
+            int ub[VEC], lb[VEC];
+            bins_argmax<DT, VEC>(ul, Ku, N, i, ub);
+            bins_argmax<DT, VEC>(ll, Kl, N, i, lb);
+            float vx[VEC], vy[VEC], vl[VEC], c[VEC];
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                vx[k] = bins_tab[2 * ub[k]];
+                vy[k] = bins_tab[2 * ub[k] + 1];
+                vl[k] = ltab[lb[k]];
+            }
+            bins_store_f32<VEC>(ox, i, vx);
+            bins_store_f32<VEC>(ox + N, i, vy);
+            bins_store_f32<VEC>(lat, plane + i, vl);
+            if (slat) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) c[k] = dev::sin_halfpi(vl[k]);
+                bins_store_f32<VEC>(slat, plane + i, c);
+            }
+            if (up_lc) {
+                bins_load_f32<VEC>(up_lc, plane + i, c);
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) c[k] = 1.0f / (1.0f + expf(-c[k]));      // pack_fields_kernel's expression
+                bins_store_f32<VEC>(upc, plane + i, c);
+            }
+            if (lat_lc) {
+                bins_load_f32<VEC>(lat_lc, plane + i, c);
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) c[k] = 1.0f / (1.0f + expf(-c[k]));
+                bins_store_f32<VEC>(latc, plane + i, c);
             }
         }
     }
@@ -458,6 +601,35 @@ hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const flo
     const dim3 grid(bx, B < 4096 ? B : 4096), block(256);
     if (vec4) hipLaunchKernelGGL(pack_fields_kernel<4>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc, slat);
     else hipLaunchKernelGGL(pack_fields_kernel<1>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc, slat);
+    return hipGetLastError();
+}
+
+// `vec`: every plane of the call is 16-byte aligned and H * W is a multiple of the type's pixels per lane (the entry decides).
+template <int DT, int VEC>
+static void launch_pack_bins_as(const void* up_logits, int Ku, const void* lat_logits, int Kl, const float* up_table,
+                                const float* lat_table, const float* up_lc, const float* lat_lc, int B, size_t N, float* up,
+                                float* upc, float* lat, float* latc, float* slat, hipStream_t s) {
+    const size_t units = N / VEC;
+    const int bx = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
+    const dim3 grid(bx, B < 4096 ? B : 4096), block(256);
+    hipLaunchKernelGGL((pack_bins_kernel<DT, VEC>), grid, block, (size_t)(2 * Ku + Kl) * sizeof(float), s,
+                       static_cast<const bins_elem<DT>*>(up_logits), Ku, static_cast<const bins_elem<DT>*>(lat_logits), Kl, up_table,
+                       lat_table, up_lc, lat_lc, B, N, up, upc, lat, latc, slat);
+}
+hipError_t launch_pack_fields_bins(const void* up_logits, int Ku, const void* lat_logits, int Kl, int dtype, const float* up_table,
+                                   const float* lat_table, const float* up_lc, const float* lat_lc, int B, int H, int W, bool vec,
+                                   float* up, float* upc, float* lat, float* latc, float* slat, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    const size_t N = (size_t)H * W;
+    auto go = [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (vec) launch_pack_bins_as<DT, bins_vec(DT)>(up_logits, Ku, lat_logits, Kl, up_table, lat_table, up_lc, lat_lc, B, N, up, upc, lat, latc, slat, s);
+        else launch_pack_bins_as<DT, 1>(up_logits, Ku, lat_logits, Kl, up_table, lat_table, up_lc, lat_lc, B, N, up, upc, lat, latc, slat, s);
+    };
+    if (dtype == GCLM_LOGITS_F32) go(std::integral_constant<int, GCLM_LOGITS_F32>{});
+    else if (dtype == GCLM_LOGITS_F16) go(std::integral_constant<int, GCLM_LOGITS_F16>{});
+    else if (dtype == GCLM_LOGITS_BF16) go(std::integral_constant<int, GCLM_LOGITS_BF16>{});
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -221,6 +221,9 @@ hipError_t launch_upsample_multi(const UpsampleMulti& m, int h, int w, int H, in
 hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const float* lat_raw, const float* lat_lc,
                               int B, int H, int W, bool vec4, float* up, float* upc, float* lat, float* latc,
                               float* slat /* or nullptr */, hipStream_t s);
+hipError_t launch_pack_fields_bins(const void* up_logits, int Ku, const void* lat_logits, int Kl, int dtype, const float* up_table,
+                                   const float* lat_table, const float* up_lc, const float* lat_lc, int B, int H, int W, bool vec,
+                                   float* up, float* upc, float* lat, float* latc, float* slat /* or nullptr */, hipStream_t s);
 
 // gclm_synth.hip
 hipError_t launch_read_probe(const float* const* planes, int n, size_t floats, hipStream_t s);

@@ -8,7 +8,8 @@ Replaces the tail of the reference's UpDecoder / LatitudeDecoder (geocalib/geoca
     latitude_confidence = sigmoid(lat_log_confidence)
 
 and writes the five planes in the layout LMOptimizer reads (eager PyTorch: 8 kernels, ~18 plane passes) -- and, on request,
-a sixth: sin(latitude_field), which the LM solve reads in place of the radians (gclm_pack_fields_ex)."""
+a sixth: sin(latitude_field), which the LM solve reads in place of the radians (gclm_pack_fields_ex).  `pack_fields_from_logits`
+is the same step for classification heads (gclm_pack_fields_bins)."""
 import ctypes
 from typing import Dict, Optional
 
@@ -42,6 +43,73 @@ def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: 
     p = _call.ptr
     _call.call("gclm_pack_fields_ex", p(up_raw), p(ulc), p(lat_raw), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc), p(slat),
                _call.raw_stream(lat_raw.device), device=lat_raw.device)
+    out = {"up_field": up, "latitude_field": lat}
+    if upc is not None:
+        out["up_confidence"] = upc
+    if latc is not None:
+        out["latitude_confidence"] = latc
+    if slat is not None:
+        out["sin_latitude"] = slat
+    return out
+
+
+_LOGIT_DTYPES = {torch.float32: _lib.LOGIT_DTYPE_IDS["float32"], torch.float16: _lib.LOGIT_DTYPE_IDS["float16"],
+                 torch.bfloat16: _lib.LOGIT_DTYPE_IDS["bfloat16"]}
+
+
+def pack_fields_from_logits(up_logits: torch.Tensor, lat_logits: torch.Tensor, up_log_confidence: Optional[torch.Tensor] = None,
+                            lat_log_confidence: Optional[torch.Tensor] = None, sin_latitude: bool = False) -> Dict[str, torch.Tensor]:
+    """`pack_fields` for classification heads (the original PerspectiveFields weights; the reference's decoders with
+    loss_type == "classification"): up_logits (B, Ku, h, w) and lat_logits (B, Kl, h, w) -- 73 and 180 bins there --, both
+    float32, float16 or bfloat16 and contiguous; log-confidences (B, h, w) or (B, 1, h, w).  Returns the dict
+    `LMOptimizer.forward` consumes, float32, with the keys of `pack_fields`:
+
+        up_field       = decode_up_bin(up_logits.argmax(1), Ku)                     (B, 2, h, w)
+        latitude_field = decode_bin_latitude(lat_logits.argmax(1), Kl)[:, None]     (B, 1, h, w)
+        confidences    = sigmoid(log-confidences)                                    (B, h, w)
+
+    with the decodes of `perspective_encoding` and torch.argmax's rule (the first index of the greatest value, a NaN greater
+    than everything).  On a HIP device that is ONE launch on torch's current stream (gclm_pack_fields_bins), which gathers
+    from the tables of `perspective_encoding`: fields equal to this composition's bit for bit.  On CPU tensors the composition
+    itself runs -- the readable statement of the definition; there `sin_latitude` is torch.sin of the latitude, the device
+    plane's definition up to the sweep's polynomial, not bit-equal to it.
+
+    Raises ValueError for logits that are not two 4-D tensors of one (B, h, w), device and dtype, for another dtype, for more
+    than 2048 bins, and for non-contiguous logits: 253 planes are not copied silently."""
+    from . import perspective_encoding as pe
+    if up_logits.dim() != 4 or lat_logits.dim() != 4:
+        raise ValueError(f"logits are (B, bins, h, w), got {tuple(up_logits.shape)} and {tuple(lat_logits.shape)}")
+    (B, Ku, H, W), Kl = up_logits.shape, lat_logits.shape[1]
+    if lat_logits.shape != (B, Kl, H, W) or lat_logits.device != up_logits.device:
+        raise ValueError(f"up logits {tuple(up_logits.shape)} on {up_logits.device} and latitude logits {tuple(lat_logits.shape)} "
+                         f"on {lat_logits.device} must share B, h, w and the device")
+    if up_logits.dtype != lat_logits.dtype:
+        raise ValueError(f"the logits must share one dtype, got {up_logits.dtype} and {lat_logits.dtype}")
+    if up_logits.dtype not in _LOGIT_DTYPES:
+        raise ValueError(f"logits are float32, float16 or bfloat16, got {up_logits.dtype}")
+    if not 2 <= Ku <= _lib.MAX_BINS or not 1 <= Kl <= _lib.MAX_BINS:
+        raise ValueError(f"2..{_lib.MAX_BINS} up bins and 1..{_lib.MAX_BINS} latitude bins, got {Ku} and {Kl}")
+    if not (up_logits.is_contiguous() and lat_logits.is_contiguous()):
+        raise ValueError("the logits must be contiguous (B, bins, h, w): call .contiguous() if a copy of every plane is meant")
+    confs = {"up_log_confidence": up_log_confidence, "lat_log_confidence": lat_log_confidence}
+    for name, c in confs.items():
+        if c is not None and (c.numel() != B * H * W or c.shape[-2:] != (H, W) or c.device != up_logits.device):
+            raise ValueError(f"`{name}` {tuple(c.shape)} on {c.device} does not fit {B} images of {H} x {W} on {up_logits.device}")
+    dev = up_logits.device
+    up_table, lat_table = pe.up_bin_table(Ku, dev), pe.latitude_bin_table(Kl, dev)
+    if not up_logits.is_cuda:
+        up, lat = pe.fields_from_logits(up_logits.detach(), lat_logits.detach())
+        upc, latc = (None if c is None else torch.sigmoid(c.detach().float()).reshape(B, H, W) for c in confs.values())
+        slat = torch.sin(lat) if sin_latitude else None
+    else:
+        up_logits, lat_logits = up_logits.detach(), lat_logits.detach()
+        ulc, llc = (None if c is None else _call.dev_f32(c, name) for name, c in confs.items())
+        up, lat = up_table.new_empty((B, 2, H, W)), up_table.new_empty((B, 1, H, W))
+        upc, latc = (None if c is None else torch.empty_like(c).view(B, H, W) for c in (ulc, llc))
+        slat = torch.empty_like(lat) if sin_latitude else None
+        p = _call.ptr
+        _call.call("gclm_pack_fields_bins", p(up_logits), Ku, p(lat_logits), Kl, _LOGIT_DTYPES[up_logits.dtype], p(up_table),
+                   p(lat_table), p(ulc), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc), p(slat), _call.raw_stream(dev), device=dev)
     out = {"up_field": up, "latitude_field": lat}
     if upc is not None:
         out["up_confidence"] = upc

@@ -52,7 +52,8 @@ extern "C" {
  * batches keep their two confidence planes as one plane of 16-bit pairs, see gclm_set_conf_pack; gclm_rpf_hypotheses added, also
  * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks; gclm_reproject_image added, also within 610;
  * gclm_undistort_image_u8 and gclm_reproject_image_u8 added, also within 610: the two image calls for uint8 images;
- * gclm_draw_fields and gclm_draw_fields_u8 added, also within 610: the perspective fields drawn over an image).  gclm_create refuses a gclm_config whose first two fields do not
+ * gclm_draw_fields and gclm_draw_fields_u8 added, also within 610: the perspective fields drawn over an image;
+ * gclm_pack_fields_bins added, also within 610: the head epilogue for classification heads).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -271,6 +272,41 @@ int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const flo
 int gclm_pack_fields_ex(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
                         const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
                         float* d_lat_conf, float* d_sin_lat /* (B,1,H,W) or NULL */, void* stream);
+
+/*
+ * The same step for CLASSIFICATION heads (siclib's UpDecoder / LatitudeDecoder with loss_type == "classification", the format
+ * of the original PerspectiveFields weights; siclib/models/utils/perspective_encoding.py): the up head emits up_bins logits per
+ * pixel (73: one per 5 degrees and an "invalid" class), the latitude head lat_bins (180: one per degree), and the fields are
+ * the decodes of the per-pixel argmax.  One pass reads d_up_logits (B,up_bins,H,W) and d_lat_logits (B,lat_bins,H,W) --
+ * contiguous, both of the type logit_dtype -- once and writes the planes gclm_calibrate reads:
+ *   u = argmax_k up_logits[b,k,y,x]      up[b,0,y,x] = up_table[u][0]     up[b,1,y,x] = up_table[u][1]
+ *   l = argmax_k lat_logits[b,k,y,x]     lat[b,0,y,x] = lat_table[l]
+ *   up_conf = sigmoid(up_logconf), lat_conf = sigmoid(lat_logconf)   (NULL: skipped; the floats gclm_pack_fields writes)
+ *   sin_lat = sin(lat) by the sweeps' polynomial                      (NULL: skipped; the plane of gclm_pack_fields_ex)
+ * argmax is torch.argmax's: the FIRST index of the greatest value; a NaN counts as greater than everything and the first NaN
+ * wins; a pixel whose logits are all -inf gives 0.  16-bit logits are compared as the floats they widen to.
+ * The two tables are the caller's, float32 in device memory, and hold the decode of every bin; the kernel only gathers from
+ * them, so its output is the table's bits.  The reference's decodes, every operation in float32 in the order written (the
+ * constants 360.0 / (up_bins - 1), s = 180.0 / lat_bins, s / 2 and pi formed in double and rounded to float32 once):
+ *   up_table[k]  = (cos(a), sin(a)),  a = (k * (360 / (up_bins - 1)) - 180) / 180 * pi,   k < up_bins - 1
+ *   up_table[up_bins - 1] = (0, 0)                                      (the invalid class)
+ *   lat_table[k] = (e_k + s / 2) / 180 * pi,   e_k = the float32 nearest to -90 + k * s (that sum in double)
+ * (geocalib_amd.perspective_encoding.up_bin_table / latitude_bin_table build them with torch on the CPU: the reference's
+ * floats.)  Every lat_table entry must lie within +-pi/2, as bin centres do: sin_lat is evaluated without a range fold.
+ * -3: a NULL logit tensor, table, d_up or d_lat; up_bins < 2, lat_bins < 1 or either above GCLM_MAX_BINS; an unknown
+ * logit_dtype; H or W <= 0, B < 0; a log-confidence without its output; a pointer off its element's alignment; an output that
+ * overlaps a logit tensor, a table or another output; d_sin_lat overlapping anything.  A log-confidence may be converted in
+ * place (output pointer == input pointer; any other overlap of the two is refused).  B = 0 succeeds and launches nothing.
+ * Where H * W is a multiple of the pixels per lane (4 for float32, 8 for the 16-bit types) and every plane is 16-byte
+ * aligned, each channel is read with one 16-byte load per lane; any other call takes one pixel per lane, same results.
+ */
+enum gclm_logit_dtype { GCLM_LOGITS_F32 = 0, GCLM_LOGITS_F16 = 1, GCLM_LOGITS_BF16 = 2 };
+#define GCLM_MAX_BINS 2048
+int gclm_pack_fields_bins(const void* d_up_logits, int up_bins, const void* d_lat_logits, int lat_bins, int logit_dtype,
+                          const float* d_up_table /* (up_bins,2) */, const float* d_lat_table /* (lat_bins) */,
+                          const float* d_up_logconf, const float* d_lat_logconf, int B, int H, int W, float* d_up,
+                          float* d_up_conf, float* d_lat, float* d_lat_conf, float* d_sin_lat /* (B,1,H,W) or NULL */,
+                          void* stream);
 
 /*
  * The step AFTER the path: GeoCalib._post_process (geocalib/extractor.py:51-69) resizes the fields and confidences

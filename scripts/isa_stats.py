@@ -2,6 +2,7 @@
 
 usage: python scripts/isa_stats.py [--json OUT] [--dump SYMBOL_SUBSTRING] [--slat 0|1|2] [--mirror 0|1] [--cpack 0|1|2] [MODEL ...]
        MODEL in {0 pinhole, 1 simple_radial, 2 radial, 3 simple_divisional}; default: all four.
+       python scripts/isa_stats.py --pack-bins       (registers and scratch of the classification-head epilogue instead)
 Looks at the instantiation sweep_kernel<MODEL, HAS_UP=1, HAS_UPC=1, HAS_LATC=1, LOGF=1, VEC=4> (the loop sweep of the
 default conf with both confidences: what bench.py runs) by its mangled template arguments, independent of how many
 template parameters precede / follow them; --slat picks the SLAT instantiation (0: sin(latitude) computed per sweep, 1: computed
@@ -23,8 +24,27 @@ asm = "/tmp/gclm_pass.s"
 NAMES = {0: "pinhole", 1: "simple_radial", 2: "radial", 3: "simple_divisional"}
 
 
+def pack_bins_stats():
+    """--pack-bins: VGPRs, scratch and vector loads / VALU of every pack_bins_kernel<DT, VEC> instantiation (gclm_fields.hip:
+    the classification-head epilogue; DT 0 float32, 1 float16, 2 bfloat16)."""
+    out = "/tmp/gclm_fields.s"
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast-honor-pragmas", "-S",
+                    "--cuda-device-only", "-o", out, os.path.join(ROOT, "geocalib_amd", "csrc", "gclm_fields.hip")], check=True,
+                   capture_output=True)
+    text = open(out).read()
+    for m in re.finditer(r"^(_ZN4gclm\S*pack_bins_kernelILi(\d)ELi(\d)E\S*):\s*;.*?\n(.*?)\.amdhsa_kernel(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
+        body = [l.strip().split()[0] for l in m.group(4).split("\n") if l.startswith("\t") and l.strip() and not l.strip().startswith((".", ";"))]
+        nv =re.search(r"\.amdhsa_next_free_vgpr\s+(\d+)", m.group(5))
+        sc = re.search(r"; ScratchSize: (\d+)", text[m.start():m.end() + 6000])
+        print(f"pack_bins_kernel<DT={m.group(2)}, VEC={m.group(3)}>: VGPRs {nv.group(1)}, scratch {sc.group(1) if sc else '?'} B, "
+              f"{len(body)} instructions, {sum(o.startswith('global_load') for o in body)} global loads, "
+              f"{sum(o.startswith('v_') for o in body)} VALU")
+
+
 def main():
     args = sys.argv[1:]
+    if "--pack-bins" in args:
+        return pack_bins_stats()
     out_json = dump = None
     if "--json" in args:
         i = args.index("--json"); out_json = args[i + 1]; del args[i:i + 2]

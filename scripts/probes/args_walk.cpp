@@ -95,7 +95,7 @@ int main() {
         e.writes(at(4096), 8);
         EXPECT(!a.pass() && !b.pass() && !e.pass());
         ArgCheck f;
-        for (int i = 0; i < 4; ++i) f.writes(at(4096 + 64 * i), 64, 64);
+        for (int i = 0; i < 5; ++i) f.writes(at(4096 + 64 * i), 64, 64);
         EXPECT(f.pass());
         f.writes(at(16384), 64);                                   // more written ranges than the object holds: refused
         EXPECT(!f.pass());
