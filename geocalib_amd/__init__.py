@@ -11,6 +11,8 @@ Public surface (mirrors the reference's geocalib package for this path):
     viz                                 geocalib/interactive_demo.py: render_frame  (draw_perspective_fields: the fields drawn over an image)
     perspective_encoding                siclib/models/utils/perspective_encoding.py  (fields as classification bins; with
                                         fields.pack_fields_from_logits: classification heads to fields in one pass)
+    PerspectiveParamOpt                 siclib/models/optimization/perspective_opt.py  (Adam on roll, pitch, vfov against the
+                                        fields, batched; perspective_opt.cost_function: its cost and gradient in one pass)
 """
 from .camera import BaseCamera, Pinhole, Radial, SimpleDivisional, SimpleRadial, camera_models  # noqa: F401
 from .gravity import Gravity  # noqa: F401
@@ -20,5 +22,6 @@ from . import metrics  # noqa: F401,E402
 from .ransac import RPFSolver, solve_rpf  # noqa: F401,E402
 from . import viz  # noqa: F401,E402
 from . import perspective_encoding  # noqa: F401,E402
+from .perspective_opt import PerspectiveParamOpt  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -22,6 +22,10 @@ RPF_DRAW_SALT = 0x5250465F44524157     # GCLM_RPF_DRAW_SALT: what the in-kernel 
 HYPOTHESIS_CHUNK = 16         # GCLM_HYPOTHESIS_CHUNK: hypotheses scored per read of an image's planes (gclm_hypothesis_scores)
 LOGIT_DTYPE_IDS = {"float32": 0, "float16": 1, "bfloat16": 2}     # enum gclm_logit_dtype (gclm_pack_fields_bins)
 MAX_BINS = 2048               # GCLM_MAX_BINS: most bins of one head (gclm_pack_fields_bins)
+PARAM_OPT_STATE_WORDS = 32    # GCLM_PARAM_OPT_STATE_WORDS: 32-bit words of one image's state record (gclm_param_opt_step)
+PARAM_OPT_INFO_WORDS = 12     # GCLM_PARAM_OPT_INFO_WORDS: floats per image of gclm_param_opt's d_info
+PARAM_OPT_INFO = {"steps": 0, "converged": 1, "final_cost": 2, "final_up_cost": 3, "final_latitude_cost": 4, "lr": 5, "initial": 6}
+PARAM_OPT_MAX_PATIENCE = 8    # GCLM_PARAM_OPT_MAX_PATIENCE
 ABI_VERSION = 610         # GCLM_VERSION of include/gclm.h this binding was written against
 INFO = {"stop_at": 0, "initial_up_cost": 1, "initial_latitude_cost": 2, "initial_cost": 3,
         "final_up_cost": 4, "final_latitude_cost": 5, "final_cost": 6, "roll_uncertainty": 7,
@@ -66,6 +70,24 @@ class GclmOverlayStyle(C.Structure):
                 ("arrow_step", C.c_int32), ("arrow_x0", C.c_int32), ("arrow_y0", C.c_int32), ("arrow_length", C.c_float),
                 ("arrow_halfwidth", C.c_float), ("arrow_tip", C.c_float), ("horizon_rgba", C.c_ubyte * 4),
                 ("arrow_rgba", C.c_ubyte * 4)]
+
+
+class GclmParamOptConfig(C.Structure):
+    """struct gclm_param_opt_config (include/gclm.h)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("max_steps", C.c_int32), ("patience", C.c_int32), ("use_scheduler", C.c_int32),
+                ("sched_patience", C.c_int32), ("sched_cooldown", C.c_int32), ("poll_every", C.c_int32), ("reserved", C.c_int32),
+                ("lr", C.c_double), ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("lamb", C.c_double),
+                ("sched_factor", C.c_double), ("sched_threshold", C.c_double), ("sched_min_lr", C.c_double),
+                ("sched_eps", C.c_double)]
+
+    @classmethod
+    def default(cls) -> "GclmParamOptConfig":
+        """gclm_default_param_opt_config: PerspectiveParamOpt.default_conf, torch's scheduler defaults, poll_every 16."""
+        cfg = cls()
+        if load().gclm_default_param_opt_config(C.byref(cfg)) != 0:
+            raise GclmError("gclm_default_param_opt_config failed")
+        return cfg
 
 
 class GclmError(RuntimeError):
@@ -124,6 +146,11 @@ _SIGNATURES = {
     "gclm_hypothesis_scores": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_float,
                                          C.c_float, C.c_float, _P, C.c_size_t, _P, _P, _P]),
     "gclm_rpf_hypotheses": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gclm_default_param_opt_config": (C.c_int, [C.POINTER(GclmParamOptConfig)]),
+    "gclm_param_opt_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gclm_param_opt_cost": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P]),
+    "gclm_param_opt_step": (C.c_int, [_P, _P, C.c_int, C.POINTER(GclmParamOptConfig), _P]),
+    "gclm_param_opt": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(GclmParamOptConfig), _P, C.c_size_t, _P, _P, _P]),
     "gclm_pack_fields": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "gclm_pack_fields_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gclm_pack_fields_bins": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,

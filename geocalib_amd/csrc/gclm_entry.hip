@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the five render kernels, the field errors, the hypothesis scores, the minimal solver, the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the five render kernels, the field errors, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -60,6 +60,17 @@ int reproject_image(int src_model, const float* d_src_cam, int dst_model, const 
 constexpr uint32_t kOverlayLayers = GCLM_OVERLAY_HEAT | GCLM_OVERLAY_TINT | GCLM_OVERLAY_CONTOURS | GCLM_OVERLAY_HORIZON | GCLM_OVERLAY_ARROWS;
 bool unit_interval(float v) { return v >= 0.f && v <= 1.f; }                 // (false for NaN)
 bool finite_nonneg(float v) { return v >= 0.f && v <= FLT_MAX; }
+
+// gclm_param_opt / gclm_param_opt_step: the one check of a config (include/gclm.h lists the conditions)
+bool finite_nonneg(double v) { return v >= 0.0 && v <= DBL_MAX; }
+bool param_opt_config_ok(const gclm_param_opt_config& c) {
+    if (c.struct_size != (int32_t)sizeof(gclm_param_opt_config) || c.max_steps < 1 || c.max_steps > GCLM_PARAM_OPT_MAX_STEPS) return false;
+    if (c.patience < 1 || c.patience > GCLM_PARAM_OPT_MAX_PATIENCE || c.sched_patience < 0 || c.sched_cooldown < 0 || c.poll_every < 0)
+        return false;
+    if (!finite_nonneg(c.lr) || !(c.lamb >= 0.0 && c.lamb <= 1.0) || c.abs_tol != c.abs_tol || c.rel_tol != c.rel_tol) return false;
+    return c.sched_factor >= 0.0 && c.sched_factor < 1.0 && finite_nonneg(c.sched_threshold) && finite_nonneg(c.sched_min_lr) &&
+           finite_nonneg(c.sched_eps);
+}
 
 template <typename T>
 int draw_fields(int camera_model, const float* d_cam, const float* d_grav, int cal_batch, const T* d_src, int B, int C, int H, int W,
@@ -335,6 +346,59 @@ int gclm_hypothesis_scores(int camera_model, const float* d_cam, const float* d_
     return launched(launch_hypothesis_scores(camera_model, d_cam, d_grav, B, N, H, W, d_up, d_lat, d_up_conf, d_lat_conf, d_mask,
                                              up_threshold_deg, lat_threshold_deg, up_weight, lat_weight, d_workspace, d_scores,
                                              d_best, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_default_param_opt_config(gclm_param_opt_config* config) {
+    if (!config) return -3;
+    // PerspectiveParamOpt.default_conf, perspective_opt.py:24-36, and torch's ReduceLROnPlateau defaults
+    *config = gclm_param_opt_config{(int32_t)sizeof(gclm_param_opt_config), 1000, 3, 1, 3, 0, 16, 0, 0.01, 1e-7, 1e-9, 0.5, 0.1, 1e-4, 0.0, 1e-8};
+    return 0;
+}
+
+size_t gclm_param_opt_workspace(int B, int H, int W) { return param_opt_workspace(B, H, W); }
+
+int gclm_param_opt_cost(const float* d_up, const float* d_lat, const float* d_rpv, int B, int H, int W, void* d_workspace,
+                        size_t workspace_bytes, float* d_out, void* stream) {
+    if (!d_up || !d_lat || !d_rpv || !d_workspace || !d_out) return -3;
+    const size_t ws_bytes = param_opt_workspace(B, H, W);                        // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_out, floats(B, 8), 4);
+    a.writes(d_workspace, ws_bytes, 16);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_rpv, floats(B, 3), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_param_opt_cost(d_up, d_lat, d_rpv, B, H, W, d_workspace, d_out, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_param_opt_step(void* d_state, const float* d_cost, int B, const gclm_param_opt_config* config, void* stream) {
+    if (!d_state || !d_cost || !config || B < 1 || B > kMaxCallImages || !param_opt_config_ok(*config)) return -3;
+    ArgCheck a;
+    a.writes(d_state, floats(B, GCLM_PARAM_OPT_STATE_WORDS), 8);
+    a.reads(d_cost, floats(B, 8), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_param_opt_step(d_state, d_cost, B, *config, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_param_opt(const float* d_up, const float* d_lat, const float* d_init_rpv, int B, int H, int W,
+                   const gclm_param_opt_config* config, void* d_workspace, size_t workspace_bytes, float* d_rpv, float* d_info,
+                   void* stream) {
+    if (!d_up || !d_lat || !config || !d_workspace || !d_rpv || !d_info || !param_opt_config_ok(*config)) return -3;
+    const size_t ws_bytes = param_opt_workspace(B, H, W);                        // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_rpv, floats(B, 3), 4);
+    a.writes(d_info, floats(B, GCLM_PARAM_OPT_INFO_WORDS), 4);
+    a.writes(d_workspace, ws_bytes, 16);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_init_rpv, floats(B, 3), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_param_opt(d_up, d_lat, d_init_rpv, B, H, W, *config, d_workspace, d_rpv, d_info,
+                                     static_cast<hipStream_t>(stream)));
 }
 
 int gclm_rpf_hypotheses(const float* d_up, const float* d_lat, const float* d_prior_focal, const int32_t* d_samples, uint64_t seed,

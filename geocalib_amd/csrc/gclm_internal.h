@@ -274,4 +274,12 @@ hipError_t launch_rpf_hypotheses(const float* up, const float* lat /* or nullptr
                                  const int32_t* samples /* or nullptr: drawn */, uint64_t seed, int64_t first_index, int B, int N, int H,
                                  int W, float* cam, float* grav, int32_t* samples_out /* or nullptr */, hipStream_t s);
 
+// gclm_param_opt.hip
+size_t param_opt_workspace(int B, int H, int W);                          // bytes of records, pose and state records; 0: sizes out of range
+hipError_t launch_param_opt_cost(const float* up, const float* lat, const float* rpv, int B, int H, int W, void* workspace, float* out,
+                                 hipStream_t s);
+hipError_t launch_param_opt_step(void* state, const float* cost, int B, const gclm_param_opt_config& cfg, hipStream_t s);
+hipError_t launch_param_opt(const float* up, const float* lat, const float* init /* or nullptr */, int B, int H, int W,
+                            const gclm_param_opt_config& cfg, void* workspace, float* rpv, float* info, hipStream_t s);
+
 }  // namespace gclm

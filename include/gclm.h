@@ -53,7 +53,9 @@ extern "C" {
  * within 610: the three-pixel minimal solver whose rows gclm_hypothesis_scores ranks; gclm_reproject_image added, also within 610;
  * gclm_undistort_image_u8 and gclm_reproject_image_u8 added, also within 610: the two image calls for uint8 images;
  * gclm_draw_fields and gclm_draw_fields_u8 added, also within 610: the perspective fields drawn over an image;
- * gclm_pack_fields_bins added, also within 610: the head epilogue for classification heads).  gclm_create refuses a gclm_config whose first two fields do not
+ * gclm_pack_fields_bins added, also within 610: the head epilogue for classification heads;
+ * gclm_param_opt, gclm_param_opt_cost, gclm_param_opt_step, gclm_param_opt_workspace and gclm_default_param_opt_config added, also
+ * within 610: Adam on (roll, pitch, vfov) against perspective fields, the reference's third optimiser).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -609,6 +611,100 @@ int gclm_hypothesis_scores(int camera_model, const float* d_cam, const float* d_
 int gclm_rpf_hypotheses(const float* d_up, const float* d_lat, const float* d_prior_focal, const int32_t* d_samples,
                         uint64_t seed, int64_t first_index, int B, int N, int H, int W, float* d_cam, float* d_grav,
                         int32_t* d_samples_out, void* stream);
+
+/*
+ * The reference's THIRD optimiser beside the LM and the RANSAC baseline (siclib/models/optimization/perspective_opt.py:
+ * PerspectiveParamOpt): Adam on (roll, pitch, vfov) of a pinhole camera, per image, against predicted fields d_up (B,2,H,W)
+ * planar and d_lat (B,1,H,W), float32.  The reference takes one image per call, renders both fields and runs autograd each
+ * step; here a step is one pass over the three planes and one small launch for the whole batch, and every image is its own
+ * reference call: own Adam moments, own learning rate, own stop.
+ *
+ * Per image the state is (r, p, v); g = (-sin r cos p, -cos r cos p, sin p), f = (H / 2) / tan(v / 2), fx = fy = f, principal
+ * point (W / 2, H / 2), integer pixel centres.  With the predicted fields of that camera (gclm_perspective_fields' formulas),
+ * means over H * W:
+ *   up  = mean acos(clip(cos_sim(up_pred, t), -1 + 1e-7, 1 - 1e-7)),   cos_sim as torch: t / max(|t|, 1e-8)
+ *   lat = mean |lat_pred - l|
+ *   total = lamb * lat + (1 - lamb) * up, formed in float64 from the two float32 means and rounded once to float32.
+ * The angle is evaluated as atan2(|U x T|, U . T) held to [theta_clip, pi - theta_clip], theta_clip = acos(1 - 1e-7) -- the
+ * same function, but small angles resolve in float32 -- and the gradient in closed form, without autograd and without a
+ * division by sin of the angle: d angle / ds = -sign(U x T) (n . dq/ds) / |q| with q the unnormalised up, n = (-U_y, U_x); 0
+ * where the clip is active.  Latitude: sign(lat_pred - l) ds / sqrt(1 - s^2), s the sine under the asin, 0 where its clamp
+ * (gclm_perspective_fields') is active.  (r, p) enter by the tangent columns of Gravity.J_rp, v by df/dv = -(H / 4) / sin^2(v / 2).
+ *
+ * gclm_param_opt_cost: ONE evaluation at given parameters d_rpv (B,3): d_out (B,8) = [up, lat, d up / d(r, p, v),
+ * d lat / d(r, p, v)].  Three launches (pose records, the pass, the per-image sums).
+ *
+ * gclm_param_opt_step: ONE update of B state records d_state from d_cost (B,8) as above -- the stage entry of the loop's
+ * update, in the reference's order: the Adam step, then the scheduler's step on the loss, then check_convergence on the same
+ * loss.  A state record is GCLM_PARAM_OPT_STATE_WORDS 32-bit words, 8-byte aligned:
+ *   0..2  float   roll, pitch, vfov            9  int32  steps taken (Adam's t)     14..15 double  learning rate
+ *   3..5  float   Adam's first moments        10  int32  converged (0 / 1)          16     float   scheduler's best
+ *   6..8  float   Adam's second moments       11  int32  scheduler's num_bad_epochs 17..19 float   last total, up, lat
+ *                                             12  int32  scheduler's cooldown count 20..27 float   the window of losses
+ *                                             13  int32  losses in the window       28..31 (the loop: initial r, p, v; else 0)
+ * A fresh record holds the parameters, the learning rate, best = +inf and zeros.  A record whose converged word is set is
+ * left as it is.
+ *   Adam: torch's defaults, betas (0.9, 0.999), eps 1e-8, bias corrections, gradient = float32(lamb * d lat + (1 - lamb) * d up);
+ *     parameters and moments are float32, one step's arithmetic is float64 and each is rounded once.
+ *   Scheduler (use_scheduler != 0): torch's ReduceLROnPlateau, mode "min", threshold_mode "rel": loss < best * (1 -
+ *     sched_threshold) sets best and zeroes num_bad_epochs, anything else (a NaN too) counts one; a running cooldown counts down and
+ *     zeroes num_bad_epochs; num_bad_epochs > sched_patience sets lr = max(lr * sched_factor, sched_min_lr) if that lowers it by
+ *     more than sched_eps, starts the cooldown and zeroes num_bad_epochs.
+ *   check_convergence, in this order: loss <= abs_tol stops; a window of fewer than `patience` losses appends the loss;
+ *     |loss - window[0]| < rel_tol stops; otherwise the loss is appended and the last `patience` are kept.
+ *   Every comparison is made in float64 on the float32 loss (Python's .item()).  The step that detects convergence has
+ *   applied its Adam update.  Nothing clamps vfov.  A NaN loss never converges.
+ *
+ * gclm_param_opt: the loop.  d_init_rpv (B,3), or NULL for the reference's _get_init_params: roll = -atan2(up_x, -up_y) and
+ * pitch = latitude at pixel (H / 2, W / 2) (integer division), vfov = |lat[0, W / 2] - lat[H - 1, W / 2]| held to [20, 120]
+ * degrees -- read back, as the reference reads them, from the Gravity and the camera built of them (Gravity.roll's 1e-4 in
+ * the denominator included).  Up to max_steps steps of pass + update; an image that has converged freezes and its workgroups
+ * return after one load.  d_rpv (B,3) receives the parameters, d_info (B, GCLM_PARAM_OPT_INFO_WORDS) floats:
+ *   [0] steps taken  [1] converged (0 / 1)  [2..4] total, up, lat of the last evaluation (at the parameters BEFORE the last
+ *   update, as the reference's last loss)  [5] final learning rate  [6..8] the initial (r, p, v)  [9..11] 0.
+ * poll_every = 0 enqueues all max_steps steps without a host synchronisation; poll_every = n > 0 reads the count of
+ * converged images back every n steps -- a synchronisation of `stream` the caller asked for -- and stops enqueueing once no
+ * image is live.  The results are bit-identical either way, and an image's bits depend on its own pixels, H, W and the
+ * alignment of the planes alone (4 pixels per lane where W % 4 == 0 and both planes are 16-byte aligned, 2 where W is even and
+ * both 8-byte aligned, else 1; the three paths agree to float32 rounding of a pixel's terms and the order of the sums), not on B or
+ * the other images.
+ *
+ * The caller owns the workspace: gclm_param_opt_workspace(B, H, W) bytes (0 for sizes the calls refuse), 16-byte aligned, for
+ * gclm_param_opt and gclm_param_opt_cost alike.  gclm_default_param_opt_config fills the reference's default_conf (max_steps
+ * 1000, lr 0.01, patience 3, abs_tol 1e-7, rel_tol 1e-9, lamb 0.5, ReduceLROnPlateau with patience 3 and torch's other
+ * defaults: factor 0.1, threshold 1e-4, cooldown 0, min_lr 0, eps 1e-8), poll_every 16 and struct_size.
+ * All three calls return -3 (before any HIP call) for a NULL pointer (d_init_rpv may be NULL), B outside 1..65535, H or W < 2,
+ * H * W > 2^31 - 1, a pointer off its alignment (4 bytes; d_state 8; the workspace 16), an output that overlaps an input, the
+ * workspace or another output, a workspace smaller than gclm_param_opt_workspace says, or a config with a wrong struct_size,
+ * max_steps outside 1..GCLM_PARAM_OPT_MAX_STEPS, patience outside 1..GCLM_PARAM_OPT_MAX_PATIENCE, lr negative or not finite,
+ * lamb outside [0, 1], a NaN tolerance, sched_patience, sched_cooldown or poll_every < 0, sched_factor outside [0, 1),
+ * sched_threshold, sched_min_lr or sched_eps negative or not finite; -10 if a launch fails.  Asynchronous on `stream` (but for the
+ * polls); no allocation.
+ */
+#define GCLM_PARAM_OPT_STATE_WORDS 32
+#define GCLM_PARAM_OPT_INFO_WORDS 12
+#define GCLM_PARAM_OPT_MAX_PATIENCE 8
+#define GCLM_PARAM_OPT_MAX_STEPS 1000000
+typedef struct gclm_param_opt_config {
+    int32_t struct_size;        /* sizeof(gclm_param_opt_config) */
+    int32_t max_steps;
+    int32_t patience;           /* check_convergence's window */
+    int32_t use_scheduler;      /* 0: lr_scheduler.name = None */
+    int32_t sched_patience;
+    int32_t sched_cooldown;
+    int32_t poll_every;
+    int32_t reserved;           /* 0 */
+    double lr, abs_tol, rel_tol, lamb;
+    double sched_factor, sched_threshold, sched_min_lr, sched_eps;
+} gclm_param_opt_config;
+int gclm_default_param_opt_config(gclm_param_opt_config* config);
+size_t gclm_param_opt_workspace(int B, int H, int W);
+int gclm_param_opt_cost(const float* d_up, const float* d_lat, const float* d_rpv, int B, int H, int W, void* d_workspace,
+                        size_t workspace_bytes, float* d_out, void* stream);
+int gclm_param_opt_step(void* d_state, const float* d_cost, int B, const gclm_param_opt_config* config, void* stream);
+int gclm_param_opt(const float* d_up, const float* d_lat, const float* d_init_rpv, int B, int H, int W,
+                   const gclm_param_opt_config* config, void* d_workspace, size_t workspace_bytes, float* d_rpv, float* d_info,
+                   void* stream);
 
 /*
  * BaseCamera.get_img_from_pano (geocalib/camera.py:414-514) for n images, in one pass: d_dst (n, C, H, W) holds image i
