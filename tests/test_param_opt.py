@@ -1,6 +1,7 @@
 """GPU: PerspectiveParamOpt on the HIP path (gclm_param_opt, gclm_param_opt_cost, gclm_param_opt_step) against what the
 reference's module computed on the same fields (tests/golden/param_opt_reference.npz, written by
-tests/golden/make_golden_param_opt.py) and against torch.optim run live.  Every test prints the figures it gates."""
+tests/golden/make_golden_param_opt.py) and against torch.optim run live; section 9 holds the pass at its branch edges, ragged
+tiles and batches to the bound tests/param_opt_gate.py derives on the CPU.  Every test prints the figures it gates."""
 import ctypes as C
 import math
 
@@ -9,6 +10,7 @@ import pytest
 import torch
 
 from geocalib_amd import Gravity, PerspectiveParamOpt, Pinhole, _lib, perspective_opt
+from conftest import MEASURED
 import param_opt_gate as pg
 
 pytestmark = pytest.mark.gpu
@@ -258,3 +260,114 @@ def test_module_dict_in_dict_out(dev):
         perspective_opt.cost_function(one["rpv"].repeat(2, 1), data)
     with pytest.raises(RuntimeError, match="HIP device"):
         PerspectiveParamOpt({})({k: v.cpu() for k, v in data.items()})
+
+
+# ------------------------------------------------------------------ 9. the pass at its branch edges and ragged tiles
+# Every number below is held to param_opt_gate.gate's bound, MARGIN * D_k + MARGIN * 2^-23 * A_k, derived on the CPU from the
+# float64 statement and its float32 restatement: nothing the device computes enters it.  test_param_opt_abi.py shows that
+# every case is decisive and that the bound refuses each mutant of the pass by POWER x or more.
+def planes_of(up, lat, dev, shift=0):
+    """(B, 2, H, W) and (B, 1, H, W) arrays as device tensors that start `shift` floats past an aligned address."""
+    out = {}
+    for k, a in (("up_field", up), ("latitude_field", lat)):
+        t = torch.from_numpy(np.array(a, np.float32))
+        flat = torch.empty(t.numel() + shift, dtype=t.dtype, device=dev)
+        assert flat.data_ptr() % 256 == 0
+        flat[shift:].copy_(t.reshape(-1))
+        out[k] = flat[shift:].view(t.shape)
+    return out
+
+
+def eight(states, data):
+    """gclm_param_opt_cost: the (B, 8) float32 tensor [up, lat, up gradient, latitude gradient]."""
+    rpv = torch.from_numpy(np.asarray(states, np.float32).reshape(-1, 3)).to(data["up_field"].device)
+    out = perspective_opt.cost_function(rpv, data)
+    torch.cuda.synchronize()
+    return torch.cat([out["up"][:, None], out["latitude"][:, None], out["up_grad"], out["latitude_grad"]], 1)
+
+
+def hold(tag, got, up, lat, state):
+    """Prints, records and returns the ratio of each of the eight numbers to its bound (inf: not exactly 0 where the bound is 0)."""
+    want, bound, _ = pg.gate(up, lat, state)
+    got = np.asarray(got, np.float64)
+    r = pg.ratios(got, want, bound)
+    for k in range(8):
+        print(f"{tag} number {k}: hip {got[k]:+.9e} f64 {want[k]:+.9e} err {abs(got[k] - want[k]):.2e} bound {bound[k]:.2e} ratio {r[k]:.3f}")
+    MEASURED[f"param_opt_edges/{tag}"] = r.tolist()
+    return r
+
+
+@pytest.mark.parametrize("name", list(pg.RAGGED))
+def test_ragged_tiles_against_float64(name, dev):
+    """(a) The smallest shapes that reach a second tile column with idle lanes, a last tile row with idle waves, more tiles
+    than the finish kernel has chains, and two and one pixels per lane natively: each number within its bound."""
+    H, W, shift, px, tiles, _, _ = pg.RAGGED[name]
+    up, lat, state = pg.ragged_case(name)
+    data = planes_of(up[None], lat[None], dev, shift)
+    assert pg.pixels_per_lane(W, data["up_field"].data_ptr(), data["latitude_field"].data_ptr()) == px       # the path under test
+    assert pg.tile_count(H, W, px) == tiles
+    r = hold(f"ragged/{name}", eight(state, data)[0].cpu().numpy(), up, lat, state)
+    assert r.max() <= 1.0, r
+
+
+@pytest.mark.parametrize("name", pg.EDGE_NAMES)
+def test_branch_edges_against_float64(name, dev):
+    """(b) tests/golden/param_opt_edges.npz: the latitude clamp, the clamp of |q|, both forms of the short-target branch, both
+    angle clips (up gradients exactly 0 where every pixel is inside a clip), sign(0) and the extreme poses."""
+    up, lat, state = pg.edge_case(name)
+    got = eight(state, planes_of(up[None], lat[None], dev))[0].cpu().numpy()
+    r = hold(f"edge/{name}", got, up, lat, state)
+    assert r.max() <= 1.0, r
+    if name in ("lower_clip", "upper_clip"):
+        assert not got[2:5].any()
+
+
+@pytest.mark.parametrize("name", ["B70 6x8", "B3 50x516"])
+def test_batches_of_the_cost_entry_against_float64_and_each_image_alone(name, dev):
+    """(c) gclm_param_opt_cost with B > 1 (B = 70: the pose kernel's second block): every image within its own bound and equal,
+    bit for bit, to that image evaluated alone."""
+    up, lat, states = pg.batch70() if name.startswith("B70") else pg.batch3()
+    got = eight(states, planes_of(up, lat, dev))
+    worst = np.zeros(8)
+    for b in range(len(states)):
+        alone = eight(states[b], planes_of(up[b:b + 1], lat[b:b + 1], dev))
+        assert torch.equal(alone[0], got[b]), (b, alone[0], got[b])
+        worst = np.maximum(worst, hold(f"batch/{name}/{b}", got[b].cpu().numpy(), up[b], lat[b], states[b]))
+    print(f"{name}: worst ratio per number {worst.round(3).tolist()}")
+    assert worst.max() <= 1.0, worst
+
+
+@pytest.mark.parametrize("name", list(pg.RAGGED))
+def test_loop_of_one_step_reports_the_bits_of_the_cost_entry(name, dev):
+    """(d) gclm_param_opt with max_steps = 1 from an explicit init, three distinct images of a ragged shape: final_up_cost and
+    final_latitude_cost are the bits gclm_param_opt_cost gives at that init (the same pass and sums; the loop reads the state
+    32 words apart, the cost entry 3)."""
+    H, W, shift, px, _, _, _ = pg.RAGGED[name]
+    up, lat, states = pg.batch3(H, W)
+    data = planes_of(up, lat, dev, shift)
+    assert pg.pixels_per_lane(W, data["up_field"].data_ptr(), data["latitude_field"].data_ptr()) == px
+    init = torch.from_numpy(states.astype(np.float32)).to(dev)
+    cost = eight(states, data)
+    out = PerspectiveParamOpt({"max_steps": 1})(data, init=init)
+    torch.cuda.synchronize()
+    print(name, "cost entry", cost[:, :2].tolist(), "loop", out["final_up_cost"].tolist(), out["final_latitude_cost"].tolist())
+    assert out["steps"].tolist() == [1, 1, 1] and torch.equal(out["initial"], init)
+    assert torch.equal(out["final_up_cost"], cost[:, 0]) and torch.equal(out["final_latitude_cost"], cost[:, 1])
+    assert len({float(c) for c in cost[:, 0]}) == 3                              # distinct images: a wrong `b` would show
+
+
+def test_initial_estimate_at_its_edges(dev):
+    """(e) Rolls beyond +-90 degrees and of exactly 90 (the mirrored branch, g_y >= 0) and both ends of the vfov clamp, in one
+    call: each parameter inside param_opt_gate.initial_interval."""
+    fields = [pg.init_fields(pose) for pose in pg.INIT_EDGES]
+    data = planes_of(np.stack([f[0] for f in fields]), np.stack([f[1] for f in fields]), dev)
+    out = PerspectiveParamOpt({"max_steps": 1})(data)
+    torch.cuda.synchronize()
+    got = out["initial"].double().cpu().numpy()
+    for b, pose in enumerate(pg.INIT_EDGES):
+        lo, hi = pg.initial_interval(*fields[b])
+        est = pg.initial_estimate(*fields[b])
+        where = (got[b] - lo) / (hi - lo)
+        print(f"pose {pose}: initial {np.degrees(got[b])} float64 {np.degrees(est)} position in the interval {where.round(3).tolist()}")
+        MEASURED[f"param_opt_edges/initial/{pose}"] = where.tolist()
+        assert (lo <= got[b]).all() and (got[b] <= hi).all(), (pose, got[b], lo, hi)

@@ -2,7 +2,9 @@
 reference's default_conf, the workspace size is monotone, every invalid argument is refused before any HIP call, the float64
 statement of tests/param_opt_gate.py equals the reference's float64 autograd (tests/golden/param_opt_reference.npz) and its
 state machine equals torch.optim.Adam + ReduceLROnPlateau run live, the Python module refuses what it does not implement and
-hands the C entries the arguments of include/gclm.h."""
+hands the C entries the arguments of include/gclm.h.  For the edge gates of tests/test_param_opt.py: the per-pixel statement
+equals the yardstick, the yardstick equals the reference at the recorded edges (tests/golden/param_opt_edges.npz), every case is
+decisive and enters the branch it is named for, and the derived bound refuses each mutant of the pass."""
 import ctypes as C
 import math
 import os
@@ -290,3 +292,198 @@ def test_pass_kernels_carry_no_scratch(tmp_path):
     # at most 128 VGPRs: a SIMD's 512 registers per lane then hold four waves or more, which an arithmetic-bound pass needs to
     # cover its transcendental chains; LDS is the one record per wave
     assert all(v["scratch"] == 0 and v["vgpr"] <= 128 and v["lds"] <= 512 for v in k.values()), k
+
+
+# ------------------------------------------------------------------ the per-pixel statement, its bound and the edge cases
+EDGE_NAMES = pg.EDGE_NAMES
+CLIP_CASES = ("lower_clip", "upper_clip")
+ALL_CASES = [f"ragged/{n}" for n in pg.RAGGED] + [f"edge/{n}" for n in EDGE_NAMES] + [f"batch3/{b}" for b in range(3)] + ["batch70"]
+
+
+def images_of(case):
+    """[(up, latitude, state)] of a case of ALL_CASES: one image, or the seventy of batch70."""
+    kind, _, name = case.partition("/")
+    if kind == "ragged":
+        return [pg.ragged_case(name)]
+    if kind == "edge":
+        return [pg.edge_case(name)]
+    up, lat, states = pg.batch3() if kind == "batch3" else pg.batch70()
+    return [(up[b], lat[b], states[b]) for b in ([int(name)] if kind == "batch3" else range(pg.B70))]
+
+
+def test_edges_file_holds_the_recorded_cases():
+    g = pg.edges()
+    assert os.path.getsize(pg.EDGES) < 100_000
+    assert g["names"].tolist() == EDGE_NAMES
+    for name in EDGE_NAMES:
+        up, lat, state = pg.edge_case(name)
+        H, W = {"zenith_q0": (6, 12), "zenith": (8, 12), "nadir": (8, 12), "roll80_vfov120": (8, 12), "vfov20": (8, 12), "pitch-60": (33, 47)}.get(name, (6, 8))
+        assert up.shape == (2, H, W) and lat.shape == (1, H, W) and up.dtype == lat.dtype == np.float32
+        assert state.dtype == np.float64 and np.array_equal(state, pg.f32(state))
+        assert g[f"ref64_{name}"].shape == (8,) and g[f"finite_{name}"].all() and int(g[f"nudges_{name}"]) <= 2
+    f = 4 / math.tan(math.radians(30))
+    assert np.array_equal(pg.edge_case("zenith")[2], pg.f32([0, math.atan(f / 2), math.radians(60)]))
+    assert np.array_equal(pg.edge_case("nadir")[2], pg.f32([0, -math.atan(f / 2), math.radians(60)]))
+    assert abs(math.degrees(pg.edge_case("roll80_vfov120")[2][2]) - 120) < 1e-5 and abs(math.degrees(pg.edge_case("vfov20")[2][2]) - 20) < 1e-5
+    assert abs(math.degrees(pg.edge_case("pitch-60")[2][1]) + 60 - math.degrees(pg.OFFSET[1])) < 1e-5
+
+
+@pytest.mark.parametrize("name", EDGE_NAMES)
+def test_closed_form_equals_the_reference_float64_autograd_at_the_edges(name):
+    """tests/golden/param_opt_edges.npz: each of the eight numbers within 1e-10 of the reference's cost under float64 autograd,
+    relative to the largest entry of its term, with the reference's float64 clamp bound (the double 1 - 1e-6); a term the
+    reference has at exactly 0 (the up gradients of the clip cases) is exactly 0.  A number the reference returned non-finite
+    would be held to nothing here (the file has none)."""
+    up, lat, state = pg.edge_case(name)
+    got, want, finite = pg.cost_and_gradient(up, lat, state, clamp_hi=pg.LAT_HI64), pg.edges()[f"ref64_{name}"], pg.edges()[f"finite_{name}"]
+    for sl in (slice(0, 1), slice(1, 2), slice(2, 5), slice(5, 8)):
+        ok = finite[sl]
+        scale = np.abs(want[sl][ok]).max() if ok.any() else 0.0
+        err = np.abs(got[sl] - want[sl])[ok].max() if ok.any() else 0.0
+        print(name, sl, err, scale)
+        assert err <= 1e-10 * scale, (name, sl, got[sl], want[sl])
+    if "zenith" in name or name == "nadir":   # the clamp bound matters: one pixel's latitude error changes by asin's slope there
+        assert abs(pg.cost_and_gradient(up, lat, state)[1] - want[1]) > 1e-10 * want[1]
+
+
+@pytest.mark.parametrize("case", ALL_CASES)
+def test_per_pixel_statement_in_float64_is_the_yardstick(case):
+    """The means of per_pixel's float64 planes equal cost_and_gradient to 1e-12 (of 1, or of the number where it is larger)."""
+    for up, lat, state in images_of(case):
+        got, want = pg.per_pixel(up, lat, state)[0].mean((1, 2)), pg.cost_and_gradient(up, lat, state)
+        assert (np.abs(got - want) <= 1e-12 * np.maximum(1, np.abs(want))).all(), (case, got, want)
+        hi = pg.per_pixel(up, lat, state, clamp_hi=pg.LAT_HI64)[0].mean((1, 2))
+        assert (np.abs(hi - pg.cost_and_gradient(up, lat, state, clamp_hi=pg.LAT_HI64)) <= 1e-12 * np.maximum(1, np.abs(want))).all()
+
+
+@pytest.mark.parametrize("case", ALL_CASES)
+def test_every_case_is_decisive(case):
+    """No pixel of any case lies where float32 and float64 may take different sides of a switch (param_opt_gate.indecisive),
+    and the float32 restatement takes every branch as float64 does."""
+    for up, lat, state in images_of(case):
+        bad = pg.indecisive(up, lat, state)
+        assert not any(v.any() for v in bad.values()), (case, {k: np.argwhere(v).tolist() for k, v in bad.items()})
+        a64, a32 = pg.per_pixel(up, lat, state)[1], pg.per_pixel(up, lat, state, np.float32)[1]
+        for k in ("lo", "hi", "clamped", "long"):
+            assert np.array_equal(a64[k], a32[k]), (case, k)
+        assert np.array_equal(np.sign(a64["e"]), np.sign(a32["e"]))
+
+
+def test_edge_cases_enter_the_branches_they_are_named_for():
+    for name, row, H in (("zenith", 2, 8), ("nadir", 6, 8), ("zenith_q0", 1, 6)):
+        up, lat, state = pg.edge_case(name)
+        for dtype in (np.float64, np.float32):
+            a = pg.per_pixel(up, lat, state, dtype)[1]
+            assert np.argwhere(a["clamped"]).tolist() == [[row, 6]]
+            assert np.abs(a["s"][row, 6]) - pg.LAT_HI > 9e-7                       # the clamp's margin
+            assert sorted(np.argwhere(~a["long"]).tolist()) == sorted([[row, 6], [H - 1 - row, 3], [4, 9]])
+        assert abs(np.hypot(*up[:, 4, 9].astype(np.float64)) - pg.DELIBERATE_SHORT) < 1e-12 and not up[:, row, 6].any() and not up[:, H - 1 - row, 3].any()
+    # the clamp of |q|: a float32 state leaves |q| near 1e-8 at the pole's pixel, except where the pose record is exact
+    up, lat, state = pg.edge_case("zenith_q0")
+    assert pg.per_pixel(up, lat, state, np.float32)[1]["n2"][1, 6] == 0 and np.argwhere(pg.per_pixel(up, lat, state, np.float32)[1]["n2"] < 1e-24).tolist() == [[1, 6]]
+    up, lat, state = pg.edge_case("lower_clip")
+    t, a = pg.per_pixel(up, lat, state)
+    assert a["lo"].all() and (t[0] == pg.THETA_CLIP).all() and not t[2:5].any()
+    assert np.array_equal(pg.gate(up, lat, state)[1][2:5], np.zeros(3))             # bound 0: the device must return exactly 0
+    up, lat, state = pg.edge_case("upper_clip")
+    t, a = pg.per_pixel(up, lat, state)
+    assert a["hi"].sum() == 18 and a["hi"][:, :3].all() and a["lo"][:, 3:].all() and not t[2:5].any()
+    assert np.array_equal(pg.gate(up, lat, state)[1][2:5], np.zeros(3))
+    up, lat, state = pg.edge_case("exact_zero")
+    for dtype in (np.float64, np.float32):
+        assert np.argwhere(pg.per_pixel(up, lat, state, dtype)[1]["e"] == 0).tolist() == [[3, 4]]
+    # the noisy cases reach the lower clip by chance only; the test of the clip-off mutant counts on these
+    assert sum(int(pg.per_pixel(*c)[1]["lo"].sum()) for n in pg.RAGGED for c in [pg.ragged_case(n)]) >= 3
+
+
+@pytest.mark.parametrize("case", ALL_CASES)
+def test_bound_is_a_float32_bound_and_the_restatement_meets_it(case):
+    """The bound of each number is MARGIN * D_k + MARGIN * 2^-23 * A_k > 0 except where the term is identically 0; it stays
+    below 4e-5 of the mean magnitude of the term's planes (A_k, for a gradient the largest of its three): a float32
+    evaluation's, not a looser one (the latitude cost is the loosest: an error near 0.01 rad formed from latitudes near 1 rad,
+    whose float32 rounding is 6e-8, times MARGIN).  The float32 restatement itself stays within a quarter of it (it must: a mean of differences
+    is no larger than the mean of their magnitudes) -- what the device's ratio is to be read against."""
+    worst_rel, worst_own = 0.0, 0.0
+    for up, lat, state in images_of(case):
+        t64 = pg.per_pixel(up, lat, state)[0]
+        want, bound, f32 = pg.gate(up, lat, state)
+        A = np.abs(t64).mean((1, 2))
+        scale = np.array([A[0], A[1]] + [A[2:5].max()] * 3 + [A[5:8].max()] * 3)
+        assert ((bound > 0) | (A == 0)).all() and (bound[scale > 0] <= 4e-5 * scale[scale > 0]).all(), (case, bound[scale > 0] / scale[scale > 0])
+        own = pg.ratios(f32, want, bound)
+        worst_rel, worst_own = max(worst_rel, (bound[scale > 0] / scale[scale > 0]).max()), max(worst_own, own.max())
+    print(f"{case}: bound up to {worst_rel:.2e} of the term, float32 restatement up to {worst_own:.3f} of the bound")
+    assert worst_own <= 0.25
+
+
+# mutant -> the cases it must be caught at.  "all" is every case but, for an error in the up gradient alone, the two clip
+# cases: every pixel of theirs is inside the clip, their up gradient is 0 whatever its formula (and is gated to exactly 0).
+def _under_the_clip(case):
+    return all(pg.per_pixel(*c)[1]["lo"].any() or pg.per_pixel(*c)[1]["hi"].any() for c in images_of(case))
+
+
+MUTANT_CASES = {"principal point": ALL_CASES, "dg/dr swapped": ALL_CASES,
+                "dcp w dropped": [c for c in ALL_CASES if c.split("/")[-1] not in CLIP_CASES],
+                "clip off": [f"edge/{n}" for n in CLIP_CASES] + [c for c in ALL_CASES if c.startswith(("ragged", "batch3", "edge/zenith", "edge/nadir")) and _under_the_clip(c)],
+                "clamp off": ["edge/zenith", "edge/nadir", "edge/zenith_q0"], "short target by |crs|": ["edge/zenith", "edge/nadir", "edge/zenith_q0"],
+                "sign(0) = 1": ["edge/exact_zero"]}
+MUTANT_IDS = [(m, c) for m, cs in MUTANT_CASES.items() for c in cs]
+POWER = 4.0                                   # a mutant must exceed the bound by this factor
+
+
+@pytest.mark.parametrize("mutant,case", MUTANT_IDS, ids=[f"{m}-{c}" for m, c in MUTANT_IDS])
+def test_bound_refuses_the_mutants_of_the_pass(mutant, case):
+    """Each deliberate error in the float64 statement puts at least one of the eight numbers POWER x outside its bound, at every
+    image of the case.  (clip off: at the noisy cases only where a pixel lies under the clip.)"""
+    caught = []
+    for up, lat, state in images_of(case):
+        want, bound, _ = pg.gate(up, lat, state)
+        got = pg.per_pixel(up, lat, state, mutant=mutant)[0].mean((1, 2))
+        caught.append(pg.ratios(got, want, bound).max())
+    print(f"{mutant} at {case}: {min(caught):.3g} .. {max(caught):.3g} of the bound")
+    assert min(caught) >= POWER
+
+
+@pytest.mark.parametrize("name", ["6x260", "50x516"])
+def test_bound_refuses_a_dropped_tile_column(name):
+    up, lat, state = pg.ragged_case(name)
+    W, px = pg.RAGGED[name][1], pg.RAGGED[name][3]
+    x0 = pg.last_tile_column(W, px)
+    assert 0 < x0 < W
+    t = pg.per_pixel(up, lat, state)[0].copy()
+    t[:, :, x0:] = 0
+    want, bound, _ = pg.gate(up, lat, state)
+    r = pg.ratios(t.mean((1, 2)), want, bound)
+    print(name, "columns from", x0, "left out:", r)
+    assert r.max() >= POWER
+
+
+def test_bound_refuses_image_b_at_the_state_of_image_0():
+    up, lat, states = pg.batch70()
+    assert len({tuple(s) for s in states}) == pg.B70
+    for b in range(1, pg.B70):
+        want, bound, _ = pg.gate(up[b], lat[b], states[b])
+        r = pg.ratios(pg.per_pixel(up[b], lat[b], states[0])[0].mean((1, 2)), want, bound)
+        assert r.max() >= POWER, (b, r)
+
+
+@pytest.mark.parametrize("pose", pg.INIT_EDGES)
+def test_initial_interval_holds_the_estimate_and_the_edges_take_their_branches(pose):
+    """(e): the fields of INIT_EDGES reach the mirrored-roll branch (|roll| > 90 degrees, and roll = 90 where g_y = 0) and both
+    ends of the vfov clamp; the interval for the device holds the float64 estimate and is a few float32 ulps wide except in
+    roll near +-90 degrees."""
+    up, lat = pg.init_fields(pose)
+    est = pg.initial_estimate(up, lat)
+    lo, hi = pg.initial_interval(up, lat)
+    assert (lo <= est).all() and (est <= hi).all()
+    width = (hi - lo) / np.spacing(np.abs(est).astype(np.float32)).astype(np.float64)
+    print(pose, np.degrees(est), width)
+    assert (width[1:] <= 9).all()
+    if abs(pose[0]) > 90:
+        assert abs(abs(math.degrees(est[0])) - abs(pose[0])) < 0.1 and np.sign(est[0]) == np.sign(pose[0]) and width[0] <= (13 if abs(pose[0]) > 100 else 400)
+    if pose[0] == 90:
+        assert up[1, 24, 32] == 0 and 89 < math.degrees(lo[0]) < 90 < math.degrees(hi[0]) < 91     # the two branches meet here
+    if pose[2] == 10:
+        assert est[2] == pytest.approx(float(np.float32(math.radians(20))), abs=1e-12)
+    if pose[2] == 150:
+        assert est[2] == pytest.approx(float(np.float32(math.radians(120))), abs=1e-12)
