@@ -13,6 +13,9 @@ Public surface (mirrors the reference's geocalib package for this path):
                                         fields.pack_fields_from_logits: classification heads to fields in one pass)
     PerspectiveParamOpt                 siclib/models/optimization/perspective_opt.py  (Adam on roll, pitch, vfov against the
                                         fields, batched; perspective_opt.cost_function: its cost and gradient in one pass)
+    losses                              siclib/models/decoders/{up,latitude,perspective}_decoder.py: calculate_losses, loss
+                                        (perspective_field_loss: the heads' training losses against a calibration,
+                                        differentiable in the predicted fields, one HIP pass each way)
 """
 from .camera import BaseCamera, Pinhole, Radial, SimpleDivisional, SimpleRadial, camera_models  # noqa: F401
 from .gravity import Gravity  # noqa: F401
@@ -23,5 +26,7 @@ from .ransac import RPFSolver, solve_rpf  # noqa: F401,E402
 from . import viz  # noqa: F401,E402
 from . import perspective_encoding  # noqa: F401,E402
 from .perspective_opt import PerspectiveParamOpt  # noqa: F401,E402
+from . import losses  # noqa: F401,E402
+from .losses import perspective_decoder_loss, perspective_field_loss  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -22,6 +22,7 @@ RPF_DRAW_SALT = 0x5250465F44524157     # GCLM_RPF_DRAW_SALT: what the in-kernel 
 HYPOTHESIS_CHUNK = 16         # GCLM_HYPOTHESIS_CHUNK: hypotheses scored per read of an image's planes (gclm_hypothesis_scores)
 LOGIT_DTYPE_IDS = {"float32": 0, "float16": 1, "bfloat16": 2}     # enum gclm_logit_dtype (gclm_pack_fields_bins)
 MAX_BINS = 2048               # GCLM_MAX_BINS: most bins of one head (gclm_pack_fields_bins)
+FIELD_LOSS_IDS = {"l1": 0, "l2": 1, "dot": 2, "cauchy": 3, "huber": 4}     # enum gclm_field_loss (gclm_field_loss, gclm_field_loss_grad)
 PARAM_OPT_STATE_WORDS = 32    # GCLM_PARAM_OPT_STATE_WORDS: 32-bit words of one image's state record (gclm_param_opt_step)
 PARAM_OPT_INFO_WORDS = 12     # GCLM_PARAM_OPT_INFO_WORDS: floats per image of gclm_param_opt's d_info
 PARAM_OPT_INFO = {"steps": 0, "converged": 1, "final_cost": 2, "final_up_cost": 3, "final_latitude_cost": 4, "lr": 5, "initial": 6}
@@ -142,6 +143,10 @@ _SIGNATURES = {
     "gclm_field_errors_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gclm_field_errors": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float), _P,
                                     C.c_size_t, _P, _P, _P, _P]),
+    "gclm_field_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gclm_field_loss": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P,
+                                  _P]),
+    "gclm_field_loss_grad": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gclm_hypothesis_scores_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gclm_hypothesis_scores": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_float,
                                          C.c_float, C.c_float, _P, C.c_size_t, _P, _P, _P]),

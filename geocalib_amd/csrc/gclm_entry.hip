@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the five render kernels, the field errors, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the five render kernels, the field errors, the field losses and their gradients, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -103,6 +103,15 @@ int draw_fields(int camera_model, const float* d_cam, const float* d_grav, int c
     const bool dwords = interleaved && C == 4 && is_aligned(d_src, 4) && is_aligned(d_dst, 4);
     return launched(launch_draw_fields(camera_model, d_cam, d_grav, cal_batch, d_src, B, C, H, W, interleaved != 0, dwords, d_conf,
                                        d_palette, d_heat_palette, st, d_dst, static_cast<hipStream_t>(stream)));
+}
+
+// gclm_field_loss / gclm_field_loss_grad: the plain conditions the two share
+bool field_loss_plain_ok(int camera_model, const float* d_cam, const float* d_grav, const float* d_up, const float* d_lat,
+                         const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss) {
+    if (!d_cam || !d_grav || (!d_up && !d_lat) || (!d_up && d_up_conf) || (!d_lat && d_lat_conf) || !known_model(camera_model)) return false;
+    if (up_loss < GCLM_FIELD_LOSS_L1 || up_loss > GCLM_FIELD_LOSS_HUBER || lat_loss < GCLM_FIELD_LOSS_L1 || lat_loss > GCLM_FIELD_LOSS_HUBER)
+        return false;
+    return lat_loss != GCLM_FIELD_LOSS_DOT;
 }
 }  // namespace
 
@@ -316,6 +325,52 @@ int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav,
     if (!a.pass()) return -3;
     return launched(launch_field_errors(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, n_thresholds,
                                         thresholds_deg, d_workspace, d_stats, d_up_err, d_lat_err, static_cast<hipStream_t>(stream)));
+}
+
+size_t gclm_field_loss_workspace(int B, int H, int W) { return field_loss_workspace(B, H, W); }
+
+int gclm_field_loss(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                    const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
+                    void* d_workspace, size_t workspace_bytes, float* d_out, void* stream) {
+    if (!d_out || !d_workspace) return -3;
+    if (!field_loss_plain_ok(camera_model, d_cam, d_grav, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss)) return -3;
+    const size_t ws_bytes = field_loss_workspace(B, H, W);                       // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_out, floats(B, 4), 4);
+    a.writes(d_workspace, ws_bytes, 4);
+    a.reads(d_cam, floats(B, 8), 4);
+    a.reads(d_grav, floats(B, 3), 4);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    if (!a.pass()) return -3;
+    return launched(launch_field_loss(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss,
+                                      d_workspace, d_out, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_field_loss_grad(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                         const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
+                         const float* d_scale, float* d_grad_up, float* d_grad_lat, void* stream) {
+    if (!d_scale || (d_up != nullptr) != (d_grad_up != nullptr) || (d_lat != nullptr) != (d_grad_lat != nullptr)) return -3;
+    if (!field_loss_plain_ok(camera_model, d_cam, d_grav, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss)) return -3;
+    if (field_loss_workspace(B, H, W) == 0) return -3;                           // (the sizes the forward refuses)
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_grad_up, mul_sat(px, 2), 4);
+    a.writes(d_grad_lat, px, 4);
+    a.reads(d_cam, floats(B, 8), 4);
+    a.reads(d_grav, floats(B, 3), 4);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    a.reads(d_scale, floats(B, 2), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_field_loss_grad(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss,
+                                           d_scale, d_grad_up, d_grad_lat, static_cast<hipStream_t>(stream)));
 }
 
 size_t gclm_hypothesis_scores_workspace(int B, int N, int H, int W) { return hypothesis_scores_workspace(B, N, H, W); }

@@ -1,0 +1,344 @@
+// gclm_field_loss.hip -- gclm_field_loss / gclm_field_loss_grad: the losses the up and latitude heads are trained with, per
+// image, and their gradients with respect to the predicted fields (the reference's UpDecoder.calculate_losses /
+// LatitudeDecoder.calculate_losses, siclib/models/decoders/up_decoder.py:51-79, latitude_decoder.py:53-79), with the target
+// fields of get_perspective_field evaluated per pixel in registers (gclm_render.h: persp_up normalised, persp_lat) instead
+// of rendered to memory, read back by a dozen eager kernels and replayed backwards by autograd.
+//
+// Per pixel of one field, r = p - t per component (up: 2, latitude: 1), with s = sum_c r_c^2:
+//   l1      l = sum_c |r_c|                                   dl/dp_c = sign(r_c), 0 at 0 (a NaN stays NaN)
+//   l2      l = s                                             dl/dp_c = 2 r_c
+//   dot     l = 1 - sum_c r_c t_c  (up only; on the residual, as the reference writes it)   dl/dp_c = -t_c
+//   cauchy  l = c^2 / 2 log1p(s / c^2), c = 0.007             dl/dp_c = r_c / (1 + s / c^2)
+//   huber   l = sum_c h(r_c), delta = pi / 180: h = r^2 / 2 for |r| < delta, else delta (|r| - delta / 2)
+//                                                             dl/dp_c = clamp(r_c, -delta, delta) (a NaN stays NaN)
+// Per image: loss = sum l / (H W), or sum(l conf) / sum conf where that confidence is given (the reference's
+// loss * (conf / sum conf * H W) followed by .mean(), the confidence detached).  The gradient of a pixel is
+// scale[b, field] * dl/dp_c, times conf where given; the caller forms scale = grad_output * weight / denominator from the
+// forward's d_out.  Nothing but the inputs lives between the two calls: the gradient call evaluates the target again.
+//
+// Forward: the layout of gclm_metrics.hip -- the tile geometry of gclm_render.h, a lane sums its PX pixels in float32, a wave
+// its lanes by a butterfly, lane 0 of each wave leaves four sums in LDS and after one barrier the block writes one record
+// per tile: sum l_up (x c_up), sum c_up, sum l_lat (x c_lat), sum c_lat.  field_loss_finish_kernel (grid = B) sums each
+// image's records in float64 in a fixed order (eight strided chains, combined in order).  No atomics: the bits of an image's
+// losses depend on that image's pixels, H, W and the pixels per lane alone.
+// Gradient: the same walk with no reduction, no LDS, no barrier; plain stores (the planes are read next, by autograd).
+// The loss type is a kernel argument taken by a branch every lane of the grid takes alike, not a template parameter:
+// camera model x PX instantiations per kernel.  Pixels per lane as gclm_metrics.hip has them.  64-bit offsets.  No scratch.
+#include "gclm_render.h"
+
+namespace gclm {
+namespace {
+
+constexpr int kLossWords = 4;                // float sums per record
+constexpr int kLossChains = 8;               // summation chains per image of the second launch
+constexpr float kCauchyC2 = 0.007f * 0.007f;
+constexpr float kHuberDelta = 0.017453292519943295f;          // deg2rad(1)
+
+struct FieldLossArgs {
+    const float *cam, *grav, *up, *lat, *upc, *latc;
+    float* rec;
+    int H, W, tiles_x, up_loss, lat_loss;
+};
+
+struct FieldLossGradArgs {
+    const float *cam, *grav, *up, *lat, *upc, *latc, *scale;
+    float *grad_up, *grad_lat;
+    int H, W, tiles_x, up_loss, lat_loss;
+};
+
+__device__ __forceinline__ float huber(float r) {
+    const float a = fabsf(r);
+    return a < kHuberDelta ? 0.5f * r * r : kHuberDelta * (a - 0.5f * kHuberDelta);      // (a NaN takes the second arm: NaN)
+}
+
+// l of one pixel: r and t hold its C components
+template <int C>
+__device__ __forceinline__ float pixel_loss(int type, const float (&r)[C], const float (&t)[C]) {
+    float s = 0.f;
+    switch (type) {
+        case GCLM_FIELD_LOSS_L1:
+#pragma unroll
+            for (int c = 0; c < C; ++c) s += fabsf(r[c]);
+            return s;
+        case GCLM_FIELD_LOSS_DOT:
+#pragma unroll
+            for (int c = 0; c < C; ++c) s += r[c] * t[c];
+            return 1.f - s;
+        case GCLM_FIELD_LOSS_HUBER:
+#pragma unroll
+            for (int c = 0; c < C; ++c) s += huber(r[c]);
+            return s;
+        default:
+#pragma unroll
+            for (int c = 0; c < C; ++c) s += r[c] * r[c];
+            return type == GCLM_FIELD_LOSS_L2 ? s : (0.5f * kCauchyC2) * log1pf(s / kCauchyC2);
+    }
+}
+
+// dl/dp_c of one pixel, into g
+template <int C>
+__device__ __forceinline__ void pixel_grad(int type, const float (&r)[C], const float (&t)[C], float (&g)[C]) {
+    switch (type) {
+        case GCLM_FIELD_LOSS_L1:
+#pragma unroll
+            for (int c = 0; c < C; ++c) g[c] = r[c] > 0.f ? 1.f : (r[c] < 0.f ? -1.f : (r[c] == 0.f ? 0.f : r[c]));
+            return;
+        case GCLM_FIELD_LOSS_L2:
+#pragma unroll
+            for (int c = 0; c < C; ++c) g[c] = 2.f * r[c];
+            return;
+        case GCLM_FIELD_LOSS_DOT:
+#pragma unroll
+            for (int c = 0; c < C; ++c) g[c] = -t[c];
+            return;
+        case GCLM_FIELD_LOSS_HUBER:
+#pragma unroll
+            for (int c = 0; c < C; ++c) g[c] = r[c] < -kHuberDelta ? -kHuberDelta : (r[c] > kHuberDelta ? kHuberDelta : r[c]);
+            return;
+        default: {
+            float s = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) s += r[c] * r[c];
+            const float w = 1.f / (1.f + s / kCauchyC2);
+#pragma unroll
+            for (int c = 0; c < C; ++c) g[c] = r[c] * w;
+        }
+    }
+}
+
+// The gradient planes' stores: plain, since autograd reads the planes next.  A build with -DGCLM_FIELD_LOSS_NT_STORES=1 is the
+// measured alternative (scripts/field_loss_bench.py --variant-lib times such a build against this one).
+#ifndef GCLM_FIELD_LOSS_NT_STORES
+#define GCLM_FIELD_LOSS_NT_STORES 0
+#endif
+
+template <int PX>
+__device__ __forceinline__ void store_grad_px(const float (&v)[PX], float* p) {
+    if constexpr (GCLM_FIELD_LOSS_NT_STORES) {
+        if constexpr (PX == 1) {
+            store_nt(v[0], p);
+        } else if constexpr (PX == 2) {
+            store_nt(f32x2{v[0], v[1]}, reinterpret_cast<f32x2*>(p));
+        } else {
+            store_nt(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
+        }
+    } else if constexpr (PX == 1) {
+        *p = v[0];
+    } else if constexpr (PX == 2) {
+        *reinterpret_cast<f32x2*>(p) = f32x2{v[0], v[1]};
+    } else {
+        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+    }
+}
+
+// The per-image and per-row terms of this lane's pixels (x, y), and u, r2 of each of them.
+template <int PX>
+__device__ __forceinline__ PerspRow lane_row(const float* cam, const float* grav, int b, int x, int y, float (&u)[PX], float (&r2)[PX]) {
+    const float* cb = cam + (size_t)b * 8;
+    const float* gb = grav + (size_t)b * 3;
+    PerspRow r;
+    r.ifx = 1.f / cb[2];
+    r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
+    r.a = gb[0], r.b = gb[1], r.c = gb[2];
+    r.v = ((float)y - cb[5]) * (1.f / cb[3]);
+    r.v2 = r.v * r.v;
+    r.py = r.b - r.c * r.v;
+#pragma unroll
+    for (int j = 0; j < PX; ++j) {
+        u[j] = ((float)(x + j) - r.cx) * r.ifx;
+        r2[j] = u[j] * u[j] + r.v2;
+    }
+    return r;
+}
+
+template <int MODEL, int PX>
+__global__ __launch_bounds__(kBlock) void field_loss_kernel(const FieldLossArgs a) {
+    __shared__ float s_sum[kTileRows][kLossWords];
+    int x, y;
+    const bool in = tile_pixel<PX>(a.tiles_x, a.H, a.W, x, y);
+    const int b = blockIdx.y, wave = threadIdx.x >> 6;
+    float sum[kLossWords] = {0.f, 0.f, 0.f, 0.f};
+    if (in) {
+        float u[PX], r2[PX];
+        const PerspRow r = lane_row<PX>(a.cam, a.grav, b, x, y, u, r2);
+        // PX > 1 runs only where W % PX == 0: x is a multiple of PX, so x + PX <= W
+        const size_t hw = (size_t)a.H * a.W, o = (size_t)b * hw + (size_t)y * a.W + x;
+        if (a.up) {
+            float px[PX], py[PX], l[PX];
+            load_px<PX>(a.up + o + (size_t)b * hw, px);          // (B, 2, H, W): image b starts at 2 b H W
+            load_px<PX>(a.up + o + (size_t)b * hw + hw, py);
+#pragma unroll
+            for (int j = 0; j < PX; ++j) {
+                const f32x2 t = persp_up<MODEL>(r, u[j], r2[j], true);
+                const float tt[2] = {t.x, t.y}, rr[2] = {px[j] - t.x, py[j] - t.y};
+                l[j] = pixel_loss<2>(a.up_loss, rr, tt);
+            }
+            if (a.upc) {
+                float c[PX];
+                load_px<PX>(a.upc + o, c);
+#pragma unroll
+                for (int j = 0; j < PX; ++j) sum[0] += l[j] * c[j], sum[1] += c[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < PX; ++j) sum[0] += l[j];
+            }
+        }
+        if (a.lat) {
+            float p[PX], l[PX];
+            load_px<PX>(a.lat + o, p);
+#pragma unroll
+            for (int j = 0; j < PX; ++j) {
+                const float tt[1] = {persp_lat<MODEL>(r, u[j], r2[j])}, rr[1] = {p[j] - tt[0]};
+                l[j] = pixel_loss<1>(a.lat_loss, rr, tt);
+            }
+            if (a.latc) {
+                float c[PX];
+                load_px<PX>(a.latc + o, c);
+#pragma unroll
+                for (int j = 0; j < PX; ++j) sum[2] += l[j] * c[j], sum[3] += c[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < PX; ++j) sum[2] += l[j];
+            }
+        }
+    }
+    // every lane of the block from here on: wave sums, one record per wave in LDS, one per tile in the workspace
+#pragma unroll
+    for (int k = 0; k < kLossWords; ++k) sum[k] = wave_sum(sum[k]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kLossWords; ++k) s_sum[wave][k] = sum[k];
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < kLossWords) {
+        float s = s_sum[0][k];
+        for (int i = 1; i < kTileRows; ++i) s += s_sum[i][k];
+        a.rec[((size_t)b * gridDim.x + blockIdx.x) * kLossWords + k] = s;
+    }
+}
+
+// One block per image: word k of the image's records is summed by kLossChains chains (record t goes to chain
+// t % kLossChains), the chains are added in order, all in float64.  out (B, 4) = [up loss, latitude loss, up denominator,
+// latitude denominator]: the denominator is H W, or sum conf where that confidence is given; NaN for an absent field.
+__global__ __launch_bounds__(kBlock) void field_loss_finish_kernel(const float* __restrict__ rec, int tiles, int hw, int has_up,
+                                                                   int has_upc, int has_lat, int has_latc, float* __restrict__ out) {
+    __shared__ double part[kLossChains][kLossWords];
+    const int b = blockIdx.x, k = threadIdx.x & 31, chain = threadIdx.x >> 5;
+    if (k < kLossWords) {
+        double acc = 0.0;
+        const float* p = rec + (size_t)b * tiles * kLossWords + k;
+        for (int t = chain; t < tiles; t += kLossChains) acc += (double)p[(size_t)t * kLossWords];
+        part[chain][k] = acc;
+    }
+    __syncthreads();
+    const int field = threadIdx.x;
+    if (field < 2) {
+        double num = part[0][2 * field], den = part[0][2 * field + 1];
+        for (int i = 1; i < kLossChains; ++i) num += part[i][2 * field], den += part[i][2 * field + 1];
+        const bool has = field ? has_lat != 0 : has_up != 0, hasc = field ? has_latc != 0 : has_upc != 0;
+        if (!hasc) den = (double)hw;
+        out[(size_t)b * 4 + field] = has ? (float)(num / den) : __builtin_nanf("");
+        out[(size_t)b * 4 + 2 + field] = has ? (float)den : __builtin_nanf("");
+    }
+}
+
+template <int MODEL, int PX>
+__global__ __launch_bounds__(kBlock) void field_loss_grad_kernel(const FieldLossGradArgs a) {
+    int x, y;
+    if (!tile_pixel<PX>(a.tiles_x, a.H, a.W, x, y)) return;
+    const int b = blockIdx.y;
+    float u[PX], r2[PX];
+    const PerspRow r = lane_row<PX>(a.cam, a.grav, b, x, y, u, r2);
+    const size_t hw = (size_t)a.H * a.W, o = (size_t)b * hw + (size_t)y * a.W + x;
+    if (a.up) {
+        const float scale = a.scale[(size_t)b * 2];
+        float px[PX], py[PX], gx[PX], gy[PX];
+        load_px<PX>(a.up + o + (size_t)b * hw, px);
+        load_px<PX>(a.up + o + (size_t)b * hw + hw, py);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const f32x2 t = persp_up<MODEL>(r, u[j], r2[j], true);
+            const float tt[2] = {t.x, t.y}, rr[2] = {px[j] - t.x, py[j] - t.y};
+            float g[2];
+            pixel_grad<2>(a.up_loss, rr, tt, g);
+            gx[j] = scale * g[0], gy[j] = scale * g[1];
+        }
+        if (a.upc) {
+            float c[PX];
+            load_px<PX>(a.upc + o, c);
+#pragma unroll
+            for (int j = 0; j < PX; ++j) gx[j] *= c[j], gy[j] *= c[j];
+        }
+        store_grad_px<PX>(gx, a.grad_up + o + (size_t)b * hw);
+        store_grad_px<PX>(gy, a.grad_up + o + (size_t)b * hw + hw);
+    }
+    if (a.lat) {
+        const float scale = a.scale[(size_t)b * 2 + 1];
+        float p[PX], gl[PX];
+        load_px<PX>(a.lat + o, p);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const float tt[1] = {persp_lat<MODEL>(r, u[j], r2[j])}, rr[1] = {p[j] - tt[0]};
+            float g[1];
+            pixel_grad<1>(a.lat_loss, rr, tt, g);
+            gl[j] = scale * g[0];
+        }
+        if (a.latc) {
+            float c[PX];
+            load_px<PX>(a.latc + o, c);
+#pragma unroll
+            for (int j = 0; j < PX; ++j) gl[j] *= c[j];
+        }
+        store_grad_px<PX>(gl, a.grad_lat + o);
+    }
+}
+
+// pixels per lane of a call (gclm_metrics.hip's rule, over the planes of this call)
+int pixels_per_lane(int W, std::initializer_list<const float*> planes) {
+    uintptr_t bits = 0;
+    for (const float* p : planes) bits |= reinterpret_cast<uintptr_t>(p);
+    if (W % 4 == 0 && bits % 16 == 0) return 4;
+    return W % 2 == 0 && bits % 8 == 0 ? 2 : 1;
+}
+
+}  // namespace
+
+size_t field_loss_workspace(int B, int H, int W) {
+    if (B < 1 || B > kMaxCallImages || H < 1 || W < 1 || !tile_grid_fits(H, W)) return 0;
+    // sized for one pixel per lane, the path with the most tiles
+    return (size_t)B * tile_count(H, W, 1) * kLossWords * sizeof(float);
+}
+
+hipError_t launch_field_loss(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
+                             const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss, void* workspace,
+                             float* out, hipStream_t st) {
+    const int px = pixels_per_lane(W, {up, lat, upc, latc});
+    const FieldLossArgs a{cam, grav, up, lat, upc, latc, static_cast<float*>(workspace), H, W, tile_columns(W, px), up_loss, lat_loss};
+    const int tiles = tile_count(H, W, px);
+    return with_camera_model(camera_model, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        auto kernel = px == 4 ? field_loss_kernel<M, 4> : px == 2 ? field_loss_kernel<M, 2> : field_loss_kernel<M, 1>;
+        hipLaunchKernelGGL(kernel, dim3(tiles, B), dim3(kBlock), 0, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(field_loss_finish_kernel, dim3(B), dim3(kBlock), 0, st, static_cast<const float*>(workspace), tiles, H * W,
+                           up != nullptr, upc != nullptr, lat != nullptr, latc != nullptr, out);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_field_loss_grad(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
+                                  const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss, const float* scale,
+                                  float* grad_up, float* grad_lat, hipStream_t st) {
+    const int px = pixels_per_lane(W, {up, lat, upc, latc, grad_up, grad_lat});
+    const FieldLossGradArgs a{cam, grav, up, lat, upc, latc, scale, grad_up, grad_lat, H, W, tile_columns(W, px), up_loss, lat_loss};
+    return with_camera_model(camera_model, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        auto kernel = px == 4 ? field_loss_grad_kernel<M, 4> : px == 2 ? field_loss_grad_kernel<M, 2> : field_loss_grad_kernel<M, 1>;
+        hipLaunchKernelGGL(kernel, dim3(tile_count(H, W, px), B), dim3(kBlock), 0, st, a);
+        return hipGetLastError();
+    });
+}
+
+}  // namespace gclm

@@ -262,6 +262,15 @@ hipError_t launch_field_errors(int camera_model, const float* cam, const float* 
                                const float* thresholds /* host */, void* workspace, float* stats, float* up_err /* or nullptr */,
                                float* lat_err /* or nullptr */, hipStream_t s);
 
+// gclm_field_loss.hip
+size_t field_loss_workspace(int B, int H, int W);                         // bytes of one call's partial records; 0: sizes out of range
+hipError_t launch_field_loss(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
+                             const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss, void* workspace,
+                             float* out, hipStream_t s);
+hipError_t launch_field_loss_grad(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
+                                  const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss, const float* scale,
+                                  float* grad_up /* or nullptr */, float* grad_lat /* or nullptr */, hipStream_t s);
+
 // gclm_hypotheses.hip
 size_t hypothesis_scores_workspace(int B, int N, int H, int W);           // bytes of one call's partial records; 0: sizes out of range
 hipError_t launch_hypothesis_scores(int camera_model, const float* cam, const float* grav, int B, int N, int H, int W,

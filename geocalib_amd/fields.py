@@ -374,7 +374,70 @@ def field_errors(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: O
     return stats, up_err, lat_err
 
 
-HYPOTHESIS_CHUNK = _lib.HYPOTHESIS_CHUNK      # K: hypotheses scored per read of an image's planes (GCLM_HYPOTHESIS_CHUNK)
+def _loss_call(who: str, cam, grav, up, lat, up_conf, lat_conf, up_loss: str, lat_loss: str):
+    """What field_loss and field_loss_grad share: the checked inputs as their kernels read them -- (cam, grav, planes, B, H, W,
+    loss ids)."""
+    if up is None and lat is None:
+        raise ValueError("at least one of the up and latitude fields is needed")
+    if (up is None and up_conf is not None) or (lat is None and lat_conf is not None):
+        raise ValueError("a confidence needs its field")
+    if up_loss not in _lib.FIELD_LOSS_IDS or lat_loss not in _lib.FIELD_LOSS_IDS or lat_loss == "dot":
+        raise ValueError(f"{who}: loss types are {sorted(_lib.FIELD_LOSS_IDS)} ('dot' for the up field only), got {up_loss!r} and "
+                         f"{lat_loss!r}")
+    cam, grav = _call.dev_f32(cam, "cam").reshape(-1, 8), _call.dev_f32(grav, "grav").reshape(-1, 3)
+    dev, B = cam.device, cam.shape[0]
+    planes, H, W = _field_planes({"up": up, "lat": lat, "up_conf": up_conf, "lat_conf": lat_conf}, B, dev)
+    if grav.shape[0] != B or grav.device != dev:
+        raise ValueError(f"camera batch {B} and gravity batch {grav.shape[0]} must be equal and on one device")
+    return cam, grav, planes, B, H, W, (_lib.FIELD_LOSS_IDS[up_loss], _lib.FIELD_LOSS_IDS[lat_loss])
+
+
+def field_loss(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: Optional[torch.Tensor] = None,
+               lat: Optional[torch.Tensor] = None, up_conf: Optional[torch.Tensor] = None,
+               lat_conf: Optional[torch.Tensor] = None, up_loss: str = "l1", lat_loss: str = "l1") -> torch.Tensor:
+    """gclm_field_loss: the decoders' training losses of predicted fields `up` (B, 2, H, W) / `lat` (B, 1, H, W) (one may be
+    None) against the fields of cameras `cam` (B, 8) and gravities `grav` (B, 3), float32 on one HIP device, in one pass per
+    65 535 images on torch's current stream.  A confidence (B, H, W) weights its field's loss; None is the plain mean.
+    Returns (B, 4) as include/gclm.h lays it out: [up loss, latitude loss, up denominator, latitude denominator], NaN for an
+    absent field, no loss weight applied.  losses.perspective_field_loss is the public entry."""
+    cam, grav, planes, B, H, W, ids = _loss_call("field_loss", cam, grav, up, lat, up_conf, lat_conf, up_loss, lat_loss)
+    dev = cam.device
+    out = cam.new_empty((B, 4))
+    if B * H * W == 0:
+        return out.fill_(float("nan"))
+    ws_bytes = int(_lib.load().gclm_field_loss_workspace(min(B, _call.MAX_CALL), H, W))
+    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=dev)
+    for b0, n in _call.slices(B):
+        _call.call("gclm_field_loss", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, H, W,
+                   *(_call.ptr_at(t, b0) for t in planes.values()), *ids, ws.data_ptr(), ws_bytes, out[b0].data_ptr(),
+                   _call.raw_stream(dev), device=dev)
+    return out
+
+
+def field_loss_grad(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, scale: torch.Tensor,
+                    up: Optional[torch.Tensor] = None, lat: Optional[torch.Tensor] = None, up_conf: Optional[torch.Tensor] = None,
+                    lat_conf: Optional[torch.Tensor] = None, up_loss: str = "l1", lat_loss: str = "l1"):
+    """gclm_field_loss_grad: the gradients of field_loss's two losses with respect to the fields given, (grad_up (B, 2, H, W),
+    grad_lat (B, 1, H, W)), None for an absent field: `scale` (B, 2) = [up, latitude] (grad_output x weight / denominator, on
+    the device) times the per-pixel derivative, times the confidence where given.  The target is evaluated again in
+    registers; one launch per 65 535 images on torch's current stream."""
+    cam, grav, planes, B, H, W, ids = _loss_call("field_loss_grad", cam, grav, up, lat, up_conf, lat_conf, up_loss, lat_loss)
+    dev = cam.device
+    scale = _call.dev_f32(scale, "scale")
+    if scale.shape != (B, 2) or scale.device != dev:
+        raise ValueError(f"`scale` {tuple(scale.shape)} on {scale.device} must be ({B}, 2) on {dev}")
+    g_up = None if planes["up"] is None else torch.empty_like(planes["up"])
+    g_lat = None if planes["lat"] is None else torch.empty_like(planes["lat"])
+    if B * H * W == 0:
+        return g_up, g_lat
+    for b0, n in _call.slices(B):
+        _call.call("gclm_field_loss_grad", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, H, W,
+                   *(_call.ptr_at(t, b0) for t in planes.values()), *ids, scale[b0].data_ptr(), _call.ptr_at(g_up, b0),
+                   _call.ptr_at(g_lat, b0), _call.raw_stream(dev), device=dev)
+    return g_up, g_lat
+
+
+HYPOTHESIS_CHUNK = _lib.HYPOTHESIS_CHUNK     # K: hypotheses scored per read of an image's planes (GCLM_HYPOTHESIS_CHUNK)
 
 
 def hypothesis_scores(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up: Optional[torch.Tensor] = None,

@@ -1,0 +1,183 @@
+"""The losses the up and latitude heads are trained with (reference: UpDecoder.calculate_losses, LatitudeDecoder.calculate_losses
+and PerspectiveDecoder.loss, siclib/models/decoders/up_decoder.py:51-109, latitude_decoder.py:53-114, perspective_decoder.py:41-59).
+
+`field_loss` is the reference's calculate_losses for explicit target tensors, as a torch composition: differentiable in
+everything torch can differentiate, on any device and dtype.
+
+`perspective_field_loss` takes the targets from a camera and a gravity, which is how the reference's datasets make them.
+float32 fields on one HIP device, with a camera and a gravity that do not require grad, take the HIP path: one pass
+evaluates the target per pixel in registers and reduces the loss per image (gclm_field_loss), and when a field requires
+grad a torch.autograd.Function hands autograd the gradient of a second such pass (gclm_field_loss_grad) -- no target field
+is rendered, nothing but the inputs is kept for backward.  That path is differentiable with respect to the predicted fields
+only, once; the confidences are detached, as in the reference.  Anything else (CPU, float64, half-precision predictions, a
+camera or gravity that requires grad) renders the target with get_perspective_field and runs `field_loss`.
+
+The two paths differ where arithmetic leaves no choice: the l1 gradient of a NaN residual is NaN on the HIP path and 0 in
+torch (torch's sgn), and the HIP path takes the cauchy loss as log1p, which keeps small residuals the float32 log(1 + x)
+rounds away."""
+import math
+from typing import Dict, Optional, Sequence
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import fields, metrics
+from .camera import BaseCamera
+from .gravity import Gravity
+from .perspective_fields import get_perspective_field
+
+LOSS_TYPES = ("l1", "l2", "dot", "cauchy", "huber")
+CAUCHY_C = 0.007                    # the reference's scale: "corresponds to about 5 degrees"
+HUBER_DELTA = math.pi / 180         # deg2rad(1)
+
+
+def _check_loss_type(loss_type: str, field: str) -> None:
+    if loss_type not in LOSS_TYPES or (loss_type == "dot" and field != "up"):
+        raise ValueError(f"unknown {field} loss type {loss_type!r}: one of {LOSS_TYPES} ('dot' for the up field only)")
+
+
+def field_loss(predictions: torch.Tensor, targets: torch.Tensor, confidence: Optional[torch.Tensor] = None, loss_type: str = "l1",
+               use_uncertainty_loss: bool = True) -> torch.Tensor:
+    """The reference's calculate_losses without its weight: predictions and targets (B, C, H, W) (up: C = 2, latitude: C = 1),
+    an optional confidence (B, H, W); returns (B,).  Per pixel, with r = predictions - targets: l1 sum |r|, l2 sum r^2,
+    dot 1 - sum r t, cauchy c^2 / 2 log(1 + sum r^2 / c^2) with c = 0.007, huber nn.HuberLoss(delta=deg2rad(1)) summed over
+    C.  With a confidence and `use_uncertainty_loss` the pixel is weighted by conf / sum conf * H W, detached; then the mean.
+    Half-precision predictions are cast to float32 as the reference casts them (its predictions.float()); float64 stays
+    float64, which the reference's cast would round."""
+    if loss_type not in LOSS_TYPES:
+        raise ValueError(f"unknown loss type {loss_type!r}: one of {LOSS_TYPES}")
+    predictions = predictions.float() if predictions.dtype in (torch.float16, torch.bfloat16) else predictions
+    residuals = predictions - targets
+    if loss_type == "l2":
+        loss = (residuals ** 2).sum(axis=1)
+    elif loss_type == "l1":
+        loss = residuals.abs().sum(axis=1)
+    elif loss_type == "dot":
+        loss = 1 - (residuals * targets).sum(axis=1)
+    elif loss_type == "cauchy":
+        c = CAUCHY_C
+        loss = c ** 2 / 2 * torch.log(1 + (residuals ** 2).sum(axis=1) / c ** 2)
+    else:
+        loss = torch.nn.HuberLoss(reduction="none", delta=HUBER_DELTA)(predictions, targets.expand_as(predictions)).sum(axis=1)
+    if confidence is not None and use_uncertainty_loss:
+        confidence = confidence.reshape(loss.shape)
+        weight = confidence / confidence.sum(axis=(-2, -1), keepdims=True)
+        loss = loss * (weight * (weight.size(-1) * weight.size(-2))).detach()
+    return loss.mean(axis=(1, 2))
+
+
+class _FieldLossFunction(torch.autograd.Function):
+    """(up, lat) -> (B, 2) weighted losses [up, latitude] on the HIP path; a missing field is None and its column NaN."""
+
+    @staticmethod
+    def forward(ctx, up, lat, model, cam, grav, up_conf, lat_conf, up_loss, lat_loss, up_weight, lat_weight):
+        out = fields.field_loss(model, cam, grav, up, lat, up_conf, lat_conf, up_loss, lat_loss)
+        ctx.save_for_backward(*(t for t in (up, lat, up_conf, lat_conf) if t is not None), cam, grav, out[:, 2:])
+        ctx.given = [t is not None for t in (up, lat, up_conf, lat_conf)]
+        ctx.call = (model, up_loss, lat_loss, up_weight, lat_weight)
+        # (the weights stay host floats: a tensor of them would be a blocking copy to the device in every step)
+        return torch.stack([out[:, 0] * up_weight, out[:, 1] * lat_weight], 1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
+        up, lat, up_conf, lat_conf = (saved.pop(0) if g else None for g in ctx.given)
+        cam, grav, den = saved
+        model, up_loss, lat_loss, up_weight, lat_weight = ctx.call
+        if not ctx.needs_input_grad[0]:              # a field that asks for no gradient is left out of the pass
+            up = up_conf = None
+        if not ctx.needs_input_grad[1]:
+            lat = lat_conf = None
+        # grad_output x weight / denominator, on the device; an absent field's column is never read
+        scale = grad_out.to(torch.float32) / den
+        scale[:, 0] *= up_weight
+        scale[:, 1] *= lat_weight
+        g_up, g_lat = fields.field_loss_grad(model, cam, grav, scale, up, lat, up_conf, lat_conf, up_loss, lat_loss)
+        return (g_up, g_lat) + (None,) * 9
+
+
+def _hip_path(tensors, cam: torch.Tensor, grav: torch.Tensor) -> bool:
+    """Whether these inputs take gclm_field_loss: all float32 on one HIP device, matching batches, camera and gravity without
+    grad (the fields may require it)."""
+    dev = cam.device
+    return (all(t.is_cuda and t.dtype == torch.float32 and t.device == dev for t in list(tensors) + [cam, grav])
+            and not (cam.requires_grad or grav.requires_grad) and cam.dim() == grav.dim() == 2 and cam.shape[0] == grav.shape[0]
+            and all(t.shape[0] == cam.shape[0] for t in tensors))
+
+
+def _field_loss_torch(pred, camera, gravity, types, use_uncertainty_loss):
+    """The torch composition: {field: (B,) unweighted loss} against the fields of get_perspective_field."""
+    up_t, lat_t = get_perspective_field(camera, gravity, use_up="up_field" in pred, use_latitude="latitude_field" in pred)
+    out = {}
+    for name, target in (("up", up_t), ("latitude", lat_t)):
+        if f"{name}_field" in pred:
+            out[name] = field_loss(pred[f"{name}_field"], target, pred.get(f"{name}_confidence"), types[name], use_uncertainty_loss)
+    return out
+
+
+def perspective_field_loss(pred: Dict[str, torch.Tensor], camera: BaseCamera, gravity: Gravity, up_loss: str = "l1",
+                           latitude_loss: str = "l1", use_uncertainty_loss: bool = True, up_loss_weight: float = 1.0,
+                           latitude_loss_weight: float = 1.0) -> Dict[str, torch.Tensor]:
+    """The decoders' losses of the fields in `pred` against the calibration (camera, gravity), per image.
+
+    `pred` is the dict LMOptimizer and metrics.perspective_field_metrics take: "up_field" (B, 2, H, W), "latitude_field"
+    (B, 1, H, W) in radians, optionally "up_confidence", "latitude_confidence" (B, H, W) or (B, 1, H, W); at least one field.
+    Returns the reference's keys, each (B,): "up-{type}-loss" and "up_total", "latitude-{type}-loss" and "latitude_total" --
+    a field's keys only when the field is in `pred` -- and "perspective_total", their sum.  The weights multiply the losses,
+    as the decoders' loss_weight.  A confidence weights its field's pixels by conf / sum conf (detached) when
+    `use_uncertainty_loss`; sum conf = 0 gives NaN.
+
+    float32 HIP fields with a camera and gravity that do not require grad take the HIP path (module docstring), also when a
+    field requires grad; anything else the torch composition.  Raises ValueError for an unknown loss type and for 'dot' on
+    the latitude, on both paths."""
+    if "up_field" not in pred and "latitude_field" not in pred:
+        raise ValueError("`pred` holds neither up_field nor latitude_field")
+    types = {"up": up_loss, "latitude": latitude_loss}
+    for name, t in types.items():
+        _check_loss_type(t, name)
+    if len(camera.shape) == 0:
+        camera, gravity = camera.unsqueeze(0), gravity.unsqueeze(0)
+    pred = dict(pred)
+    for name in ("up", "latitude"):
+        conf = pred.get(f"{name}_confidence")
+        if f"{name}_field" not in pred:
+            pred.pop(f"{name}_confidence", None)
+        elif conf is not None and conf.dim() == 4:
+            pred[f"{name}_confidence"] = conf.reshape(conf.shape[0], *conf.shape[-2:])
+    given = [pred[k] for f in ("up", "latitude") for k in (f"{f}_field", f"{f}_confidence") if k in pred]
+    cam, grav = camera._data, gravity._data
+    if _hip_path(given, cam, grav):
+        confs = [pred.get(f"{f}_confidence") if use_uncertainty_loss else None for f in ("up", "latitude")]
+        both = _FieldLossFunction.apply(pred.get("up_field"), pred.get("latitude_field"), camera.name(), cam, grav,
+                                        *(None if c is None else c.detach() for c in confs), up_loss, latitude_loss,
+                                        float(up_loss_weight), float(latitude_loss_weight))
+        per_field = {name: both[:, i] for i, name in enumerate(("up", "latitude")) if f"{name}_field" in pred}
+    else:
+        weights = {"up": up_loss_weight, "latitude": latitude_loss_weight}
+        per_field = {k: v * weights[k] for k, v in _field_loss_torch(pred, camera, gravity, types, use_uncertainty_loss).items()}
+    out, total = {}, 0
+    for name, loss in per_field.items():
+        out[f"{name}-{types[name]}-loss"] = loss
+        out[f"{name}_total"] = 0 + loss
+        total = total + loss
+    out["perspective_total"] = total
+    return out
+
+
+def perspective_decoder_loss(pred: Dict[str, torch.Tensor], camera: BaseCamera, gravity: Gravity,
+                             recall_thresholds: Sequence[float] = (1, 3, 5, 10), **loss_options):
+    """(losses, metrics), the pair PerspectiveDecoder.loss returns: perspective_field_loss(pred, camera, gravity,
+    **loss_options) and metrics.perspective_field_metrics on the detached fields -- the scorer keeps its HIP pass while the
+    loss carries the graph."""
+    losses = perspective_field_loss(pred, camera, gravity, **loss_options)
+    detached = {k: v.detach() for k, v in pred.items() if torch.is_tensor(v) and k in
+                ("up_field", "latitude_field", "up_confidence", "latitude_confidence")}
+    for name in ("up", "latitude"):
+        conf = detached.get(f"{name}_confidence")
+        if f"{name}_field" not in detached:
+            detached.pop(f"{name}_confidence", None)
+        elif conf is not None and conf.dim() == 4:
+            detached[f"{name}_confidence"] = conf.reshape(conf.shape[0], *conf.shape[-2:])
+    with torch.no_grad():
+        return losses, metrics.perspective_field_metrics(detached, camera, gravity, recall_thresholds)

@@ -55,7 +55,9 @@ extern "C" {
  * gclm_draw_fields and gclm_draw_fields_u8 added, also within 610: the perspective fields drawn over an image;
  * gclm_pack_fields_bins added, also within 610: the head epilogue for classification heads;
  * gclm_param_opt, gclm_param_opt_cost, gclm_param_opt_step, gclm_param_opt_workspace and gclm_default_param_opt_config added, also
- * within 610: Adam on (roll, pitch, vfov) against perspective fields, the reference's third optimiser).  gclm_create refuses a gclm_config whose first two fields do not
+ * within 610: Adam on (roll, pitch, vfov) against perspective fields, the reference's third optimiser;
+ * gclm_field_loss, gclm_field_loss_grad and gclm_field_loss_workspace added, also within 610: the decoders' training losses
+ * against a calibration and their gradients with respect to the predicted fields).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -530,6 +532,57 @@ int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav,
                       const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int n_thresholds,
                       const float* thresholds_deg, void* d_workspace, size_t workspace_bytes, float* d_stats, float* d_up_err,
                       float* d_lat_err, void* stream);
+
+/*
+ * The losses the up and latitude heads are trained with, per image, and their gradients with respect to the predicted
+ * fields: the reference's UpDecoder.calculate_losses / LatitudeDecoder.calculate_losses (siclib/models/decoders/
+ * up_decoder.py:51-79, latitude_decoder.py:53-79), with the target fields of gclm_perspective_fields (normalize_up = 1) at
+ * d_cam (B, 8) / d_grav (B, 3) evaluated per pixel in registers -- no target field is written or read, and nothing but the
+ * inputs lives between the forward and the gradient call.  Planes as gclm_field_errors takes them: d_up (B, 2, H, W) planar,
+ * d_lat (B, 1, H, W), either may be NULL, not both; confidences d_up_conf, d_lat_conf (B, H, W), either may be NULL -- a
+ * NULL confidence is how a caller expresses use_uncertainty_loss = False.  All float32 in device memory; gravity is used as
+ * stored.  Per pixel of a field, with r = p - t per component (up: 2, latitude: 1) and s = sum_c r_c^2:
+ *   GCLM_FIELD_LOSS_L1      l = sum_c |r_c|                            dl/dp_c = sign(r_c), 0 at 0
+ *   GCLM_FIELD_LOSS_L2      l = s                                      dl/dp_c = 2 r_c
+ *   GCLM_FIELD_LOSS_DOT     l = 1 - sum_c r_c t_c  (up only; on the residual, as the reference writes it)   dl/dp_c = -t_c
+ *   GCLM_FIELD_LOSS_CAUCHY  l = c^2 / 2 log1p(s / c^2), c = 0.007      dl/dp_c = r_c / (1 + s / c^2)
+ *   GCLM_FIELD_LOSS_HUBER   l = sum_c h(r_c), delta = pi / 180 (nn.HuberLoss(delta=deg2rad(1))): h = r^2 / 2 for |r| < delta,
+ *                           else delta (|r| - delta / 2)               dl/dp_c = clamp(r_c, -delta, delta)
+ * gclm_field_loss: d_out (B, 4) = [up loss, latitude loss, up denominator, latitude denominator], loss = sum l / (H W) with
+ * denominator H W, or sum(l conf) / sum conf with denominator sum conf where that confidence is given (the reference's
+ * loss * (conf / sum conf * H W) followed by .mean()); no loss weight is applied; both entries of a NULL field are NaN.
+ * sum conf = 0 gives NaN (0 / 0); a NaN prediction makes the loss of its image and field NaN and leaves the others untouched.
+ * Every workgroup leaves one record of four float32 sums in d_workspace, of at least gclm_field_loss_workspace(B, H, W)
+ * bytes (0 for sizes the call refuses); a second small launch sums each image's records in float64 in a fixed order.  No
+ * atomics: results are bit-identical from call to call and do not depend on the other images of the batch (they depend on
+ * the image's pixels, H, W and the pixels per lane, chosen as gclm_field_errors chooses them).
+ * gclm_field_loss_grad: d_grad_up (B, 2, H, W) and d_grad_lat (B, 1, H, W), each given exactly when its field is:
+ *   grad = d_scale[b, field] * dl/dp_c * (conf where that confidence is given),
+ * d_scale (B, 2) = [up, latitude] in device memory, which the caller forms as grad_output * weight / denominator from d_out.
+ * A NaN residual gives a NaN gradient at that pixel only (dot: -t_c does not depend on p); a NaN or zero-denominator scale
+ * reaches every pixel of its image and field.  There is no gradient to the confidences, the camera or the gravity.
+ * Both return -3 (before any HIP call) for whatever gclm_field_errors refuses among the arguments they share (NULL d_cam or
+ * d_grav, both fields NULL, a confidence given for a NULL field, B outside 1..65535, H or W < 1, H * W > 2^31 - 1 or a tile
+ * grid over 2^32 threads, a camera_model outside 0..3), a loss id outside 0..4, GCLM_FIELD_LOSS_DOT for the latitude, a
+ * pointer that is not 4-byte aligned, and an output that overlaps an input or another output; gclm_field_loss also for a
+ * NULL d_out or d_workspace and a workspace that is too small; gclm_field_loss_grad also for a NULL d_scale, a gradient plane
+ * given for a NULL field and a field without its gradient plane.  -10 if a launch fails.  Asynchronous on `stream`; no
+ * allocation.
+ */
+enum gclm_field_loss {         /* (a tag: it shares no name space with the function below) */
+    GCLM_FIELD_LOSS_L1 = 0,
+    GCLM_FIELD_LOSS_L2 = 1,
+    GCLM_FIELD_LOSS_DOT = 2,
+    GCLM_FIELD_LOSS_CAUCHY = 3,
+    GCLM_FIELD_LOSS_HUBER = 4
+};
+size_t gclm_field_loss_workspace(int B, int H, int W);
+int gclm_field_loss(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                    const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
+                    void* d_workspace, size_t workspace_bytes, float* d_out, void* stream);
+int gclm_field_loss_grad(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                         const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
+                         const float* d_scale, float* d_grad_up, float* d_grad_lat, void* stream);
 
 /*
  * Which of N candidate calibrations per image fits the image's predicted perspective fields best, in one pass over the
