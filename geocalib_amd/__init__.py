@@ -1,7 +1,10 @@
 """geocalib_amd -- MI355X-native (gfx950) implementation of GeoCalib's LM calibration path.
 
 Public surface (mirrors the reference's geocalib package for this path):
-    LMOptimizer                         geocalib/lm_optimizer.py:141   (+ optimizer_step, update_lambda, early_stop)
+    LMOptimizer                         geocalib/lm_optimizer.py:141   (+ optimizer_step, update_lambda, early_stop; conf
+                                        "differentiable": gradients through the LM steps to the fields and confidences,
+                                        .loss / .metrics of siclib/models/optimization/lm_optimizer.py:577-625)
+    lm_grad                             the recorded HIP solve, its HIP adjoint, and lm_unrolled_torch: the unrolled loop in torch
     Camera models / camera_models       geocalib/camera.py
     Gravity                             geocalib/gravity.py
     GeoCalib (extractor with calibrate) geocalib/extractor.py:15  (CNN supplied by the caller)
@@ -28,5 +31,6 @@ from . import perspective_encoding  # noqa: F401,E402
 from .perspective_opt import PerspectiveParamOpt  # noqa: F401,E402
 from . import losses  # noqa: F401,E402
 from .losses import perspective_decoder_loss, perspective_field_loss  # noqa: F401,E402
+from . import lm_grad  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -27,6 +27,7 @@ PARAM_OPT_STATE_WORDS = 32    # GCLM_PARAM_OPT_STATE_WORDS: 32-bit words of one 
 PARAM_OPT_INFO_WORDS = 12     # GCLM_PARAM_OPT_INFO_WORDS: floats per image of gclm_param_opt's d_info
 PARAM_OPT_INFO = {"steps": 0, "converged": 1, "final_cost": 2, "final_up_cost": 3, "final_latitude_cost": 4, "lr": 5, "initial": 6}
 PARAM_OPT_MAX_PATIENCE = 8    # GCLM_PARAM_OPT_MAX_PATIENCE
+LM_RECORD_STRIDE = 48         # GCLM_LM_RECORD_STRIDE: floats per image and step of the record of gclm_solve_recorded
 ABI_VERSION = 610         # GCLM_VERSION of include/gclm.h this binding was written against
 INFO = {"stop_at": 0, "initial_up_cost": 1, "initial_latitude_cost": 2, "initial_cost": 3,
         "final_up_cost": 4, "final_latitude_cost": 5, "final_cost": 6, "roll_uncertainty": 7,
@@ -112,6 +113,12 @@ _SIGNATURES = {
     "gclm_solve_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "gclm_calibrate_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P,
                                     _P]),
+    "gclm_solve_recorded": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "gclm_calibrate_recorded": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P,
+                                          _P]),
+    "gclm_lm_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gclm_lm_backward": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_float, C.c_float,
+                                   C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "gclm_system": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
     "gclm_shared_begin": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
     "gclm_shared_begin_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P]),

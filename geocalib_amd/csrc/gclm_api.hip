@@ -493,14 +493,14 @@ int solve_one_launch_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, float
 
 // init | { sweep(theta_i) ; update_i } x num_steps | prep_final ; sweep(theta_final, rpf) ; finalize
 int solve_two_launches_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, float* d_cam_out, float* d_grav_out,
-                                float* d_info_out, hipStream_t s) {
+                                float* d_info_out, hipStream_t s, float* d_record = nullptr) {
     const SolveCtx& c = h->ctx;
     const bool es = h->cfg.early_stop != 0;
     GCLM_HIP(h, launch_init(c, ia, s));
     for (int step = 0; step < h->cfg.num_steps; ++step) {
         if (int rc = timed_sweep(h, p.next_sweep(h, c.pb[step & 1], true, es ? step : 0), s)) return rc;
         if (!h->cfg.shared_intrinsics) {
-            GCLM_HIP(h, launch_update(c, step, s));
+            GCLM_HIP(h, launch_update(c, step, s, d_record));
         } else {
             GCLM_HIP(h, launch_shared_step(c, step, s));     // reduce + Schur solve + update: one launch
         }
@@ -517,8 +517,9 @@ int solve_two_launches_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, flo
 }
 
 int run_solve(gclm_handle* h, const Fields& f, int B, int H, int W, const InitArgs& ia, float* d_cam_out,
-              float* d_grav_out, float* d_info_out, const float* d_sin_lat, void* stream) {
+              float* d_grav_out, float* d_info_out, const float* d_sin_lat, void* stream, float* d_record = nullptr) {
     if (int rc = check_shapes(h, f.lat, B, H, W)) return rc;
+    if (d_record && h->cfg.shared_intrinsics) return fail(h, -3, "the step record is kept for per-image solves only");
     if (B > 0 && (!d_cam_out || !d_grav_out || !d_info_out)) return fail(h, -3, "null output pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (B == 0) return solve_empty_shard(h, H, W, ia, s);
@@ -530,7 +531,15 @@ int run_solve(gclm_handle* h, const Fields& f, int B, int H, int W, const InitAr
     h->ctx.iso_final = (ia.cam == nullptr && ia.scales == nullptr && GCLM_ISO_FINAL) ? 1 : 0;
     Plan p;
     if (int rc = make_plan(h, p, f, B, H, W, d_sin_lat, h->cfg.num_steps + 1)) return rc;
-    return (p.one_launch ? solve_one_launch_per_step : solve_two_launches_per_step)(h, p, ia, d_cam_out, d_grav_out, d_info_out, s);
+    if (d_record) {
+        // the record is written by the per-image update kernel: a call planned as one launch per step takes its two-launch
+        // twin (same geometry, no plane of its own: the plan above stands), which computes the same bits
+        p.one_launch = false;
+        GCLM_HIP(h, hipMemsetAsync(d_record, 0, sizeof(float) * GCLM_LM_RECORD_STRIDE * (size_t)B * h->cfg.num_steps, s));
+        return solve_two_launches_per_step(h, p, ia, d_cam_out, d_grav_out, d_info_out, s, d_record);
+    }
+    if (p.one_launch) return solve_one_launch_per_step(h, p, ia, d_cam_out, d_grav_out, d_info_out, s);
+    return solve_two_launches_per_step(h, p, ia, d_cam_out, d_grav_out, d_info_out, s);
 }
 
 }  // namespace
@@ -846,15 +855,27 @@ int gclm_last_pass_timing(gclm_handle* h, int* n_launches, float* total_ms) {
     return 0;
 }
 
-int gclm_solve_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
-                  const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
-                  float* d_info_out, const float* d_sin_lat, void* stream) {
+static int solve_entry(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                       const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
+                       float* d_info_out, const float* d_sin_lat, float* d_record, void* stream) {
     if (!h) return -1;
     InitArgs ia{};
     ia.cam = d_cam_io;
     ia.grav = d_grav_io;
     if (B != 0 && (!d_cam_io || !d_grav_io)) return fail(h, -3, "gclm_solve: null camera / gravity pointer");
-    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_io, d_grav_io, d_info_out, d_sin_lat, stream);
+    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_io, d_grav_io, d_info_out, d_sin_lat, stream, d_record);
+}
+
+int gclm_solve_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                  const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
+                  float* d_info_out, const float* d_sin_lat, void* stream) {
+    return solve_entry(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_cam_io, d_grav_io, d_info_out, d_sin_lat, nullptr, stream);
+}
+
+int gclm_solve_recorded(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                        const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
+                        float* d_info_out, float* d_record, void* stream) {
+    return solve_entry(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_cam_io, d_grav_io, d_info_out, nullptr, d_record, stream);
 }
 
 int gclm_solve(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
@@ -863,11 +884,11 @@ int gclm_solve(gclm_handle* h, const float* d_up, const float* d_lat, const floa
     return gclm_solve_ex(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_cam_io, d_grav_io, d_info_out, nullptr, stream);
 }
 
-int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
-                      const float* d_lat_conf, int B, int H, int W, const float* d_scales,
-                      const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
-                      int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
-                      const float* d_sin_lat, void* stream) {
+static int calibrate_entry(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                           const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                           const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                           int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
+                           const float* d_sin_lat, float* d_record, void* stream) {
     if (!h) return -1;
     if (d_prior_dist && (prior_dist_cols < 1 || prior_dist_cols > 2)) return fail(h, -3, "gclm_calibrate: prior_dist_cols must be 1 or 2");
     // the free-parameter flags must agree with the priors (setup_optimization_and_priors, :204-221); an empty batch has
@@ -884,7 +905,25 @@ int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, con
     ia.lat = d_lat;
     if (h->cfg.heuristic_init && !d_up && B != 0) return fail(h, -3, "gclm_calibrate: heuristic_init needs the up field");
     // (the initial estimate -- the heuristic one reads `lat` -- always reads the radians: ia.lat)
-    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, d_sin_lat, stream);
+    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, d_sin_lat, stream, d_record);
+}
+
+int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                      const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                      const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                      int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
+                      const float* d_sin_lat, void* stream) {
+    return calibrate_entry(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_scales, d_prior_focal, d_prior_gravity, d_prior_dist,
+                           prior_dist_cols, d_cam_out, d_grav_out, d_info_out, d_sin_lat, nullptr, stream);
+}
+
+int gclm_calibrate_recorded(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                            const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                            const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                            int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
+                            float* d_record, void* stream) {
+    return calibrate_entry(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_scales, d_prior_focal, d_prior_gravity, d_prior_dist,
+                           prior_dist_cols, d_cam_out, d_grav_out, d_info_out, nullptr, d_record, stream);
 }
 
 int gclm_calibrate(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,

@@ -324,9 +324,11 @@ __device__ inline void cost_bookkeeping(const gclm_config& cfg, Ctrl* ctrl, int 
 struct StepDelta {
     float dg0, dg1, df, dk1, dk2;
 };
+// (`d`: the full-size solution over the columns (d1, d2, f, k1[, k2]), zero in fixed columns and after a failed step --
+//  what the step record of gclm_solve_recorded keeps)
 template <int PM>
 __device__ inline bool lm_solve(const gclm_config& cfg, int H, int W, int step, State& s, const float (&acc)[kNAccMax],
-                                StepDelta& dl) {
+                                StepDelta& dl, float (&d)[PM]) {
     const float invN = 1.0f / (float)((size_t)H * W);
     float cu, cl;
     const float total = total_cost(acc, invN, true, cu, cl);   // A_CU is 0 without an up field
@@ -334,7 +336,7 @@ __device__ inline bool lm_solve(const gclm_config& cfg, int H, int W, int step, 
     const bool moved = cost_rules(cfg, step, total, s, !cfg.fix_lambda);
 
     // damped normal equations over the estimated columns (lm_optimizer.py:109-137)
-    float A[PM][PM], d[PM];
+    float A[PM][PM];
     bool act[PM];
     unpack_system<PM>(acc, A, d);
     active_columns<PM>(cfg, act);
@@ -356,6 +358,12 @@ __device__ inline bool lm_solve(const gclm_config& cfg, int H, int W, int step, 
     split_delta<PM>(cfg, d, dl.dg0, dl.dg1, dl.df, dl.dk1, dl.dk2);
     return moved;
 }
+template <int PM>
+__device__ inline bool lm_solve(const gclm_config& cfg, int H, int W, int step, State& s, const float (&acc)[kNAccMax],
+                                StepDelta& dl) {
+    float d[PM];
+    return lm_solve<PM>(cfg, H, W, step, s, acc, dl, d);
+}
 __device__ inline void lm_apply_gravity(const gclm_config& cfg, State& s, const StepDelta& dl) {
     const V3 g = grav_update({s.gx, s.gy, s.gz}, dl.dg0, dl.dg1, cfg.use_spherical_manifold != 0);
     s.gx = g.x; s.gy = g.y; s.gz = g.z;
@@ -367,13 +375,19 @@ __device__ inline void lm_apply_dist(const gclm_config& cfg, State& s, const Ste
     if (cfg.camera_model != GCLM_PINHOLE && cfg.estimate_dist) update_dist(s, cfg.camera_model, dl.dk1, dl.dk2);
 }
 template <int PM>
-__device__ inline bool lm_step(const gclm_config& cfg, int H, int W, int step, State& s, const float (&acc)[kNAccMax]) {
+__device__ inline bool lm_step(const gclm_config& cfg, int H, int W, int step, State& s, const float (&acc)[kNAccMax],
+                               float (&d)[PM]) {
     StepDelta dl;
-    const bool moved = lm_solve<PM>(cfg, H, W, step, s, acc, dl);
+    const bool moved = lm_solve<PM>(cfg, H, W, step, s, acc, dl, d);
     lm_apply_gravity(cfg, s, dl);
     lm_apply_focal(cfg, s, dl);
     lm_apply_dist(cfg, s, dl);
     return moved;
+}
+template <int PM>
+__device__ inline bool lm_step(const gclm_config& cfg, int H, int W, int step, State& s, const float (&acc)[kNAccMax]) {
+    float d[PM];
+    return lm_step<PM>(cfg, H, W, step, s, acc, d);
 }
 
 // The state after update `step` and its parameter block go into the OTHER half of the double buffers, for the next sweep.

@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the five render kernels, the field errors, the field losses and their gradients, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the five render kernels, the field errors, the field losses and their gradients, the adjoint of the LM steps, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -371,6 +371,42 @@ int gclm_field_loss_grad(int camera_model, const float* d_cam, const float* d_gr
     if (!a.pass()) return -3;
     return launched(launch_field_loss_grad(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss,
                                            d_scale, d_grad_up, d_grad_lat, static_cast<hipStream_t>(stream)));
+}
+
+size_t gclm_lm_backward_workspace(int B, int H, int W) { return lm_backward_workspace(B, H, W); }
+
+int gclm_lm_backward(int camera_model, const float* d_up, const float* d_lat, const float* d_up_conf, const float* d_lat_conf,
+                     int B, int H, int W, const float* d_record, int num_steps, int early_stop, const float* d_info,
+                     float up_scale, float lat_scale, int estimate_gravity, int estimate_focal, int estimate_dist,
+                     const float* d_grad_cam, const float* d_grad_grav, float* d_grad_up, float* d_grad_lat,
+                     float* d_grad_up_conf, float* d_grad_lat_conf, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (camera_model != GCLM_PINHOLE && camera_model != GCLM_SIMPLE_RADIAL) return -3;
+    if (!d_lat || !d_record || !d_grad_cam || !d_grad_grav || !d_workspace || (early_stop && !d_info)) return -3;
+    if (num_steps < 1 || num_steps > GCLM_MAX_STEPS || !(up_scale > 0.f) || !(lat_scale > 0.f)) return -3;
+    // a gradient plane only for an input that is there (the up confidence counts only beside the up field)
+    if ((d_grad_up && !d_up) || (d_grad_up_conf && !(d_up && d_up_conf)) || (d_grad_lat_conf && !d_lat_conf)) return -3;
+    const size_t ws_bytes = lm_backward_workspace(B, H, W);                      // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_grad_up, mul_sat(px, 2), 4);
+    a.writes(d_grad_lat, px, 4);
+    a.writes(d_grad_up_conf, px, 4);
+    a.writes(d_grad_lat_conf, px, 4);
+    a.writes(d_workspace, ws_bytes, 8);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    a.reads(d_record, floats(B, num_steps, GCLM_LM_RECORD_STRIDE), 4);
+    a.reads(d_info, floats(B, GCLM_INFO_STRIDE), 4);
+    a.reads(d_grad_cam, floats(B, 8), 4);
+    a.reads(d_grad_grav, floats(B, 3), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_lm_backward(camera_model, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_record, num_steps, early_stop,
+                                       d_info, up_scale, lat_scale, estimate_gravity, estimate_focal, estimate_dist, d_grad_cam,
+                                       d_grad_grav, d_grad_up, d_grad_lat, d_grad_up_conf, d_grad_lat_conf, d_workspace,
+                                       static_cast<hipStream_t>(stream)));
 }
 
 size_t gclm_hypothesis_scores_workspace(int B, int N, int H, int W) { return hypothesis_scores_workspace(B, N, H, W); }

@@ -201,7 +201,7 @@ hipError_t launch_jacobian_fields(int camera_model, const float* d_cam, const fl
 
 // gclm_update.hip
 hipError_t launch_init(const SolveCtx& c, const InitArgs& ia, hipStream_t s);
-hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s);
+hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s, float* d_record = nullptr);   // d_record: gclm_solve_recorded
 hipError_t launch_prep_final(const SolveCtx& c, hipStream_t s);
 hipError_t launch_finalize(const SolveCtx& c, float* d_cam, float* d_grav, float* d_info, hipStream_t s);
 hipError_t launch_merge_stop(const MergeStopArgs& a, hipStream_t s);
@@ -270,6 +270,15 @@ hipError_t launch_field_loss(int camera_model, const float* cam, const float* gr
 hipError_t launch_field_loss_grad(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
                                   const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss, const float* scale,
                                   float* grad_up /* or nullptr */, float* grad_lat /* or nullptr */, hipStream_t s);
+
+// gclm_lm_grad.hip
+size_t lm_backward_workspace(int B, int H, int W);                        // bytes of one call's workspace; 0: sizes out of range
+hipError_t launch_lm_backward(int camera_model, const float* up, const float* lat, const float* upc, const float* latc, int B, int H,
+                              int W, const float* record, int num_steps, int early_stop, const float* info, float up_scale,
+                              float lat_scale, int estimate_gravity, int estimate_focal, int estimate_dist, const float* grad_cam,
+                              const float* grad_grav, float* grad_up /* or nullptr */, float* grad_lat /* or nullptr */,
+                              float* grad_up_conf /* or nullptr */, float* grad_lat_conf /* or nullptr */, void* workspace,
+                              hipStream_t s);
 
 // gclm_hypotheses.hip
 size_t hypothesis_scores_workspace(int B, int N, int H, int W);           // bytes of one call's partial records; 0: sizes out of range

@@ -69,8 +69,11 @@ __global__ void init_kernel(SolveCtx c, InitArgs ia) {
 }
 
 // Independent intrinsics: reduce the partial records, then one thread per image applies the LM step.
+// `record` (gclm_solve_recorded): null, or (B, num_steps, GCLM_LM_RECORD_STRIDE) floats; the image's leader leaves row `step`
+// there -- the state the step started from, the damping used, the full-size step, "failed", "executed" and the reduced
+// accumulator record (include/gclm.h has the layout).  Plain vector stores of values the step computes anyway.
 template <int PM>
-__global__ __launch_bounds__(kGroups * kSlots) void update_kernel(SolveCtx c, int step) {
+__global__ __launch_bounds__(kGroups * kSlots) void update_kernel(SolveCtx c, int step, float* record) {
     if (c.cfg.early_stop && stop_fired_before(c.ctrl, step)) return;          // block-uniform
     // the leader of an image fetches its state BEFORE the reduction: the load overlaps the partial records' round trip
     // instead of heading the serial chain behind it
@@ -79,8 +82,21 @@ __global__ __launch_bounds__(kGroups * kSlots) void update_kernel(SolveCtx c, in
     if (r.leader) s = c.state[step & 1][r.b];
     float acc[kNAccMax];
     if (!coop_reduce_partials(c, r, acc)) return;
-    if (lm_step<PM>(c.cfg, c.H, c.W, step, s, acc)) atomicAdd(&c.ctrl->notclose[step], 1);
+    const State s0 = s;
+    float d[PM];
+    if (lm_step<PM>(c.cfg, c.H, c.W, step, s, acc, d)) atomicAdd(&c.ctrl->notclose[step], 1);
     commit_state(c, step, r.b, s);
+    if (record) {
+        float* o = record + ((size_t)r.b * c.cfg.num_steps + step) * GCLM_LM_RECORD_STRIDE;
+        params_from_state(s0, o + GCLM_LM_RECORD_CAMERA, o + GCLM_LM_RECORD_GRAVITY);
+        o[GCLM_LM_RECORD_LAMBDA] = s.lambda;                 // (the rule ran before the solve: the damping this step used)
+#pragma unroll
+        for (int i = 0; i < GCLM_MAX_PARAMS; ++i) o[GCLM_LM_RECORD_DELTA + i] = i < PM ? d[i < PM ? i : 0] : 0.f;
+        o[GCLM_LM_RECORD_FAILED] = s.fails != s0.fails ? 1.f : 0.f;
+        o[GCLM_LM_RECORD_EXECUTED] = 1.f;
+#pragma unroll
+        for (int i = 0; i < kNAccMax; ++i) o[GCLM_LM_RECORD_SYSTEM + i] = acc[i];
+    }
 }
 
 // Parameter block of the final sweep: (roll, pitch, focal) parametrisation (lm_optimizer.py:481-483).
@@ -557,8 +573,8 @@ hipError_t launch_init(const SolveCtx& c, const InitArgs& ia, hipStream_t s) {
     GCLM_L(init_kernel, c.B > 0 ? c.B : 1, s, c, ia);     // B = 0 (an empty shard of the split protocol): thread 0 still resets Ctrl
     return hipGetLastError();
 }
-hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s) {
-    return with_system_size(c.cfg.camera_model, [&](auto pm, auto) { GCLM_LR(update_kernel<pm>, c.B, s, c, step); });
+hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s, float* d_record) {
+    return with_system_size(c.cfg.camera_model, [&](auto pm, auto) { GCLM_LR(update_kernel<pm>, c.B, s, c, step, d_record); });
 }
 hipError_t launch_prep_final(const SolveCtx& c, hipStream_t s) {
     GCLM_L(prep_final_kernel, c.B, s, c);

@@ -175,6 +175,10 @@ class LMOptimizer(nn.Module):
         # {"trivial", "heuristic"} (siclib/models/optimization/utils.py:16-82), or {"name": "ransac", ...RPFSolver conf}: the
         # estimate of ransac.RPFSolver, which does not depend on a fixed starting point
         "init_conf": {"name": "trivial"},
+        # True: `forward` returns a camera and a gravity whose data carry an autograd graph to the fields and the confidences
+        # of `data` (lm_grad.py: the recorded HIP solve forward, the HIP adjoint of its LM steps backward)
+        "differentiable": False,
+        "loss_weight": 1.0,               # factor of every loss of `loss` (siclib/models/optimization/lm_optimizer.py:624)
     }
 
     # squared_loss (siclib/models/optimization/losses.py:26) is the Huber loss with an unreachable threshold:
@@ -346,9 +350,10 @@ class LMOptimizer(nn.Module):
                              f"{tuple(lat.shape)}")
         return t
 
-    def optimize(self, data: Dict[str, torch.Tensor], camera_opt: BaseCamera,
-                 gravity_opt: Gravity) -> Tuple[BaseCamera, Gravity, Dict[str, torch.Tensor]]:
-        """All LM steps + final costs + uncertainty on the device (reference: lm_optimizer.py:551-644)."""
+    def optimize(self, data: Dict[str, torch.Tensor], camera_opt: BaseCamera, gravity_opt: Gravity,
+                 record: torch.Tensor = None) -> Tuple[BaseCamera, Gravity, Dict[str, torch.Tensor]]:
+        """All LM steps + final costs + uncertainty on the device (reference: lm_optimizer.py:551-644).  `record`: the step
+        record of gclm_solve_recorded, (B, num_steps, _lib.LM_RECORD_STRIDE) float32 (lm_grad.recorded_solve)."""
         up, lat, upc, latc, (B, H, W) = self._fields(data)
         slat = self._sin_lat(data, lat)
         device = lat.device
@@ -358,8 +363,12 @@ class LMOptimizer(nn.Module):
         grav = _call.dev_f32(gravity_opt._data, "gravity").clone()
         info = torch.empty((B, _lib.INFO_STRIDE), dtype=torch.float32, device=device)
         P = _call.ptr
-        _call.call("gclm_solve_ex", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(), grav.data_ptr(),
-                   info.data_ptr(), P(slat), stream, handle=h.ptr)
+        if record is None:
+            _call.call("gclm_solve_ex", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(), grav.data_ptr(),
+                       info.data_ptr(), P(slat), stream, handle=h.ptr)
+        else:
+            _call.call("gclm_solve_recorded", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, cam.data_ptr(), grav.data_ptr(),
+                       info.data_ptr(), record.data_ptr(), stream, handle=h.ptr)
         self._last_raw = (cam, grav, info)     # packed device results (parallel.calibrate_sharded)
         return camera_opt.__class__(cam), _unit_gravity(grav), self._unpack_info(info, up is not None)
 
@@ -389,6 +398,9 @@ class LMOptimizer(nn.Module):
 
     def forward(self, data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """Run the LM optimisation (reference: lm_optimizer.py:646-664)."""
+        if self.conf.differentiable:
+            from . import lm_grad
+            return lm_grad.differentiable_forward(self, data)
         if self.training and not self._warned_training and any(
                 torch.is_tensor(v) and v.requires_grad for v in data.values()):
             # the training-time optimiser of siclib backpropagates through the solve; this path is an opaque C call
@@ -473,11 +485,14 @@ class LMOptimizer(nn.Module):
         info = {k: torch.cat([i[k] for i in infos]) for k in infos[0]}
         return self.camera_model(torch.cat(cams)), _unit_gravity(torch.cat(gravs)), info
 
-    def calibrate_fields(self, data: Dict[str, torch.Tensor]) -> Tuple[BaseCamera, Gravity, Dict[str, torch.Tensor]]:
+    def calibrate_fields(self, data: Dict[str, torch.Tensor],
+                         record: torch.Tensor = None) -> Tuple[BaseCamera, Gravity, Dict[str, torch.Tensor]]:
         """get_trivial_estimation + optimize in ONE C call (gclm_calibrate): the initial estimate is built
-        on the device from (H, W) and the priors, so no host-side tensor op precedes the kernels."""
+        on the device from (H, W) and the priors, so no host-side tensor op precedes the kernels.  `record`: the step
+        record of gclm_calibrate_recorded (lm_grad.recorded_solve; one call, never split or overlapped)."""
         up, lat, upc, latc, (B, H, W) = self._fields(data)
         if B > self._MAX_CALL:
+            assert record is None, "the recorded solve is one call"
             return self._calibrate_chunked(data, B)
         slat = self._sin_lat(data, lat)
         device = lat.device
@@ -504,8 +519,12 @@ class LMOptimizer(nn.Module):
         grav = torch.empty((B, 3), dtype=torch.float32, device=device)
         info = torch.empty((B, _lib.INFO_STRIDE), dtype=torch.float32, device=device)
         P = _call.ptr
-        n_over = self._overlap_parts(B, H, W, h, lambda: all(t is None or t.data_ptr() % 16 == 0 for t in (up, lat, upc, latc)))
-        if n_over > 1:
+        n_over = 1 if record is not None else \
+            self._overlap_parts(B, H, W, h, lambda: all(t is None or t.data_ptr() % 16 == 0 for t in (up, lat, upc, latc)))
+        if record is not None:
+            _call.call("gclm_calibrate_recorded", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg), P(pd), nd,
+                       cam.data_ptr(), grav.data_ptr(), info.data_ptr(), record.data_ptr(), stream, handle=h.ptr)
+        elif n_over > 1:
             self._calibrate_overlapped(n_over, device, (up, lat, upc, latc, slat), (B, H, W), scales, (pf, pg, pd), nd,
                                        (cam, grav, info))
         else:
@@ -616,6 +635,31 @@ class LMOptimizer(nn.Module):
         infos = (C.c_void_p * n)(*[info[bounds[i]:bounds[i + 1]].data_ptr() for i in range(n)])
         sizes = (C.c_int * n)(*[bounds[i + 1] - bounds[i] for i in range(n)])
         _call.call("gclm_merge_stop_at", parts, infos, sizes, n, cur.cuda_stream, handle=handles[0].ptr)
+
+    # ------------------------------------------------------------------ training-time loss and metrics
+    def metrics(self, pred: Dict[str, torch.Tensor], data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The errors of `pred` ("camera", "gravity") against the ground truth `data` ("camera", "gravity"), in degrees (k1_error
+        in the distortion's unit), plus "stop_at" and the initial_* / final_* costs of `pred`
+        (reference: siclib/models/optimization/lm_optimizer.py:577-596)."""
+        from . import metrics as M
+        cam, gt_cam, grav, gt_grav = pred["camera"], data["camera"], pred["gravity"], data["gravity"]
+        out = {"roll_error": M.roll_error(grav, gt_grav), "pitch_error": M.pitch_error(grav, gt_grav),
+               "gravity_error": M.gravity_error(grav, gt_grav), "vfov_error": M.vfov_error(cam, gt_cam),
+               "k1_error": M.dist_error(cam, gt_cam), "stop_at": pred["stop_at"]}
+        out.update({k: v for k, v in pred.items() if "initial" in k or "final" in k})
+        return out
+
+    def loss(self, pred: Dict[str, torch.Tensor], data: Dict[str, torch.Tensor]):
+        """(losses, metrics): L1 losses of the optimised parameters against the ground truth, each (B,) times conf.loss_weight --
+        "gravity" (summed over the vector), "focal" (mean over fx, fy, divided by the image width as the reference divides),
+        "dist" (zeros for a model without distortion) and "param_total", their sum
+        (reference: siclib/models/optimization/lm_optimizer.py:598-625).  Plain torch: differentiable wherever `pred` is."""
+        cam, gt_cam, grav, gt_grav = pred["camera"], data["camera"], pred["gravity"], data["gravity"]
+        gravity = (grav.vec3d - gt_grav.vec3d).abs().sum(-1)
+        focal = (cam.f - gt_cam.f).abs().mean(-1) / gt_cam.size[0, 0]
+        dist = (cam.dist - gt_cam.dist).abs().sum(-1) if self.camera_has_distortion else torch.zeros_like(focal)
+        losses = {"gravity": gravity, "focal": focal, "dist": dist, "param_total": gravity + focal + dist}
+        return {k: v * self.conf.loss_weight for k, v in losses.items()}, self.metrics(pred, data)
 
     # ------------------------------------------------------------------ kernel-level entry (tests, tools)
     def system(self, data: Dict[str, torch.Tensor], camera: BaseCamera, gravity: Gravity,

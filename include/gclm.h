@@ -57,7 +57,10 @@ extern "C" {
  * gclm_param_opt, gclm_param_opt_cost, gclm_param_opt_step, gclm_param_opt_workspace and gclm_default_param_opt_config added, also
  * within 610: Adam on (roll, pitch, vfov) against perspective fields, the reference's third optimiser;
  * gclm_field_loss, gclm_field_loss_grad and gclm_field_loss_workspace added, also within 610: the decoders' training losses
- * against a calibration and their gradients with respect to the predicted fields).  gclm_create refuses a gclm_config whose first two fields do not
+ * against a calibration and their gradients with respect to the predicted fields;
+ * gclm_solve_recorded, gclm_calibrate_recorded, gclm_lm_backward and gclm_lm_backward_workspace added, also within 610: the
+ * solve with a step record, and the adjoint of its LM steps -- the gradients of the optimised camera and gravity with respect
+ * to the fields and the confidences).  gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -222,6 +225,73 @@ int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, con
                       const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
                       int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
                       const float* d_sin_lat, void* stream);
+
+/*
+ * gclm_solve / gclm_calibrate with a step record: d_record is NULL -- the call is gclm_solve_ex / gclm_calibrate_ex with a
+ * NULL d_sin_lat -- or (B, num_steps, GCLM_LM_RECORD_STRIDE) float32 on the device, which the call zeroes and the per-image
+ * update of every LM step that runs fills, one row per step:
+ *   [GCLM_LM_RECORD_CAMERA .. +8)   the camera row the step started from (w h fx fy cx cy k1 k2)
+ *   [GCLM_LM_RECORD_GRAVITY .. +3)  ... and its gravity
+ *   [GCLM_LM_RECORD_LAMBDA]         the damping the step used (the rule of lm_optimizer.py:95-106 applied)
+ *   [GCLM_LM_RECORD_DELTA .. +5)    the solution of the damped normal equations over the full columns (d1, d2, focal, k1, k2):
+ *                                   zero in fixed columns, all zero after a failed Cholesky
+ *   [GCLM_LM_RECORD_FAILED]         1 if the Cholesky failed (the step is the zero step), else 0
+ *   [GCLM_LM_RECORD_EXECUTED]       1
+ *   [GCLM_LM_RECORD_SYSTEM .. +24)  the reduced accumulator record of the step's sweep: sum cost up, sum cost latitude, J^T W r
+ *                                   over the PM = 4 (radial: 5) full columns, the upper triangle of J^T W J row-major
+ * With early_stop the update at which the stop fires (step stop_at) still leaves its row: the state it computed is discarded, so
+ * the rows of a solve are [0, stop_at) then; rows after it stay zero.  The record holds values the update computes anyway:
+ * results equal those of the call without a record bit for bit (a call that would take one launch per LM step takes the
+ * two-launch sequence, its twin bit for bit).  Per-image solves only: -3 with shared_intrinsics.
+ */
+#define GCLM_LM_RECORD_STRIDE 48
+#define GCLM_LM_RECORD_CAMERA 0
+#define GCLM_LM_RECORD_GRAVITY 8
+#define GCLM_LM_RECORD_LAMBDA 11
+#define GCLM_LM_RECORD_DELTA 12
+#define GCLM_LM_RECORD_FAILED 17
+#define GCLM_LM_RECORD_EXECUTED 18
+#define GCLM_LM_RECORD_SYSTEM 24
+int gclm_solve_recorded(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                        const float* d_lat_conf, int B, int H, int W, float* d_cam_io, float* d_grav_io,
+                        float* d_info_out, float* d_record, void* stream);
+int gclm_calibrate_recorded(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                            const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                            const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                            int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
+                            float* d_record, void* stream);
+
+/*
+ * gclm_lm_backward: the adjoint of the LM steps of a recorded solve (no handle).  Given the gradients of a scalar with respect
+ * to the solve's outputs, d_grad_cam (B, 8) (columns fx, fy, k1, k2 are read; the size and the principal point are constants
+ * of the solve) and d_grad_grav (B, 3), it writes the gradients with respect to the inputs whose plane is given: d_grad_up
+ * (B, 2, H, W), d_grad_lat (B, 1, H, W), d_grad_up_conf and d_grad_lat_conf (B, H, W).  A NULL plane is neither computed nor
+ * written; a plane whose input is absent must be NULL.  No gradient flows through the damping (it depends on the costs
+ * through a comparison), the initial estimate or the priors.
+ *
+ * One step at state theta with the step delta = A^-1 G, A = H + diag(clamp(lambda H_jj, 1e-6)), theta+ = theta [+] delta
+ * (lm_optimizer.py:109-137, 518-549).  With the incoming adjoint of theta+: a per-image kernel takes the adjoint of [+]
+ * (Householder plus on the sphere, exp(log f + delta_f) with fx following fy, the clamped distortion) in forward mode,
+ * solves v = A^-1 delta-bar from the recorded system and forms the mask m_j = [lambda H_jj > 1e-6]; a pass over the planes
+ * evaluates, per pixel in registers,
+ *   phi = w [ (J v) . r - (J v) . (J delta) - lambda sum_j m_j v_j delta_j |J_j|^2 ]        (per field; v, delta, m frozen)
+ * with its derivatives with respect to the pixel's inputs (added into the gradient planes: the first processed step stores,
+ * later ones accumulate) and to theta (one float64 record per tile, summed per image by a finish kernel, no atomics).  J is
+ * the forward-mode derivative of the fields at theta [+] delta', delta' = 0, and its derivative with respect to theta a second
+ * forward-mode level over the same scalar-templated field formulas.  Steps run from the last executed one down to step 0:
+ * num_steps of them, or, with early_stop != 0, the first stop_at that d_info (the solve's info rows) names.
+ *
+ * camera_model: GCLM_PINHOLE or GCLM_SIMPLE_RADIAL (-3 otherwise); spherical manifold and log focal length.  up_scale /
+ * lat_scale: the Huber scales of the solve (2^20 for the squared loss).  estimate_*: the solve's free-parameter flags.
+ * d_workspace: at least gclm_lm_backward_workspace(B, H, W) bytes (0: sizes out of range), 8-byte aligned.  Returns -3 for
+ * NULL or misaligned pointers, overlapping outputs, num_steps outside 1..GCLM_MAX_STEPS and sizes out of range.
+ */
+size_t gclm_lm_backward_workspace(int B, int H, int W);
+int gclm_lm_backward(int camera_model, const float* d_up, const float* d_lat, const float* d_up_conf, const float* d_lat_conf,
+                     int B, int H, int W, const float* d_record, int num_steps, int early_stop, const float* d_info,
+                     float up_scale, float lat_scale, int estimate_gravity, int estimate_focal, int estimate_dist,
+                     const float* d_grad_cam, const float* d_grad_grav, float* d_grad_up, float* d_grad_lat,
+                     float* d_grad_up_conf, float* d_grad_lat_conf, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
  * One fused sweep at fixed parameters: calculate_residuals + calculate_costs + setup_system

@@ -1,0 +1,220 @@
+"""Writes tests/golden/lm_grad_reference.npz: what autograd makes of the reference's LM optimiser
+(geocalib/lm_optimizer.py, in train() mode) on recorded inputs.  Data only.
+
+Per case: float32 fields and confidences, the fixed weights of
+    L = sum w_c[:, 2:4] * f / height + sum w_g * gravity + sum w_c[:, 6] * k1,
+the reference's float64 gradients of L with respect to the four inputs (inputs cast to float64), its own float32 gradients of
+the same L, the up/down decision of the damping rule at every step (both precisions), and the final camera and gravity of
+both runs.  optimize() is called with the initial estimate cast to the run's dtype (get_trivial_estimation rounds to float32).
+
+Cases (noise 0.03 on both fields, 5 % latitude outliers of 0.4 rad, confidences in 0.05 .. 0.95):
+    c1  B = 3, 12 x 20,  5 steps                         c2  B = 2, 13 x 19, 10 steps (lambda reaches its 1e-6 floor)
+each for {pinhole, simple_radial} x {huber at scale 1e-2, squared (scale 2^20)}; and at 12 x 20, pinhole, huber, 5 steps:
+    prior_focal, prior_gravity, lat_only (no up field, with the latitude confidence), noconf (no confidences).
+
+Asserted here (a case that misses one is replaced by the same case with fewer steps, down to 3, then by
+the next seed, from 11 on; both are recorded): the damping decisions agree between float32 and float64 at every step; no Cholesky failure; the focal and
+distortion clamps are inactive; every lambda H_jj stays 1e-3 (relative) away from the 1e-6 clamp.
+
+Also recorded: siclib's LMOptimizer.loss / .metrics (siclib/models/optimization/lm_optimizer.py:577-625) of c1's float32
+results against the ground truth the fields were rendered from, for loss_weight 1 and 0.5.
+
+Runs where a checkout of the reference is available (oracle/ref_import.py says where); the tests that read the file do not
+need one.
+
+    python tests/golden/make_golden_lm_grad.py
+"""
+import importlib
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+from oracle import ref_import  # noqa: E402
+
+SEED = 11
+HUBER, SQUARED = 1e-2, float(2 ** 20)
+KEYS = ("up_field", "latitude_field", "up_confidence", "latitude_confidence")
+
+
+def cases():
+    out = []
+    for model in ("pinhole", "simple_radial"):
+        for loss, scale in (("huber", HUBER), ("squared", SQUARED)):
+            out.append((f"c1/{model}/{loss}", dict(model=model, scale=scale, B=3, H=12, W=20, steps=5)))
+            out.append((f"c2/{model}/{loss}", dict(model=model, scale=scale, B=2, H=13, W=19, steps=10)))
+    base = dict(model="pinhole", scale=HUBER, B=3, H=12, W=20, steps=5)
+    for extra in ("prior_focal", "prior_gravity", "lat_only", "noconf"):
+        out.append((f"{extra}/pinhole/huber", dict(base, extra=extra)))
+    return out
+
+
+def make(ns, model, B, H, W, extra=None, seed=SEED, **_):
+    """float64 inputs and the ground truth they were rendered from (the measurement probe's recipe)."""
+    g = torch.Generator().manual_seed(seed)
+    roll = (torch.rand(B, generator=g) - .5) * 0.6
+    pitch = (torch.rand(B, generator=g) - .5) * 0.6
+    vfov = 0.7 + 0.6 * torch.rand(B, generator=g)
+    d = {"width": torch.full((B,), float(W)), "height": torch.full((B,), float(H)), "vfov": vfov}
+    if model != "pinhole":
+        d["k1"] = (torch.rand(B, generator=g) - .5) * 0.2
+    cam = ns.camera.camera_models[model].from_dict(d).double()
+    grav = ns.gravity.Gravity.from_rp(roll, pitch).double()
+    up, lat = ns.perspective_fields.get_perspective_field(cam, grav)
+    up = up + 0.03 * torch.randn(up.shape, generator=g, dtype=torch.float64)
+    lat = lat + 0.03 * torch.randn(lat.shape, generator=g, dtype=torch.float64)
+    lat = lat + (torch.rand(B, H, W, generator=g) < 0.05)[:, None] * 0.4
+    upc = 0.05 + 0.9 * torch.rand(B, H, W, generator=g, dtype=torch.float64)
+    latc = 0.05 + 0.9 * torch.rand(B, H, W, generator=g, dtype=torch.float64)
+    data = dict(up_field=up, latitude_field=lat, up_confidence=upc, latitude_confidence=latc)
+    data = {k: v.float() for k, v in data.items()}
+    priors = {}
+    if extra == "prior_focal":
+        priors["prior_focal"] = (cam.f[:, 1] * 1.05).float()
+    if extra == "prior_gravity":
+        priors["prior_gravity"] = ns.gravity.Gravity.from_rp(roll + 0.02, pitch - 0.02).vec3d.float()
+    if extra == "lat_only":
+        del data["up_field"], data["up_confidence"]
+    if extra == "noconf":
+        del data["up_confidence"], data["latitude_confidence"]
+    return data, priors, cam, grav
+
+
+def weights(B, dtype):
+    return (torch.linspace(0.5, 1.5, 8 * B, dtype=dtype).reshape(B, 8), torch.linspace(-1, 1, 3 * B, dtype=dtype).reshape(B, 3))
+
+
+def run(ns, name, model, data, priors, dtype, steps, scale):
+    lmmod = ns.lm_optimizer
+    opt = lmmod.LMOptimizer({"camera_model": model, "num_steps": steps, "early_stop": False, "up_loss_fn_scale": scale,
+                             "lat_loss_fn_scale": scale})
+    opt.train()
+    leaves = {k: v.to(dtype).clone().requires_grad_(True) for k, v in data.items()}
+    full = {**leaves, **{k: v.to(dtype) for k, v in priors.items()}}
+    cam0, g0 = lmmod.get_trivial_estimation(full, opt.camera_model)
+    cam0, g0 = cam0.to(dtype), g0.to(dtype)
+    opt.setup_optimization_and_priors(full, shared_intrinsics=False)
+    decisions, margins = [], []
+    orig_lambda, orig_step, orig_update = lmmod.update_lambda, lmmod.optimizer_step, opt.update_estimate
+
+    def rec_lambda(lamb, prev, new, *a, **k):
+        decisions.append((new > prev).detach().clone())
+        return orig_lambda(lamb, prev, new, *a, **k)
+
+    def rec_step(G, H, lamb, *a, **k):
+        damp = (H.diagonal(dim1=-2, dim2=-1) * lamb.unsqueeze(-1)).detach().double()
+        margins.append(((damp - 1e-6).abs() / 1e-6).min().item())
+        delta = orig_step(G, H, lamb, *a, **k)
+        assert bool((delta.detach().abs().sum(-1) > 0).all()), f"{name}: Cholesky failure (zero step)"
+        return delta
+
+    def rec_update(camera, gravity, delta):
+        c, g = orig_update(camera, gravity, delta)
+        h = c.size[..., 1].detach().double()
+        fy = c.f[..., 1].detach().double()
+        lo, hi = h / 2 / np.tan(np.deg2rad(150) / 2), h / 2 / np.tan(np.deg2rad(5) / 2)
+        assert bool(((fy > lo * 1.001) & (fy < hi * 0.999)).all()), f"{name}: focal clamp active"
+        if hasattr(c, "dist"):
+            assert bool((c.dist.detach().abs() < 0.699).all()), f"{name}: distortion clamp active"
+        return c, g
+
+    lmmod.update_lambda, lmmod.optimizer_step, opt.update_estimate = rec_lambda, rec_step, rec_update
+    try:
+        cam, grav, info = opt.optimize(full, cam0, g0)
+    finally:
+        lmmod.update_lambda, lmmod.optimizer_step = orig_lambda, orig_step
+    B = cam.shape[0]
+    wc, wg = weights(B, dtype)
+    loss = (cam._data[:, 2:4] / cam._data[:, 1:2] * wc[:, 2:4]).sum() + (grav._data * wg).sum()
+    if cam._data.shape[-1] > 6:
+        loss = loss + (cam._data[:, 6] * wc[:, 6]).sum()
+    grads = torch.autograd.grad(loss, list(leaves.values()))
+    assert min(margins) >= 1e-3, f"{name}: lambda H_jj within {min(margins):.2e} (relative) of the 1e-6 clamp"
+    cam8 = torch.cat([cam._data.detach(), cam._data.new_zeros(B, 8 - cam._data.shape[-1])], -1)
+    return (dict(zip(leaves, (g.detach() for g in grads))), torch.stack(decisions), cam8, grav._data.detach(), loss.detach(),
+            (cam, grav, info))
+
+
+def siclib_loss():
+    ref_import.load()
+    for name in ("omegaconf", "h5py", "hydra", "hydra.utils", "albumentations", "albumentations.pytorch",
+                 "albumentations.pytorch.transforms", "matplotlib", "matplotlib.pyplot"):
+        if name not in sys.modules:
+            try:
+                importlib.import_module(name)
+            except Exception:
+                sys.modules[name] = ref_import._Anything(name)
+    mod = importlib.import_module("siclib.models.optimization.lm_optimizer")
+    return mod.LMOptimizer
+
+
+def main():
+    ns = ref_import.load()
+    rec = {}
+    kept = {}
+    for name, cfg in cases():
+        # a case that misses a condition is replaced: by the same case with fewer steps (never fewer than 3;
+        # a converged float32 solve compares costs that differ by rounding alone), then by
+        # the next seed
+        tries = [(seed, steps) for seed in range(SEED, SEED + 4) for steps in range(cfg["steps"], min(cfg["steps"], 3) - 1, -1)]
+        for seed, steps in tries:
+            try:
+                cfg = dict(cfg, steps=steps)
+                data, priors, gt_cam, gt_grav = make(ns, seed=seed, **cfg)
+                args = (cfg["model"], data, priors)
+                g64, d64, c64, gr64, l64, _ = run(ns, name, *args, torch.float64, cfg["steps"], cfg["scale"])
+                g32, d32, c32, gr32, l32, res32 = run(ns, name, *args, torch.float32, cfg["steps"], cfg["scale"])
+                assert bool((d64 == d32).all()), f"{name}: damping decisions differ between float32 and float64"
+                break
+            except AssertionError as e:
+                print(f"seed {seed}, {steps} steps replaced: {e}")
+        else:
+            raise SystemExit(f"{name}: no seed met the conditions")
+        rec[f"{name}/seed"] = np.array(seed)
+        for k, v in {**data, **priors}.items():
+            rec[f"{name}/in/{k}"] = v.numpy()
+        wc, wg = weights(cfg["B"], torch.float64)
+        rec[f"{name}/w_cam"], rec[f"{name}/w_grav"] = wc.numpy(), wg.numpy()
+        rec[f"{name}/cfg"] = np.array([cfg["steps"], cfg["scale"]], np.float64)
+        for k in g64:
+            rec[f"{name}/grad64/{k}"] = g64[k].numpy()
+            rec[f"{name}/grad32/{k}"] = g32[k].numpy()
+            a, b = g64[k], g32[k].double()
+            dims = tuple(range(1, a.dim()))
+            err = (a - b).abs().amax(dim=dims) / a.abs().amax(dim=dims)
+            print(f"{name:32s} {k:20s} |g64|max {a.abs().amax(dim=dims).min():.2e}..{a.abs().amax(dim=dims).max():.2e} "
+                  f"f32 rel err {err.min():.2e}..{err.max():.2e}")
+        rec[f"{name}/decisions"] = d64.numpy()
+        rec[f"{name}/camera64"], rec[f"{name}/gravity64"] = c64.numpy(), gr64.numpy()
+        rec[f"{name}/camera32"], rec[f"{name}/gravity32"] = c32.numpy(), gr32.numpy()
+        rec[f"{name}/L64"] = l64.numpy()
+        rec[f"{name}/gt_camera"] = torch.cat([gt_cam._data, gt_cam._data.new_zeros(cfg["B"], 8 - gt_cam._data.shape[-1])], -1).numpy()
+        rec[f"{name}/gt_gravity"] = gt_grav._data.numpy()
+        kept[name] = (res32, gt_cam, gt_grav)
+    # siclib's loss / metrics of the float32 results of the two c1 huber cases
+    LM = siclib_loss()
+    for name in ("c1/pinhole/huber", "c1/simple_radial/huber"):
+        (cam, grav, info), gt_cam, gt_grav = kept[name]
+        pred = {"camera": cam.detach(), "gravity": grav.detach(), **{k: (v.detach() if torch.is_tensor(v) else v) for k, v in info.items()}}
+        gt = {"camera": gt_cam.float(), "gravity": gt_grav.float()}
+        for lw in (1.0, 0.5):
+            me = types.SimpleNamespace(conf=types.SimpleNamespace(loss_weight=lw), camera_has_distortion=hasattr(cam, "dist"))
+            me.metrics = types.MethodType(LM.metrics, me)
+            losses, metrics = LM.loss(me, pred, gt)
+            for k, v in losses.items():
+                rec[f"{name}/loss{lw}/{k}"] = v.detach().numpy()
+            for k, v in metrics.items():
+                rec[f"{name}/metrics/{k}"] = (v.detach() if torch.is_tensor(v) else torch.as_tensor(v)).numpy()
+    out = os.path.join(HERE, "lm_grad_reference.npz")
+    np.savez_compressed(out, **rec)
+    print(out, os.path.getsize(out), "bytes,", len(rec), "arrays")
+
+
+if __name__ == "__main__":
+    main()
