@@ -16,14 +16,11 @@
 // scale[b, field] * dl/dp_c, times conf where given; the caller forms scale = grad_output * weight / denominator from the
 // forward's d_out.  Nothing but the inputs lives between the two calls: the gradient call evaluates the target again.
 //
-// Forward: the layout of gclm_metrics.hip -- the tile geometry of gclm_render.h, a lane sums its PX pixels in float32, a wave
-// its lanes by a butterfly, lane 0 of each wave leaves four sums in LDS and after one barrier the block writes one record
-// per tile: sum l_up (x c_up), sum c_up, sum l_lat (x c_lat), sum c_lat.  field_loss_finish_kernel (grid = B) sums each
-// image's records in float64 in a fixed order (eight strided chains, combined in order).  No atomics: the bits of an image's
-// losses depend on that image's pixels, H, W and the pixels per lane alone.
+// Forward: the tile walk of gclm_render.h ("The tile walk"), with a record of four float sums per tile: sum l_up (x c_up),
+// sum c_up, sum l_lat (x c_lat), sum c_lat; field_loss_finish_kernel (grid = B) sums them in eight chains.
 // Gradient: the same walk with no reduction, no LDS, no barrier; plain stores (the planes are read next, by autograd).
 // The loss type is a kernel argument taken by a branch every lane of the grid takes alike, not a template parameter:
-// camera model x PX instantiations per kernel.  Pixels per lane as gclm_metrics.hip has them.  64-bit offsets.  No scratch.
+// camera model x PX instantiations per kernel.  Pixels per lane by gclm_render.h's pixels_per_lane.  64-bit offsets.  No scratch.
 #include "gclm_render.h"
 
 namespace gclm {
@@ -112,37 +109,12 @@ __device__ __forceinline__ void pixel_grad(int type, const float (&r)[C], const 
 #define GCLM_FIELD_LOSS_NT_STORES 0
 #endif
 
-template <int PX>
-__device__ __forceinline__ void store_grad_px(const float (&v)[PX], float* p) {
-    if constexpr (GCLM_FIELD_LOSS_NT_STORES) {
-        if constexpr (PX == 1) {
-            store_nt(v[0], p);
-        } else if constexpr (PX == 2) {
-            store_nt(f32x2{v[0], v[1]}, reinterpret_cast<f32x2*>(p));
-        } else {
-            store_nt(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
-        }
-    } else if constexpr (PX == 1) {
-        *p = v[0];
-    } else if constexpr (PX == 2) {
-        *reinterpret_cast<f32x2*>(p) = f32x2{v[0], v[1]};
-    } else {
-        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-    }
-}
+constexpr bool kGradNT = GCLM_FIELD_LOSS_NT_STORES != 0;
 
-// The per-image and per-row terms of this lane's pixels (x, y), and u, r2 of each of them.
+// The row's terms of this lane's pixels (x, y), and u, r2 of each of them.
 template <int PX>
 __device__ __forceinline__ PerspRow lane_row(const float* cam, const float* grav, int b, int x, int y, float (&u)[PX], float (&r2)[PX]) {
-    const float* cb = cam + (size_t)b * 8;
-    const float* gb = grav + (size_t)b * 3;
-    PerspRow r;
-    r.ifx = 1.f / cb[2];
-    r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
-    r.a = gb[0], r.b = gb[1], r.c = gb[2];
-    r.v = ((float)y - cb[5]) * (1.f / cb[3]);
-    r.v2 = r.v * r.v;
-    r.py = r.b - r.c * r.v;
+    const PerspRow r = persp_row(cam + (size_t)b * 8, grav + (size_t)b * 3, y);
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
         u[j] = ((float)(x + j) - r.cx) * r.ifx;
@@ -161,7 +133,6 @@ __global__ __launch_bounds__(kBlock) void field_loss_kernel(const FieldLossArgs 
     if (in) {
         float u[PX], r2[PX];
         const PerspRow r = lane_row<PX>(a.cam, a.grav, b, x, y, u, r2);
-        // PX > 1 runs only where W % PX == 0: x is a multiple of PX, so x + PX <= W
         const size_t hw = (size_t)a.H * a.W, o = (size_t)b * hw + (size_t)y * a.W + x;
         if (a.up) {
             float px[PX], py[PX], l[PX];
@@ -205,17 +176,7 @@ __global__ __launch_bounds__(kBlock) void field_loss_kernel(const FieldLossArgs 
     // every lane of the block from here on: wave sums, one record per wave in LDS, one per tile in the workspace
 #pragma unroll
     for (int k = 0; k < kLossWords; ++k) sum[k] = wave_sum(sum[k]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kLossWords; ++k) s_sum[wave][k] = sum[k];
-    }
-    __syncthreads();
-    const int k = threadIdx.x;
-    if (k < kLossWords) {
-        float s = s_sum[0][k];
-        for (int i = 1; i < kTileRows; ++i) s += s_sum[i][k];
-        a.rec[((size_t)b * gridDim.x + blockIdx.x) * kLossWords + k] = s;
-    }
+    tile_record(s_sum, wave, sum, [&](int k, float s) { a.rec[((size_t)b * gridDim.x + blockIdx.x) * kLossWords + k] = s; });
 }
 
 // One block per image: word k of the image's records is summed by kLossChains chains (record t goes to chain
@@ -226,16 +187,12 @@ __global__ __launch_bounds__(kBlock) void field_loss_finish_kernel(const float* 
     __shared__ double part[kLossChains][kLossWords];
     const int b = blockIdx.x, k = threadIdx.x & 31, chain = threadIdx.x >> 5;
     if (k < kLossWords) {
-        double acc = 0.0;
-        const float* p = rec + (size_t)b * tiles * kLossWords + k;
-        for (int t = chain; t < tiles; t += kLossChains) acc += (double)p[(size_t)t * kLossWords];
-        part[chain][k] = acc;
+        part[chain][k] = chain_sum<kLossChains>(rec + (size_t)b * tiles * kLossWords + k, kLossWords, tiles, chain);
     }
     __syncthreads();
     const int field = threadIdx.x;
     if (field < 2) {
-        double num = part[0][2 * field], den = part[0][2 * field + 1];
-        for (int i = 1; i < kLossChains; ++i) num += part[i][2 * field], den += part[i][2 * field + 1];
+        double num = column_sum(part, 2 * field), den = column_sum(part, 2 * field + 1);
         const bool has = field ? has_lat != 0 : has_up != 0, hasc = field ? has_latc != 0 : has_upc != 0;
         if (!hasc) den = (double)hw;
         out[(size_t)b * 4 + field] = has ? (float)(num / den) : __builtin_nanf("");
@@ -270,8 +227,8 @@ __global__ __launch_bounds__(kBlock) void field_loss_grad_kernel(const FieldLoss
 #pragma unroll
             for (int j = 0; j < PX; ++j) gx[j] *= c[j], gy[j] *= c[j];
         }
-        store_grad_px<PX>(gx, a.grad_up + o + (size_t)b * hw);
-        store_grad_px<PX>(gy, a.grad_up + o + (size_t)b * hw + hw);
+        store_px<PX, kGradNT>(gx, a.grad_up + o + (size_t)b * hw);
+        store_px<PX, kGradNT>(gy, a.grad_up + o + (size_t)b * hw + hw);
     }
     if (a.lat) {
         const float scale = a.scale[(size_t)b * 2 + 1];
@@ -290,24 +247,14 @@ __global__ __launch_bounds__(kBlock) void field_loss_grad_kernel(const FieldLoss
 #pragma unroll
             for (int j = 0; j < PX; ++j) gl[j] *= c[j];
         }
-        store_grad_px<PX>(gl, a.grad_lat + o);
+        store_px<PX, kGradNT>(gl, a.grad_lat + o);
     }
-}
-
-// pixels per lane of a call (gclm_metrics.hip's rule, over the planes of this call)
-int pixels_per_lane(int W, std::initializer_list<const float*> planes) {
-    uintptr_t bits = 0;
-    for (const float* p : planes) bits |= reinterpret_cast<uintptr_t>(p);
-    if (W % 4 == 0 && bits % 16 == 0) return 4;
-    return W % 2 == 0 && bits % 8 == 0 ? 2 : 1;
 }
 
 }  // namespace
 
 size_t field_loss_workspace(int B, int H, int W) {
-    if (B < 1 || B > kMaxCallImages || H < 1 || W < 1 || !tile_grid_fits(H, W)) return 0;
-    // sized for one pixel per lane, the path with the most tiles
-    return (size_t)B * tile_count(H, W, 1) * kLossWords * sizeof(float);
+    return call_sizes_fit(B, H, W) ? tile_record_bytes(B, H, W, kLossWords, sizeof(float)) : 0;
 }
 
 hipError_t launch_field_loss(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
@@ -318,7 +265,7 @@ hipError_t launch_field_loss(int camera_model, const float* cam, const float* gr
     const int tiles = tile_count(H, W, px);
     return with_camera_model(camera_model, [&](auto m) {
         constexpr int M = decltype(m)::value;
-        auto kernel = px == 4 ? field_loss_kernel<M, 4> : px == 2 ? field_loss_kernel<M, 2> : field_loss_kernel<M, 1>;
+        const auto kernel = with_pixels_per_lane(px, [](auto p) { return field_loss_kernel<M, decltype(p)::value>; });
         hipLaunchKernelGGL(kernel, dim3(tiles, B), dim3(kBlock), 0, st, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -335,7 +282,7 @@ hipError_t launch_field_loss_grad(int camera_model, const float* cam, const floa
     const FieldLossGradArgs a{cam, grav, up, lat, upc, latc, scale, grad_up, grad_lat, H, W, tile_columns(W, px), up_loss, lat_loss};
     return with_camera_model(camera_model, [&](auto m) {
         constexpr int M = decltype(m)::value;
-        auto kernel = px == 4 ? field_loss_grad_kernel<M, 4> : px == 2 ? field_loss_grad_kernel<M, 2> : field_loss_grad_kernel<M, 1>;
+        const auto kernel = with_pixels_per_lane(px, [](auto p) { return field_loss_grad_kernel<M, decltype(p)::value>; });
         hipLaunchKernelGGL(kernel, dim3(tile_count(H, W, px), B), dim3(kBlock), 0, st, a);
         return hipGetLastError();
     });

@@ -12,8 +12,8 @@
 // gravity scores 0), a NaN confidence makes the sums of that field of that image NaN for every hypothesis (an infinite one
 // gives NaN wherever a hypothesis misses that pixel, 0 * inf).  A NULL confidence and a NULL mask count as 1.
 //
-// Layout: the tile geometry of gclm_render.h and the pixels-per-lane rule of gclm_metrics.hip -- a wave walks 64 PX adjacent
-// pixels of a row, 4 waves cover 4 rows -- with grid = (tiles of one image, chunks of K hypotheses, B).  A block
+// Layout: the tile walk of gclm_render.h ("The tile walk": tile geometry, pixels per lane, wave sum, chain sum) -- a wave
+// walks 64 PX adjacent pixels of a row, 4 waves cover 4 rows -- with grid = (tiles of one image, chunks of K hypotheses, B).  A block
 // loads its pixels ONCE (prediction, confidence x mask: 5 PX registers), then walks its chunk: the eleven numbers of a
 // hypothesis are wave-uniform and come through scalar loads (the index is built from blockIdx and the loop counter alone),
 // the per-hypothesis terms (1 / fx, 1 / fy) and per-row terms (PerspRow's v, v^2, p_y) are formed once per hypothesis, before the
@@ -87,15 +87,8 @@ __global__ __launch_bounds__(kBlock) void hypothesis_kernel(const HypArgs a) {
     }
     const int n0 = chunk * K, nk = a.N - n0 < K ? a.N - n0 : K;          // 1 <= nk: the grid holds no empty chunk
     for (int k = 0; k < nk; ++k) {
-        const float* cb = a.cam + ((size_t)b * a.N + (n0 + k)) * 8;      // wave-uniform addresses: scalar loads
-        const float* gb = a.grav + ((size_t)b * a.N + (n0 + k)) * 3;
-        PerspRow r;
-        r.ifx = 1.f / cb[2];
-        r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
-        r.a = gb[0], r.b = gb[1], r.c = gb[2];
-        r.v = ((float)y - cb[5]) * (1.f / cb[3]);
-        r.v2 = r.v * r.v;
-        r.py = r.b - r.c * r.v;
+        // wave-uniform addresses: scalar loads
+        const PerspRow r = persp_row(a.cam + ((size_t)b * a.N + (n0 + k)) * 8, a.grav + ((size_t)b * a.N + (n0 + k)) * 3, y);
         float su = 0.f, sl = 0.f;
 #pragma unroll
         for (int j = 0; j < PX; ++j) {
@@ -116,10 +109,7 @@ __global__ __launch_bounds__(kBlock) void hypothesis_kernel(const HypArgs a) {
     const int w = threadIdx.x;
     if (w < 2 * K) {
         float s = 0.f;                            // (the places of a last, short chunk beyond N: written, never read)
-        if (w < 2 * nk) {
-            s = s_part[0][w];
-            for (int i = 1; i < kTileRows; ++i) s += s_part[i][w];
-        }
+        if (w < 2 * nk) s = column_sum(s_part, w);
         a.rec[(((size_t)b * gridDim.y + chunk) * gridDim.x + blockIdx.x) * (2 * K) + w] = s;
     }
 }
@@ -147,19 +137,12 @@ __global__ __launch_bounds__(kFinishBlock) void hypothesis_finish_kernel(const f
     for (int c0 = 0; c0 < chunks; c0 += kFinishChunks) {
         const int c = c0 + cl, n = c * K + k;
         const bool live = c < chunks && n < N;
-        double au = 0.0, al = 0.0;
-        if (live) {
-            const float* p = rec + ((size_t)b * chunks + c) * tiles * (2 * K) + 2 * k;
-            for (int t = chain; t < tiles; t += kChains) {
-                const float* w = p + (size_t)t * (2 * K);       // (the workspace is held to 4-byte alignment only)
-                au += (double)w[0], al += (double)w[1];
-            }
-        }
-        part[cl][chain][2 * k] = au, part[cl][chain][2 * k + 1] = al;
+        double acc[2] = {0.0, 0.0};                   // up, latitude (the workspace is held to 4-byte alignment only)
+        if (live) chain_sum<kChains, 2>(rec + ((size_t)b * chunks + c) * tiles * (2 * K) + 2 * k, 2 * K, tiles, chain, acc);
+        part[cl][chain][2 * k] = acc[0], part[cl][chain][2 * k + 1] = acc[1];
         __syncthreads();
         if (live && chain == 0) {
-            double su = part[cl][0][2 * k], sl = part[cl][0][2 * k + 1];
-            for (int i = 1; i < kChains; ++i) su += part[cl][i][2 * k], sl += part[cl][i][2 * k + 1];
+            const double su = column_sum(part[cl], 2 * k), sl = column_sum(part[cl], 2 * k + 1);
             const float total = (float)((double)up_weight * su + (double)lat_weight * sl);
             float* s = scores + ((size_t)b * N + n) * 3;
             s[0] = (float)su, s[1] = (float)sl, s[2] = total;
@@ -183,34 +166,25 @@ __global__ __launch_bounds__(kFinishBlock) void hypothesis_finish_kernel(const f
     }
 }
 
-// pixels per lane of a call: the rule of gclm_metrics.hip over the planes of this one
-int pixels_per_lane(int W, const float* up, const float* lat, const float* upc, const float* latc, const float* mask) {
-    uintptr_t bits = 0;
-    for (const float* p : {up, lat, upc, latc, mask}) bits |= reinterpret_cast<uintptr_t>(p);
-    if (W % 4 == 0 && bits % 16 == 0) return 4;
-    return W % 2 == 0 && bits % 8 == 0 ? 2 : 1;
-}
-
 int chunk_count(int N) { return (N + K - 1) / K; }
 
 }  // namespace
 
 size_t hypothesis_scores_workspace(int B, int N, int H, int W) {
-    if (B < 1 || B > kMaxCallImages || N < 1 || N > kMaxCallImages || H < 1 || W < 1 || !tile_grid_fits(H, W)) return 0;
-    // sized for one pixel per lane, the path with the most tiles
-    return (size_t)B * chunk_count(N) * tile_count(H, W, 1) * (2 * K) * sizeof(float);
+    if (!call_sizes_fit(B, H, W) || N < 1 || N > kMaxCallImages) return 0;
+    return tile_record_bytes((size_t)B * chunk_count(N), H, W, 2 * K, sizeof(float));
 }
 
 hipError_t launch_hypothesis_scores(int camera_model, const float* cam, const float* grav, int B, int N, int H, int W,
                                     const float* up, const float* lat, const float* upc, const float* latc, const float* mask,
                                     float up_threshold, float lat_threshold, float up_weight, float lat_weight, void* workspace,
                                     float* scores, int* best, hipStream_t st) {
-    const int px = pixels_per_lane(W, up, lat, upc, latc, mask), tiles = tile_count(H, W, px), chunks = chunk_count(N);
+    const int px = pixels_per_lane(W, {up, lat, upc, latc, mask}), tiles = tile_count(H, W, px), chunks = chunk_count(N);
     const HypArgs a{cam, grav, up, lat, upc, latc, mask, static_cast<float*>(workspace), N, H, W, tile_columns(W, px),
                     up_threshold, lat_threshold};
     return with_camera_model(camera_model, [&](auto m) {
         constexpr int M = decltype(m)::value;
-        auto kernel = px == 4 ? hypothesis_kernel<M, 4> : px == 2 ? hypothesis_kernel<M, 2> : hypothesis_kernel<M, 1>;
+        const auto kernel = with_pixels_per_lane(px, [](auto p) { return hypothesis_kernel<M, decltype(p)::value>; });
         hipLaunchKernelGGL(kernel, dim3(tiles, chunks, B), dim3(kBlock), 0, st, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

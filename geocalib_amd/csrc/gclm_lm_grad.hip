@@ -11,12 +11,12 @@
 //                            1 / fx, 1 / fy, k1 at theta [+] delta', delta' = 0 -- as Dual<Dual<double, 1>, P>, stored as
 //                            floats: the inner level over the P columns of delta' (the Jacobian), the outer over ONE state
 //                            component, one set per component.
-//   lm_grad_pixel_kernel     the walk of gclm_field_loss.hip (tile_pixel, one block row per image, ragged tiles masked).  A lane
+//   lm_grad_pixel_kernel     the tile walk of gclm_render.h at one pixel per lane (ragged tiles masked), in float64.  A lane
 //                            evaluates the up field and sin(latitude) of its pixel in jet arithmetic from the parameter jets:
 //                            value, Jacobian columns and their derivative with respect to the state component of the pass, for
 //                            each component in turn (the jets are block-uniform loads), so that a pass holds 2 (1 + P) floats
 //                            per quantity, not (1 + 5)(1 + P).  phi's derivative with respect to the component is summed per
-//                            lane, wave (butterfly), block (LDS) in float64 into one record per tile; the first pass also forms the
+//                            lane, wave (wave_sum's butterfly, written out on doubles), block (tile_record) into one record per tile; the first pass also forms the
 //                            derivatives with respect to the pixel's own inputs and stores them, or adds them to the plane
 //                            (the first processed step stores: no memset).  No atomics.
 //   lm_grad_finish_kernel    one block per image: the tile records summed in float64 in a fixed order, plus the direct term.
@@ -313,6 +313,7 @@ __global__ __launch_bounds__(64) void lm_grad_prepare_kernel(const GradCall a, i
     }
     bool ok = !failed;
 #pragma unroll
+    // (not dev::chol_solve on doubles: gclm_device.h switches contraction off, this file has it on -- other float64 roundings)
     for (int j = 0; j < 4; ++j) {                // in-place Cholesky solve (gclm_device.h: chol_solve), in float64
         double t = A[j][j];
 #pragma unroll
@@ -536,22 +537,11 @@ __global__ __launch_bounds__(kBlock) void lm_grad_pixel_kernel(const GradCall a,
         }
         double t = in ? (double)phi.d[0] : 0.0;
 #pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) t += __shfl_xor(t, sh, 64);
+        for (int sh = 32; sh > 0; sh >>= 1) t += __shfl_xor(t, sh, 64);      // wave_sum's butterfly, in float64
 #pragma unroll
         for (int q = 0; q < kAdj; ++q) sum[q] = q == k ? t : sum[q];
     }
-    // one record per wave in LDS, one per tile in the workspace
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < kAdj; ++q) s_sum[wave][q] = sum[q];
-    }
-    __syncthreads();
-    const int q = threadIdx.x;
-    if (q < kAdj) {
-        double s = s_sum[0][q];
-        for (int i = 1; i < kTileRows; ++i) s += s_sum[i][q];
-        a.rec[((size_t)b * a.tiles + blockIdx.x) * kAdjStride + q] = s;
-    }
+    tile_record(s_sum, wave, sum, [&](int q, double s) { a.rec[((size_t)b * a.tiles + blockIdx.x) * kAdjStride + q] = s; });
 }
 
 // One block per image: word q of the image's tile records summed by 32 chains (record t goes to chain t % 32), the chains
@@ -563,16 +553,11 @@ __global__ __launch_bounds__(kBlock) void lm_grad_finish_kernel(const GradCall a
     if (step >= last_step(a) || step == 0) return;
     const int b = blockIdx.x, q = threadIdx.x & (kAdjStride - 1), chain = threadIdx.x / kAdjStride;
     double acc = 0.0;
-    if (q < state_words<MODEL>()) {
-        const double* p = a.rec + (size_t)b * a.tiles * kAdjStride + q;
-        for (int t = chain; t < a.tiles; t += kChains) acc += p[(size_t)t * kAdjStride];
-    }
+    if (q < state_words<MODEL>()) acc = chain_sum<kChains>(a.rec + (size_t)b * a.tiles * kAdjStride + q, kAdjStride, a.tiles, chain);
     part[chain][q] = acc;
     __syncthreads();
     if (threadIdx.x < kAdj) {
-        double s = part[0][threadIdx.x];
-        for (int i = 1; i < kChains; ++i) s += part[i][threadIdx.x];
-        a.adj[(size_t)b * kAdjStride + threadIdx.x] = (float)(s + (double)a.direct[(size_t)b * kAdjStride + threadIdx.x]);
+        a.adj[(size_t)b * kAdjStride + threadIdx.x] = (float)(column_sum(part, threadIdx.x) + (double)a.direct[(size_t)b * kAdjStride + threadIdx.x]);
     }
 }
 
@@ -583,12 +568,12 @@ struct Workspace {
 Workspace workspace_of(int B, int H, int W) {
     Workspace w;
     size_t o = 0;
-    auto take = [&](size_t floats) { const size_t at = o; o += (floats * sizeof(float) + 255) / 256 * 256; return at; };
-    w.adj = take((size_t)B * kAdjStride);
-    w.direct = take((size_t)B * kAdjStride);
-    w.stepc = take((size_t)B * kStepWords);
-    w.params = take((size_t)B * kParamFloats);
-    w.rec = take((size_t)B * tile_count(H, W, 1) * kAdjStride * 2);      // float64 records
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    w.adj = take((size_t)B * kAdjStride * sizeof(float));
+    w.direct = take((size_t)B * kAdjStride * sizeof(float));
+    w.stepc = take((size_t)B * kStepWords * sizeof(float));
+    w.params = take((size_t)B * kParamFloats * sizeof(float));
+    w.rec = take(tile_record_bytes(B, H, W, kAdjStride, sizeof(double)));
     w.bytes = o;
     return w;
 }
@@ -596,8 +581,7 @@ Workspace workspace_of(int B, int H, int W) {
 }  // namespace
 
 size_t lm_backward_workspace(int B, int H, int W) {
-    if (B < 1 || B > kMaxCallImages || H < 1 || W < 1 || !tile_grid_fits(H, W)) return 0;
-    return workspace_of(B, H, W).bytes;
+    return call_sizes_fit(B, H, W) ? workspace_of(B, H, W).bytes : 0;
 }
 
 hipError_t launch_lm_backward(int camera_model, const float* up, const float* lat, const float* upc, const float* latc, int B, int H,

@@ -15,19 +15,14 @@
 //
 // Per image: mean = sum e / (H W), weighted = sum(e conf) / sum conf, recall@t = #(e < t) / (H W).
 //
-// Layout: the tile geometry of gclm_render.h -- one wave walks 64 PX adjacent pixels of a row, 4 waves cover 4 rows, grid =
-// (tiles of one image, B).  A lane sums its PX pixels in float32, a wave sums its lanes with a butterfly of shuffles (every
-// lane ends with the same bits), the counts are ballots (wave-uniform integers); lane 0 of each wave leaves its record in
-// LDS, and after ONE barrier the block writes one partial record per tile into the caller's workspace:
+// Layout: the tile walk of gclm_render.h ("The tile walk": tile geometry, pixels per lane, wave sum, one record per tile, a
+// finish kernel of strided float64 chains), grid = (tiles of one image, B).  What is this file's own: the counts are ballots
+// (wave-uniform integers) that lane 0 leaves in LDS next to the wave's float sums, and the record of a tile is
 //   words [0, 6): float sum e_up, sum e_up c_up, sum c_up, sum e_lat, sum e_lat c_lat, sum c_lat;  then n_thresholds
-//   uint32 counts of up, then of latitude.
-// field_error_finish_kernel (grid = B) then sums each image's records in float64 in a fixed order (eight strided chains,
-// combined in order) and writes the statistics.  No atomics, no block waits on another: the bits of an image's statistics
-// depend on that image's pixels, H, W and the pixels per lane alone.
-//
-// Pixels per lane: PX = 4 (dwordx4 loads) where W % 4 == 0 and every plane is 16-byte aligned, else 2 (dwordx2) where W is
-// even and every plane 8-byte aligned, else 1; the planes of every image of a batch then share the alignment of the
-// first, so an image's path does not depend on its place in the batch.  64-bit offsets.  No scratch.
+//   uint32 counts of up, then of latitude,
+// so field_error_finish_kernel (grid = B, eight chains) walks words of two types and keeps chain_sum's loop written out.
+// The u, r2 loop of a lane's pixels is written out as well (as field_loss.hip's lane_row has it: through a shared function
+// field_error_kernel's instruction streams change).  64-bit offsets.  No scratch.
 // Measured (both confidences, four against two pixels per lane in one process): -5 % (pinhole) /
 // -1 .. 0 % (simple_divisional) kernel time at B = 1024, -13 % / -9 % at B = 16: four kept.
 #include "gclm_render.h"
@@ -47,17 +42,6 @@ struct FieldErrArgs {
     float thr[kMaxThr];
 };
 
-template <int PX>
-__device__ __forceinline__ void store_px(const float (&v)[PX], float* p) {
-    if constexpr (PX == 1) {
-        store_nt(v[0], p);
-    } else if constexpr (PX == 2) {
-        store_nt(f32x2{v[0], v[1]}, reinterpret_cast<f32x2*>(p));
-    } else {
-        store_nt(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
-    }
-}
-
 template <int MODEL, int PX>
 __global__ __launch_bounds__(kBlock) void field_error_kernel(const FieldErrArgs a) {
     __shared__ float s_sum[kTileRows][kSumWords];
@@ -71,16 +55,7 @@ __global__ __launch_bounds__(kBlock) void field_error_kernel(const FieldErrArgs 
 #pragma unroll
     for (int j = 0; j < PX; ++j) e_up[j] = e_lat[j] = nan;      // a lane outside the image counts at no threshold
     if (in) {
-        const float* cb = a.cam + (size_t)b * 8;
-        const float* gb = a.grav + (size_t)b * 3;
-        PerspRow r;
-        r.ifx = 1.f / cb[2];
-        r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
-        r.a = gb[0], r.b = gb[1], r.c = gb[2];
-        r.v = ((float)y - cb[5]) * (1.f / cb[3]);
-        r.v2 = r.v * r.v;
-        r.py = r.b - r.c * r.v;
-        // PX > 1 runs only where W % PX == 0: x is a multiple of PX, so x + PX <= W
+        const PerspRow r = persp_row(a.cam + (size_t)b * 8, a.grav + (size_t)b * 3, y);
         const size_t hw = (size_t)a.H * a.W, o = (size_t)b * hw + (size_t)y * a.W + x;
         float u[PX], r2[PX];
 #pragma unroll
@@ -150,9 +125,7 @@ __global__ __launch_bounds__(kBlock) void field_error_kernel(const FieldErrArgs 
     if (k < words) {
         uint32_t w;
         if (k < kSumWords) {
-            float s = s_sum[0][k];
-            for (int i = 1; i < kTileRows; ++i) s += s_sum[i][k];
-            w = __float_as_uint(s);
+            w = __float_as_uint(column_sum(s_sum, k));
         } else {
             const int c = k - kSumWords, col = c < a.nth ? c : kMaxThr + (c - a.nth);
             w = 0;
@@ -172,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void field_error_finish_kernel(const uint32
     double acc = 0.0;
     if (k < words) {
         const uint32_t* p = rec + (size_t)b * tiles * words + k;
-        for (int t = chain; t < tiles; t += kChains) {
+        for (int t = chain; t < tiles; t += kChains) {       // chain_sum's walk, over words of two types
             const uint32_t w = p[(size_t)t * words];
             acc += k < kSumWords ? (double)__uint_as_float(w) : (double)w;
         }
@@ -180,8 +153,7 @@ __global__ __launch_bounds__(kBlock) void field_error_finish_kernel(const uint32
     part[chain][k] = acc;
     __syncthreads();
     if (threadIdx.x < 32) {
-        double s = part[0][k];
-        for (int i = 1; i < kChains; ++i) s += part[i][k];
+        const double s = column_sum(part, k);
         part[0][k] = s;
     }
     __syncthreads();
@@ -203,38 +175,24 @@ __global__ __launch_bounds__(kBlock) void field_error_finish_kernel(const uint32
 #define GCLM_METRICS_MAX_PX 4
 #endif
 
-// pixels per lane of a call (file header)
-int pixels_per_lane(int W, const float* up, const float* lat, const float* upc, const float* latc, const float* up_err,
-                    const float* lat_err) {
-    uintptr_t bits = 0;
-    for (const float* p : {up, lat, upc, latc, up_err, lat_err}) bits |= reinterpret_cast<uintptr_t>(p);
-    if (GCLM_METRICS_MAX_PX >= 4 && W % 4 == 0 && bits % 16 == 0) return 4;
-    return W % 2 == 0 && bits % 8 == 0 ? 2 : 1;
-}
-
 }  // namespace
 
 size_t field_errors_workspace(int B, int H, int W, int n_thresholds) {
-    if (B < 1 || B > kMaxCallImages || H < 1 || W < 1 || n_thresholds < 0 || n_thresholds > kMaxThr) return 0;
-    if (!tile_grid_fits(H, W)) return 0;
-    // sized for one pixel per lane, the path with the most tiles
-    return (size_t)B * tile_count(H, W, 1) * (kSumWords + 2 * n_thresholds) * sizeof(uint32_t);
+    if (!call_sizes_fit(B, H, W) || n_thresholds < 0 || n_thresholds > kMaxThr) return 0;
+    return tile_record_bytes(B, H, W, kSumWords + 2 * n_thresholds, sizeof(uint32_t));
 }
 
 hipError_t launch_field_errors(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
                                const float* lat, const float* upc, const float* latc, int n_thresholds, const float* thresholds,
                                void* workspace, float* stats, float* up_err, float* lat_err, hipStream_t st) {
-    const int px = pixels_per_lane(W, up, lat, upc, latc, up_err, lat_err);
+    const int px = pixels_per_lane(W, {up, lat, upc, latc, up_err, lat_err}, GCLM_METRICS_MAX_PX);
     FieldErrArgs a{cam, grav, up, lat, upc, latc, up_err, lat_err, static_cast<uint32_t*>(workspace), H, W, tile_columns(W, px),
                    n_thresholds, {}};
     for (int k = 0; k < n_thresholds; ++k) a.thr[k] = thresholds[k];
     const int tiles = tile_count(H, W, px);
     return with_camera_model(camera_model, [&](auto m) {
         constexpr int M = decltype(m)::value;
-        auto kernel = px == 2 ? field_error_kernel<M, 2> : field_error_kernel<M, 1>;
-#if GCLM_METRICS_MAX_PX >= 4
-        if (px == 4) kernel = field_error_kernel<M, 4>;
-#endif
+        const auto kernel = with_pixels_per_lane<GCLM_METRICS_MAX_PX>(px, [](auto p) { return field_error_kernel<M, decltype(p)::value>; });
         hipLaunchKernelGGL(kernel, dim3(tiles, B), dim3(kBlock), 0, st, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

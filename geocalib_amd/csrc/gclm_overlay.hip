@@ -79,9 +79,7 @@ __device__ __forceinline__ float arrow_coverage(const PerspRow& r, float cy, flo
             const float wx = (float)(x - (int)ax), wy = (float)(y - (int)ay);
             if (!(fabsf(wx) < reach && fabsf(wy) < reach)) continue;       // beyond the arrow's reach: coverage 0
             PerspRow ra = r;
-            ra.v = ((float)(int)ay - cy) * ify;
-            ra.v2 = ra.v * ra.v;
-            ra.py = ra.b - ra.c * ra.v;
+            persp_set_row(ra, ((float)(int)ay - cy) * ify);
             const float u = ((float)(int)ax - r.cx) * r.ifx;
             const f32x2 q = persp_up<MODEL>(ra, u, u * u + ra.v2, false);
             const float n = sqrtf(q.x * q.x + q.y * q.y);
@@ -140,14 +138,8 @@ __global__ __launch_bounds__(kBlock) void overlay_kernel(const float* __restrict
     if (layers) {
         const float* cb = cam + (size_t)b * cam_stride;
         const float* gb = grav + (size_t)b * grav_stride;
-        const float ify = 1.f / cb[3], cy = cb[5];
-        PerspRow r;
-        r.ifx = 1.f / cb[2];
-        r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
-        r.a = gb[0], r.b = gb[1], r.c = gb[2];
-        r.v = ((float)y - cy) * ify;
-        r.v2 = r.v * r.v;
-        r.py = r.b - r.c * r.v;
+        const float ify = 1.f / cb[3], cy = cb[5];     // (persp_row's own: kept for the slope and the anchors' rows)
+        const PerspRow r = persp_row(cb, gb, y);
         float col[3];
 
         if (layers & GCLM_OVERLAY_HEAT) {

@@ -21,11 +21,10 @@
 // that moved the state, and left as a 16-float pose record the pass reads with uniform loads; the factors of the focal
 // derivative that do not depend on the pixel (c / f, -1 / f, df/dv) are applied after the sum, in float64.
 //
-// Reduction as gclm_metrics.hip: float32 per lane, a butterfly per wave, one record of eight floats per workgroup in the
-// caller's workspace [sum theta, sum e, three sums of d theta, three of d e]; param_opt_finish_kernel (one block per image)
-// sums an image's records in float64 in a fixed order (32 strided chains, combined in order).  No atomics on floats, no block
-// waits on another: an image's bits depend on its pixels, H, W and the pixels per lane (4 where W % 4 == 0 and both planes are
-// 16-byte aligned, 2 where W is even and both 8-byte aligned, else 1) alone -- not on B, not on the other images.
+// Reduction: the tile walk of gclm_render.h ("The tile walk"), with one record of eight floats per workgroup in the caller's
+// workspace [sum theta, sum e, three sums of d theta, three of d e]; param_opt_finish_kernel (one block per image) sums an
+// image's records in 32 chains.  No atomics on floats: an image's bits depend on its pixels, H, W and the pixels per lane
+// alone -- not on B, not on the other images.
 //
 // The update (param_opt_update, one lane per image) is the reference's step in its order: Adam (torch's defaults, bias
 // corrections; parameters and moments float32, the arithmetic of one step in float64 and rounded once), then
@@ -77,7 +76,6 @@ __global__ __launch_bounds__(kBlock) void param_opt_pass_kernel(const PassArgs a
         const float* P = a.pose + (size_t)b * kPoseWords;
         const float ga = P[0], gb = P[1], gc = P[2], ifx = P[3], dar = P[4], dbr = P[5], dap = P[6], dbp = P[7], dcp = P[8];
         const float w = ((float)y - P[10]) * ifx, w2 = w * w, qy = gb - gc * w;
-        // PX > 1 runs only where W % PX == 0: x is a multiple of PX, so x + PX <= W
         const size_t hw = (size_t)a.H * a.W, o = (size_t)b * hw + (size_t)y * a.W + x;
         float tx[PX], ty[PX], tl[PX];
         load_px<PX>(a.up + o + (size_t)b * hw, tx);              // (B, 2, H, W): image b starts at 2 b H W
@@ -131,17 +129,7 @@ __global__ __launch_bounds__(kBlock) void param_opt_pass_kernel(const PassArgs a
     }
 #pragma unroll
     for (int k = 0; k < kRecWords; ++k) sum[k] = wave_sum(sum[k]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kRecWords; ++k) s_sum[wave][k] = sum[k];
-    }
-    __syncthreads();
-    const int k = threadIdx.x;
-    if (k < kRecWords) {
-        float s = s_sum[0][k];
-        for (int i = 1; i < kTileRows; ++i) s += s_sum[i][k];
-        a.rec[((size_t)b * gridDim.x + blockIdx.x) * kRecWords + k] = s;
-    }
+    tile_record(s_sum, wave, sum, [&](int k, float s) { a.rec[((size_t)b * gridDim.x + blockIdx.x) * kRecWords + k] = s; });
 }
 
 // The pose record of a state, formed in float64 and rounded once.
@@ -209,18 +197,11 @@ __global__ __launch_bounds__(kBlock) void param_opt_finish_kernel(const float* _
     const int b = blockIdx.x, k = threadIdx.x & (kRecWords - 1), chain = threadIdx.x / kRecWords;
     uint32_t* s = state ? state + (size_t)b * kStateWords : nullptr;
     if (s && s[S_DONE]) return;               // (uniform)
-    double acc = 0.0;
-    const float* p = rec + (size_t)b * tiles * kRecWords + k;
-    for (int t = chain; t < tiles; t += kChains) acc += (double)p[(size_t)t * kRecWords];
-    part[chain][k] = acc;
+    part[chain][k] = chain_sum<kChains>(rec + (size_t)b * tiles * kRecWords + k, kRecWords, tiles, chain);
     __syncthreads();
     if (threadIdx.x != 0) return;
     double sum[kRecWords];
-    for (int j = 0; j < kRecWords; ++j) {
-        double v = part[0][j];
-        for (int i = 1; i < kChains; ++i) v += part[i][j];
-        sum[j] = v;
-    }
+    for (int j = 0; j < kRecWords; ++j) sum[j] = column_sum(part, j);
     float* P = pose + (size_t)b * kPoseWords;
     const double inv = 1.0 / ((double)H * W), half = 0.5 * (double)rpv[(size_t)b * rpv_stride + 2], sh = sin(half);
     const double dfdv = -0.25 * H / (sh * sh), ifx = P[3], gc = P[2];
@@ -305,22 +286,14 @@ ParamOptCfg device_config(const gclm_param_opt_config& c) {
             c.sched_threshold, c.sched_min_lr, c.sched_eps};
 }
 
-// pixels per lane of a call (file header)
-int pixels_per_lane(int W, const float* up, const float* lat) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(up) | reinterpret_cast<uintptr_t>(lat);
-    if (W % 4 == 0 && bits % 16 == 0) return 4;
-    return W % 2 == 0 && bits % 8 == 0 ? 2 : 1;
-}
-
-// Where the parts of a workspace lie: records (sized for one pixel per lane, the path with the most tiles), pose records,
-// state records, the count of converged images.
+// Where the parts of a workspace lie: tile records, pose records, state records, the count of converged images.
 struct Workspace {
     float *rec, *pose;
     uint32_t* state;
     int* n_done;
 };
 
-size_t record_bytes(int B, int H, int W) { return (size_t)B * tile_count(H, W, 1) * kRecWords * sizeof(float); }
+size_t record_bytes(int B, int H, int W) { return tile_record_bytes(B, H, W, kRecWords, sizeof(float)); }
 
 Workspace carve(void* workspace, int B, int H, int W) {
     char* p = static_cast<char*>(workspace);
@@ -338,7 +311,7 @@ Workspace carve(void* workspace, int B, int H, int W) {
 hipError_t launch_pass(const float* up, const float* lat, const float* pose, const int32_t* done, float* rec, int B, int H, int W,
                        int px, hipStream_t st) {
     const PassArgs a{up, lat, pose, done, rec, H, W, tile_columns(W, px)};
-    auto kernel = px == 4 ? param_opt_pass_kernel<4> : (px == 2 ? param_opt_pass_kernel<2> : param_opt_pass_kernel<1>);
+    const auto kernel = with_pixels_per_lane(px, [](auto p) { return param_opt_pass_kernel<decltype(p)::value>; });
     hipLaunchKernelGGL(kernel, dim3(tile_count(H, W, px), B), dim3(kBlock), 0, st, a);
     return hipGetLastError();
 }
@@ -346,14 +319,14 @@ hipError_t launch_pass(const float* up, const float* lat, const float* pose, con
 }  // namespace
 
 size_t param_opt_workspace(int B, int H, int W) {
-    if (B < 1 || B > kMaxCallImages || H < 2 || W < 2 || !tile_grid_fits(H, W)) return 0;
+    if (!call_sizes_fit(B, H, W) || H < 2 || W < 2) return 0;
     return record_bytes(B, H, W) + (size_t)B * (kPoseWords * sizeof(float) + kStateWords * sizeof(uint32_t)) + 16;
 }
 
 hipError_t launch_param_opt_cost(const float* up, const float* lat, const float* rpv, int B, int H, int W, void* workspace,
                                  float* out, hipStream_t st) {
     const Workspace w = carve(workspace, B, H, W);
-    const int px = pixels_per_lane(W, up, lat);
+    const int px = pixels_per_lane(W, {up, lat});
     hipLaunchKernelGGL(param_opt_pose_kernel, dim3((B + 63) / 64), dim3(64), 0, st, rpv, B, H, W, w.pose);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -372,7 +345,7 @@ hipError_t launch_param_opt_step(void* state, const float* cost, int B, const gc
 hipError_t launch_param_opt(const float* up, const float* lat, const float* init, int B, int H, int W,
                             const gclm_param_opt_config& cfg, void* workspace, float* rpv, float* info, hipStream_t st) {
     const Workspace w = carve(workspace, B, H, W);
-    const int px = pixels_per_lane(W, up, lat), tiles = tile_count(H, W, px);
+    const int px = pixels_per_lane(W, {up, lat}), tiles = tile_count(H, W, px);
     const ParamOptCfg c = device_config(cfg);
     hipLaunchKernelGGL(param_opt_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, up, lat, init, B, H, W, cfg.lr, w.state, w.pose,
                        w.n_done);

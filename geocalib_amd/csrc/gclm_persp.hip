@@ -36,15 +36,7 @@ __global__ __launch_bounds__(kBlock) void perspective_field_kernel(const float* 
     int x, y;
     if (!tile_pixel<PX>(tiles_x, H, W, x, y)) return;
     const int b = blockIdx.y;
-    const float* cb = cam + (size_t)b * 8;
-    const float* gb = grav + (size_t)b * 3;
-    PerspRow r;
-    r.ifx = 1.f / cb[2];
-    r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
-    r.a = gb[0], r.b = gb[1], r.c = gb[2];
-    r.v = ((float)y - cb[5]) * (1.f / cb[3]);
-    r.v2 = r.v * r.v;
-    r.py = r.b - r.c * r.v;
+    const PerspRow r = persp_row(cam + (size_t)b * 8, grav + (size_t)b * 3, y);
     const size_t o = ((size_t)b * H + y) * W + x;
     const bool nrm = normalize != 0;
     if constexpr (PX == 1) {

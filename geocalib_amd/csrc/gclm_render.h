@@ -1,13 +1,18 @@
-// gclm_render.h -- the per-pixel core of the one-pass render kernels (gclm_image.hip, gclm_pano.hip, gclm_reproject.hip, gclm_persp.hip) and of
-// the kernels that score fields against one calibration (gclm_metrics.hip) or against many (gclm_hypotheses.hip); device
-// code, included by those six (and by gclm_entry.hip, for the bound on the tile grid) only: the
-// camera models' undistort and distort scales, the zero-padded bilinear sampler (float32 images, and uint8 images planar or
-// interleaved with their rounding store), the nontemporal store, the tile geometry and the perspective fields of one pixel.  Each kernel keeps its own coordinate formula.
+// gclm_render.h -- the per-pixel core of the one-pass kernels over the tile geometry below.  Included by ten kernel files --
+// the renderers gclm_image.hip, gclm_pano.hip, gclm_reproject.hip, gclm_persp.hip and gclm_overlay.hip, and the kernels that
+// score, fit or differentiate predicted fields, gclm_metrics.hip, gclm_hypotheses.hip, gclm_param_opt.hip,
+// gclm_field_loss.hip and gclm_lm_grad.hip -- and by gclm_entry.hip, for the bound on the tile grid: the camera models'
+// undistort and distort scales, the zero-padded bilinear sampler (float32 images, and uint8 images planar or interleaved
+// with their rounding store), the nontemporal store, the tile geometry, the perspective fields of one pixel, and the tile
+// walk of the second group ("The tile walk" below: pixels per lane, per-row terms, wave sum, tile record, chain sum).
+// Each kernel keeps its own coordinate formula, argument struct, record layout and finish epilogue.
 //
 // Nothing here is shared with the LM sweep (gclm_pass.hip) or with synth_kernel (gclm_synth.hip), on purpose: the sweep
 // keeps the reference's float32 forms so that the solve rounds like the reference, and the synthetic fields' bits define
 // the benchmark's inputs.
 #pragma once
+#include <initializer_list>
+
 #include "gclm_internal.h"
 
 namespace gclm {
@@ -185,6 +190,23 @@ struct PerspRow {
     float v, v2, py;            // per row: v, v^2, b - c v
 };
 
+// The row's terms at normalised height v.
+__device__ __forceinline__ void persp_set_row(PerspRow& r, float v) {
+    r.v = v;
+    r.v2 = r.v * r.v;
+    r.py = r.b - r.c * r.v;
+}
+
+// The terms of row y of the image with camera row cb = {w, h, fx, fy, cx, cy, k1, k2} and gravity gb = (a, b, c).
+__device__ __forceinline__ PerspRow persp_row(const float* cb, const float* gb, int y) {
+    PerspRow r;
+    r.ifx = 1.f / cb[2];
+    r.cx = cb[4], r.k1 = cb[6], r.k2 = cb[7];
+    r.a = gb[0], r.b = gb[1], r.c = gb[2];
+    persp_set_row(r, ((float)y - cb[5]) * (1.f / cb[3]));
+    return r;
+}
+
 template <int MODEL>
 __device__ __forceinline__ f32x2 persp_up(const PerspRow& r, float u, float r2, bool normalize) {
     const float px = r.a - r.c * u;
@@ -251,11 +273,48 @@ __device__ __forceinline__ float persp_lat_slope(const PerspRow& r, float u, flo
     return sqrtf(sx * sx + sy * sy) * 57.29577951308232f / sqrtf((1.f - sc) * (1.f + sc));
 }
 
-// What the kernels that score predicted fields share (gclm_metrics.hip: one calibration per image, gclm_hypotheses.hip: N
-// per image), so that both compile the same per-pixel functions: the vector load of a lane's pixels, the wave sum and the
-// masked up error (its formula is in gclm_metrics.hip's header).
-constexpr float kDegrees = 57.29577951308232f;
-constexpr float kCosEps = 1e-8f;             // F.cosine_similarity's eps
+// The tile walk of the kernels that reduce an image's pixels to a few numbers per image (gclm_metrics.hip,
+// gclm_hypotheses.hip, gclm_param_opt.hip, gclm_field_loss.hip, gclm_lm_grad.hip).  Every rule stands here
+// once; each kernel keeps its per-pixel body, its record layout and what its finish kernel makes of the sums.
+//   - grid = (tiles of one image, .., images) over the tile geometry above, PX = 4, 2 or 1 pixels per lane
+//     (pixels_per_lane: by W and the planes' alignment; the planes of every image of a batch share the alignment of the
+//     first, so an image's path does not depend on its place in the batch); load_px / store_px move a lane's pixels.
+//   - A lane sums its pixels in its own type (float; float64 in gclm_lm_grad.hip, which writes wave_sum's butterfly out on
+//     doubles); a lane outside the image adds zeros.  wave_sum adds the lanes of a wave, lane 0 leaves the wave's record in
+//     LDS, and after ONE barrier thread k adds word k of the kTileRows waves in order and stores it (tile_record): one
+//     record per tile in the caller's workspace, which is sized for one pixel per lane, the path with the most tiles
+//     (tile_record_bytes).
+//   - The finish kernel (one block per image) sums word k of the image's records in float64 in CHAINS strided chains
+//     (chain_sum: record t goes to chain t % CHAINS) and adds the chains in order (column_sum).
+// No atomics, no block waits on another: the bits of an image's sums depend on that image's pixels, H, W, the pixels per
+// lane and the kernel's chain count alone.
+// Written out where the shared function changed a kernel's instruction stream (profiles/tile_walk_asm_equal.log): the
+// float64 butterfly of lm_grad_pixel_kernel, and the chain walk of field_error_finish_kernel over words of two types.
+
+// Pixels per lane of a call (host): 4 (dwordx4) where W % 4 == 0 and every plane is 16-byte aligned, else 2 (dwordx2) where
+// W is even and every plane 8-byte aligned, else 1.  A NULL plane is aligned.  PX > 1 thus runs only where W % PX == 0: a
+// lane's x is a multiple of PX, so x + PX <= W, and its vector loads and stores are aligned.
+inline int pixels_per_lane(int W, std::initializer_list<const void*> planes, int max_px = 4) {
+    uintptr_t bits = 0;
+    for (const void* p : planes) bits |= reinterpret_cast<uintptr_t>(p);
+    if (max_px >= 4 && W % 4 == 0 && bits % 16 == 0) return 4;
+    return W % 2 == 0 && bits % 8 == 0 ? 2 : 1;
+}
+
+// Where px becomes a template argument, as with_camera_model: returns f(std::integral_constant<int, PX>{}).  Host code.
+template <int MAX_PX = 4, typename F>
+auto with_pixels_per_lane(int px, F&& f) {
+    if constexpr (MAX_PX >= 4) {
+        if (px == 4) return f(std::integral_constant<int, 4>{});
+    }
+    return px == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 1>{});
+}
+
+// The sizes every such call takes (host), and the bytes of its tile records: at one pixel per lane, the path with the most tiles.
+constexpr bool call_sizes_fit(int B, int H, int W) { return B >= 1 && B <= kMaxCallImages && H >= 1 && W >= 1 && tile_grid_fits(H, W); }
+constexpr size_t tile_record_bytes(size_t images, int H, int W, size_t words, size_t bytes_per_word) {
+    return images * tile_count(H, W, 1) * words * bytes_per_word;
+}
 
 template <int PX>
 __device__ __forceinline__ void load_px(const float* __restrict__ p, float (&v)[PX]) {
@@ -270,6 +329,23 @@ __device__ __forceinline__ void load_px(const float* __restrict__ p, float (&v)[
     }
 }
 
+// ... and stores them: nontemporal (NT) for a plane the caller reads much later, plain for one that is read next.
+template <bool NT, typename T>
+__device__ __forceinline__ void store_as(T v, T* p) {
+    if constexpr (NT) store_nt(v, p);
+    else *p = v;
+}
+template <int PX, bool NT = true>
+__device__ __forceinline__ void store_px(const float (&v)[PX], float* p) {
+    if constexpr (PX == 1) {
+        store_as<NT>(v[0], p);
+    } else if constexpr (PX == 2) {
+        store_as<NT>(f32x2{v[0], v[1]}, reinterpret_cast<f32x2*>(p));
+    } else {
+        store_as<NT>(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
+    }
+}
+
 // Sum over the 64 lanes of a wave, the same bits in every lane (a butterfly: lane i adds lane i ^ o, o = 32 .. 1).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -277,7 +353,51 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// The masked up error in degrees (file header).
+// s[0][k] + s[1][k] + .. in that order: the waves of a tile, or the chains of a finish kernel.
+template <typename T, int N, int WORDS>
+__device__ __forceinline__ T column_sum(const T (&s)[N][WORDS], int k) {
+    T v = s[0][k];
+    for (int i = 1; i < N; ++i) v += s[i][k];
+    return v;
+}
+
+// The tail of a tile: `s` is the kernel's LDS array, `wave` this thread's row of it (threadIdx.x >> 6, which the kernel has
+// at hand), `sum` the wave's sums, the same in every lane; store(k, v) writes word k of the tile's record (thread k calls
+// it, so the record's address is formed by that thread alone).  Every thread of the block calls tile_record.
+template <typename T, int WORDS, typename Store>
+__device__ __forceinline__ void tile_record(T (&s)[kTileRows][WORDS], int wave, const T (&sum)[WORDS], Store&& store) {
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k) s[wave][k] = sum[k];
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < WORDS) store(k, column_sum(s, k));
+}
+
+// Chain `chain` of CHAINS over the records p[0], p[stride], .. of `tiles` tiles: WORDS adjacent words each, in float64.
+template <int CHAINS, int WORDS, typename T>
+__device__ __forceinline__ void chain_sum(const T* p, size_t stride, int tiles, int chain, double (&acc)[WORDS]) {
+#pragma unroll
+    for (int k = 0; k < WORDS; ++k) acc[k] = 0.0;
+    for (int t = chain; t < tiles; t += CHAINS) {
+        const T* w = p + (size_t)t * stride;
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k) acc[k] += (double)w[k];
+    }
+}
+template <int CHAINS, typename T>
+__device__ __forceinline__ double chain_sum(const T* p, size_t stride, int tiles, int chain) {
+    double acc[1];
+    chain_sum<CHAINS, 1>(p, stride, tiles, chain, acc);
+    return acc[0];
+}
+
+// What the kernels that score predicted fields share (gclm_metrics.hip: one calibration per image, gclm_hypotheses.hip: N
+// per image): the masked up error in degrees (its formula is in gclm_metrics.hip's header).
+constexpr float kDegrees = 57.29577951308232f;
+constexpr float kCosEps = 1e-8f;             // F.cosine_similarity's eps
+
 __device__ __forceinline__ float up_error_deg(float px, float py, f32x2 t) {
     const float pn2 = px * px + py * py, tn2 = t.x * t.x + t.y * t.y;
     float dot = px * t.x + py * t.y, crs = px * t.y - py * t.x, sn;
