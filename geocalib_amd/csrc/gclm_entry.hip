@@ -204,6 +204,68 @@ int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const flo
                                nullptr, stream);
 }
 
+int gclm_pack_fields_typed(int raw_dtype, const void* d_up_raw, const void* d_up_logconf, const void* d_lat_raw,
+                           const void* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
+                           float* d_lat_conf, float* d_sin_lat, void* stream) {
+    // float32 raws: gclm_pack_fields_ex itself -- its checks (outputs may alias their inputs), its kernel, its bits
+    if (raw_dtype == GCLM_LOGITS_F32)
+        return gclm_pack_fields_ex(static_cast<const float*>(d_up_raw), static_cast<const float*>(d_up_logconf),
+                                   static_cast<const float*>(d_lat_raw), static_cast<const float*>(d_lat_logconf), B, H, W, d_up,
+                                   d_up_conf, d_lat, d_lat_conf, d_sin_lat, stream);
+    if (raw_dtype != GCLM_LOGITS_F16 && raw_dtype != GCLM_LOGITS_BF16) return -3;
+    if (!d_up_raw || !d_lat_raw || !d_up || !d_lat || B < 0 || H <= 0 || W <= 0) return -3;
+    if ((d_up_logconf && !d_up_conf) || (d_lat_logconf && !d_lat_conf)) return -3;
+    // 16-bit raws: an output is twice its input's size, so nothing is converted in place -- every plane written keeps off
+    // every other plane of the call.  A confidence output without its log-confidence is not written and names no range.
+    const size_t px = floats(B, H, W), raw = elements<uint16_t>(B, H, W);
+    float* const up_conf = d_up_logconf ? d_up_conf : nullptr;
+    float* const lat_conf = d_lat_logconf ? d_lat_conf : nullptr;
+    ArgCheck a;
+    a.writes(d_sin_lat, px, 4);
+    a.writes(d_up, mul_sat(px, 2), 4);
+    a.writes(d_lat, px, 4);
+    a.writes(up_conf, px, 4);
+    a.writes(lat_conf, px, 4);
+    a.reads(d_up_raw, mul_sat(raw, 2), 2);
+    a.reads(d_lat_raw, raw, 2);
+    a.reads(d_up_logconf, raw, 2);
+    a.reads(d_lat_logconf, raw, 2);
+    if (!a.pass()) return -3;
+    bool vec = ((size_t)H * W) % 8 == 0;
+    for (const void* p : {d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, (const void*)d_up, (const void*)up_conf, (const void*)d_lat,
+                          (const void*)lat_conf, (const void*)d_sin_lat})
+        vec = vec && is_aligned(p, 16);
+    return launched(launch_pack_fields_typed(raw_dtype, d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, vec, d_up, up_conf,
+                                             d_lat, lat_conf, d_sin_lat, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_pack_fields_backward(int raw_dtype, const void* d_up_raw, const void* d_up_logconf, const void* d_lat_raw,
+                              const void* d_lat_logconf, int B, int H, int W, const float* d_g_up, const float* d_g_up_conf,
+                              const float* d_g_lat, const float* d_g_lat_conf, void* d_d_up_raw, void* d_d_up_logconf,
+                              void* d_d_lat_raw, void* d_d_lat_logconf, void* stream) {
+    if (raw_dtype != GCLM_LOGITS_F32 && raw_dtype != GCLM_LOGITS_F16 && raw_dtype != GCLM_LOGITS_BF16) return -3;
+    if (B < 0 || H <= 0 || W <= 0 || (!d_d_up_raw && !d_d_up_logconf && !d_d_lat_raw && !d_d_lat_logconf)) return -3;
+    // a gradient asked for needs the gradient of its output and its raw plane; a group not asked for is not read
+    struct Group { const void* raw; const float* g; void* d; int planes; };
+    const Group groups[] = {{d_up_raw, d_g_up, d_d_up_raw, 2}, {d_up_logconf, d_g_up_conf, d_d_up_logconf, 1},
+                            {d_lat_raw, d_g_lat, d_d_lat_raw, 1}, {d_lat_logconf, d_g_lat_conf, d_d_lat_logconf, 1}};
+    for (const Group& g : groups)
+        if (g.d && (!g.raw || !g.g)) return -3;
+    const size_t esize = raw_dtype == GCLM_LOGITS_F32 ? 4 : 2, px = floats(B, H, W), raw = mul_sat(elements<char>(B, H, W), esize);
+    ArgCheck a;
+    for (const Group& g : groups) a.writes(g.d, mul_sat(raw, g.planes), esize);
+    bool vec = ((size_t)H * W) % (esize == 4 ? 4 : 8) == 0;
+    for (const Group& g : groups) {
+        a.reads(g.raw, mul_sat(raw, g.planes), esize);      // (every plane given is held to the rules, read or not)
+        a.reads(g.g, mul_sat(px, g.planes), 4);
+        if (g.d) vec = vec && is_aligned(g.raw, 16) && is_aligned(g.g, 16) && is_aligned(g.d, 16);
+    }
+    if (!a.pass()) return -3;
+    return launched(launch_pack_fields_backward(raw_dtype, d_up_raw, d_up_logconf, d_lat_raw, d_lat_logconf, B, H, W, vec, d_g_up,
+                                                d_g_up_conf, d_g_lat, d_g_lat_conf, d_d_up_raw, d_d_up_logconf, d_d_lat_raw,
+                                                d_d_lat_logconf, static_cast<hipStream_t>(stream)));
+}
+
 int gclm_pack_fields_bins(const void* d_up_logits, int up_bins, const void* d_lat_logits, int lat_bins, int logit_dtype,
                           const float* d_up_table, const float* d_lat_table, const float* d_up_logconf,
                           const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,

@@ -1,93 +1,23 @@
 // gclm_fields.hip -- the steps before and after the path: the CNN-head epilogue that packs the planes a sweep reads
-// (gclm_pack_fields; gclm_pack_fields_bins for classification heads) and the bilinear upsampler of GeoCalib._post_process (gclm_upsample_fields).  Per-pixel streaming
-// kernels; nothing here knows about the solve.
+// (gclm_pack_fields; gclm_pack_fields_typed for 16-bit raws; gclm_pack_fields_bins for classification heads), that epilogue's
+// backward (gclm_pack_fields_backward) and the bilinear upsampler of GeoCalib._post_process (gclm_upsample_fields).  Per-pixel
+// streaming kernels; nothing here knows about the solve.
 #include "gclm_device.h"
 
 namespace gclm {
 
 namespace {
 
-// ---------------------------------------------------------------- CNN-head epilogue (the step before the path)
-// UpDecoder / LatitudeDecoder epilogues (geocalib.py:57,73-75) fused into ONE pass that writes the five
-// planes the sweep reads: up = normalize(raw, dim=1), latitude = asin(clamp(tanh(raw), +-(1-1e-5))),
-// confidences = sigmoid(log-confidence).  Eager PyTorch runs 8 elementwise kernels and ~18 plane passes.
-// slat (gclm_pack_fields_ex; NULL: not written): a sixth plane, sin of the latitude just written, by the sweep's own
-// polynomial (dev::sin_halfpi) -- the floats a sweep would compute from `lat`, so a solve that reads this plane in place of
-// the radians gives the same bits.  The packed latitude lies within +-asin(1 - 1e-5) < pi/2: the range fold the sweep keeps
-// for a caller's own radians (gclm_pass.hip: row_slat) never fires on it and is not needed here.
-template <int VEC>
-__global__ void pack_fields_kernel(const float* __restrict__ up_raw, const float* __restrict__ up_lc,
-                                   const float* __restrict__ lat_raw, const float* __restrict__ lat_lc, int B,
-                                   size_t N, float* __restrict__ up, float* __restrict__ upc,
-                                   float* __restrict__ lat, float* __restrict__ latc, float* __restrict__ slat) {
-    const size_t units = N / VEC;
-    for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        const float* ux = up_raw + (size_t)b * 2 * N;
-        const float* uy = ux + N;
-        float* ox = up + (size_t)b * 2 * N;
-        float* oy = ox + N;
-        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < units; i += (size_t)gridDim.x * blockDim.x) {
-            float vx[VEC], vy[VEC], vl[VEC], c1[VEC], c2[VEC], sl[VEC];
-            if constexpr (VEC == 4) {
-                // every byte is read once and written once: non-temporal both ways (+4 ... 8 % over plain float4 accesses,
-                // profiles/archive/r05_pack_bench.log)
-                typedef float pk4 __attribute__((ext_vector_type(4)));
-                auto ld4 = [](const float* p, size_t j) { return __builtin_nontemporal_load(reinterpret_cast<const pk4*>(p) + j); };
-                const pk4 a = ld4(ux, i), bq = ld4(uy, i), l = ld4(lat_raw + (size_t)b * N, i);
-                vx[0] = a.x; vx[1] = a.y; vx[2] = a.z; vx[3] = a.w;
-                vy[0] = bq.x; vy[1] = bq.y; vy[2] = bq.z; vy[3] = bq.w;
-                vl[0] = l.x; vl[1] = l.y; vl[2] = l.z; vl[3] = l.w;
-                if (up_lc) { const pk4 t = ld4(up_lc + (size_t)b * N, i); c1[0] = t.x; c1[1] = t.y; c1[2] = t.z; c1[3] = t.w; }
-                if (lat_lc) { const pk4 t = ld4(lat_lc + (size_t)b * N, i); c2[0] = t.x; c2[1] = t.y; c2[2] = t.z; c2[3] = t.w; }
-            } else {
-                vx[0] = ux[i]; vy[0] = uy[i]; vl[0] = lat_raw[(size_t)b * N + i];
-                if (up_lc) c1[0] = up_lc[(size_t)b * N + i];
-                if (lat_lc) c2[0] = lat_lc[(size_t)b * N + i];
-            }
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const float n = fmaxf(sqrtf(vx[k] * vx[k] + vy[k] * vy[k]), 1e-12f);     // F.normalize eps
-                vx[k] /= n; vy[k] /= n;
-                vl[k] = asinf(fminf(fmaxf(tanhf(vl[k]), -1.0f + 1e-5f), 1.0f - 1e-5f));
-                if (slat) sl[k] = dev::sin_halfpi(vl[k]);
-                if (up_lc) c1[k] = 1.0f / (1.0f + expf(-c1[k]));
-                if (lat_lc) c2[k] = 1.0f / (1.0f + expf(-c2[k]));
-            }
-            if constexpr (VEC == 4) {
-                typedef float pk4 __attribute__((ext_vector_type(4)));
-                auto st4 = [](float* p, size_t j, const float (&v)[VEC]) {
-                    __builtin_nontemporal_store(pk4{v[0], v[1], v[2], v[3]}, reinterpret_cast<pk4*>(p) + j);
-                };
-                st4(ox, i, vx); st4(oy, i, vy); st4(lat + (size_t)b * N, i, vl);
-                if (up_lc) st4(upc + (size_t)b * N, i, c1);
-                if (lat_lc) st4(latc + (size_t)b * N, i, c2);
-                if (slat) st4(slat + (size_t)b * N, i, sl);
-            } else {
-                ox[i] = vx[0]; oy[i] = vy[0]; lat[(size_t)b * N + i] = vl[0];
-                if (up_lc) upc[(size_t)b * N + i] = c1[0];
-                if (lat_lc) latc[(size_t)b * N + i] = c2[0];
-                if (slat) slat[(size_t)b * N + i] = sl[0];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------- classification heads (the same step, the other format)
-// UpDecoder / LatitudeDecoder with loss_type == "classification" (the original PerspectiveFields weights): the heads emit
-// Ku and Kl logits per pixel, the fields are the decodes of the per-pixel argmax.  ONE pass reads the Ku + Kl logit planes
-// once and writes the planes the sweep reads; a decode has one value per bin, so it is a gather from the caller's tables
-// (include/gclm.h: gclm_pack_fields_bins), staged in LDS once per workgroup -- no device cos or sin, the reference's bits.
-// Lanes run along pixels and the channel loop runs inside the lane: every channel read is a row of consecutive pixels, the
-// running maximum and its index never leave registers.  DT = the logits' type (gclm_logit_dtype); VEC = pixels per lane:
-// one 16-byte load per channel (4 floats, 8 halves) where the planes allow it, else 1.
-// slat: sin of the latitude just written, by the sweep's polynomial, as in pack_fields_kernel; a bin centre lies strictly
-// inside +-pi/2, so no range fold here either.
+// ---------------------------------------------------------------- planes of float32, float16 or bfloat16 elements
+// What the typed kernels below share (the head epilogue, its backward, the classification heads): DT = the elements' type
+// (gclm_logit_dtype); VEC = pixels per lane: one 16-byte access per plane (4 floats, 8 halves) where the planes allow it, else 1.
+// (the names are the classification heads', which had them first)
 typedef uint32_t bins_u4 __attribute__((ext_vector_type(4)));
 typedef float bins_f4 __attribute__((ext_vector_type(4)));
 template <int DT>
 using bins_elem = std::conditional_t<DT == GCLM_LOGITS_F32, float, uint16_t>;
 constexpr int bins_vec(int dt) { return dt == GCLM_LOGITS_F32 ? 4 : 8; }
-constexpr int kBinsUnroll = 8;      // channel loads in flight per lane
+constexpr int kBinsUnroll = 8;      // pack_bins_kernel: channel loads in flight per lane
 
 // 16-bit logits widen to float exactly, so one comparison serves the three types
 template <int DT>
@@ -112,6 +42,205 @@ __device__ __forceinline__ void bins_load(const bins_elem<DT>* __restrict__ plan
         }
     }
 }
+template <int VEC>
+__device__ __forceinline__ void bins_load_f32(const float* p, size_t i, float (&v)[VEC]) {
+    if constexpr (VEC == 1) v[0] = p[i];
+    else {
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q) {
+            const bins_f4 t = __builtin_nontemporal_load(reinterpret_cast<const bins_f4*>(p) + i * (VEC / 4) + q);
+            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        }
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void bins_store_f32(float* p, size_t i, const float (&v)[VEC]) {
+    if constexpr (VEC == 1) p[i] = v[0];
+    else {
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q)
+            __builtin_nontemporal_store(bins_f4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]},
+                                        reinterpret_cast<bins_f4*>(p) + i * (VEC / 4) + q);
+    }
+}
+
+// ---------------------------------------------------------------- CNN-head epilogue (the step before the path)
+// UpDecoder / LatitudeDecoder epilogues (geocalib.py:57,73-75) fused into ONE pass that writes the five
+// planes the sweep reads: up = normalize(raw, dim=1), latitude = asin(clamp(tanh(raw), +-(1-1e-5))),
+// confidences = sigmoid(log-confidence).  Eager PyTorch runs 8 elementwise kernels and ~18 plane passes.
+// slat (gclm_pack_fields_ex; NULL: not written): a sixth plane, sin of the latitude just written, by the sweep's own
+// polynomial (dev::sin_halfpi) -- the floats a sweep would compute from `lat`, so a solve that reads this plane in place of
+// the radians gives the same bits.  The packed latitude lies within +-asin(1 - 1e-5) < pi/2: the range fold the sweep keeps
+// for a caller's own radians (gclm_pass.hip: row_slat) never fires on it and is not needed here.
+// DT (gclm_pack_fields_typed): the raw planes' type.  float32 is the kernel as it always was; 16-bit raws widen exactly on
+// load, eight per lane on the vector walk (one 16-byte load per plane, two 16-byte stores per float32 output), and the
+// arithmetic below is the same float32 expressions -- the bits of the float32 kernel on the widened planes.
+template <int VEC, int DT = GCLM_LOGITS_F32>
+__global__ void pack_fields_kernel(const bins_elem<DT>* __restrict__ up_raw, const bins_elem<DT>* __restrict__ up_lc,
+                                   const bins_elem<DT>* __restrict__ lat_raw, const bins_elem<DT>* __restrict__ lat_lc, int B,
+                                   size_t N, float* __restrict__ up, float* __restrict__ upc,
+                                   float* __restrict__ lat, float* __restrict__ latc, float* __restrict__ slat) {
+    const size_t units = N / VEC;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const bins_elem<DT>* ux = up_raw + (size_t)b * 2 * N;
+        const bins_elem<DT>* uy = ux + N;
+        float* ox = up + (size_t)b * 2 * N;
+        float* oy = ox + N;
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < units; i += (size_t)gridDim.x * blockDim.x) {
+            float vx[VEC], vy[VEC], vl[VEC], c1[VEC], c2[VEC], sl[VEC];
+            if constexpr (DT != GCLM_LOGITS_F32) {
+                bins_load<DT, VEC>(ux, i, vx); bins_load<DT, VEC>(uy, i, vy); bins_load<DT, VEC>(lat_raw + (size_t)b * N, i, vl);
+                if (up_lc) bins_load<DT, VEC>(up_lc + (size_t)b * N, i, c1);
+                if (lat_lc) bins_load<DT, VEC>(lat_lc + (size_t)b * N, i, c2);
+            } else if constexpr (VEC == 4) {
+                // every byte is read once and written once: non-temporal both ways (+4 ... 8 % over plain float4 accesses,
+                // profiles/archive/r05_pack_bench.log)
+                typedef float pk4 __attribute__((ext_vector_type(4)));
+                auto ld4 = [](const float* p, size_t j) { return __builtin_nontemporal_load(reinterpret_cast<const pk4*>(p) + j); };
+                const pk4 a = ld4(ux, i), bq = ld4(uy, i), l = ld4(lat_raw + (size_t)b * N, i);
+                vx[0] = a.x; vx[1] = a.y; vx[2] = a.z; vx[3] = a.w;
+                vy[0] = bq.x; vy[1] = bq.y; vy[2] = bq.z; vy[3] = bq.w;
+                vl[0] = l.x; vl[1] = l.y; vl[2] = l.z; vl[3] = l.w;
+                if (up_lc) { const pk4 t = ld4(up_lc + (size_t)b * N, i); c1[0] = t.x; c1[1] = t.y; c1[2] = t.z; c1[3] = t.w; }
+                if (lat_lc) { const pk4 t = ld4(lat_lc + (size_t)b * N, i); c2[0] = t.x; c2[1] = t.y; c2[2] = t.z; c2[3] = t.w; }
+            } else {
+                vx[0] = ux[i]; vy[0] = uy[i]; vl[0] = lat_raw[(size_t)b * N + i];
+                if (up_lc) c1[0] = up_lc[(size_t)b * N + i];
+                if (lat_lc) c2[0] = lat_lc[(size_t)b * N + i];
+            }
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float n = fmaxf(sqrtf(vx[k] * vx[k] + vy[k] * vy[k]), 1e-12f);     // F.normalize eps
+                vx[k] /= n; vy[k] /= n;
+                vl[k] = asinf(fminf(fmaxf(tanhf(vl[k]), -1.0f + 1e-5f), 1.0f - 1e-5f));
+                if (slat) sl[k] = dev::sin_halfpi(vl[k]);
+                if (up_lc) c1[k] = 1.0f / (1.0f + expf(-c1[k]));
+                if (lat_lc) c2[k] = 1.0f / (1.0f + expf(-c2[k]));
+            }
+            if constexpr (VEC == 8) {
+                const size_t j = (size_t)b * (N / VEC) + i;
+                bins_store_f32<VEC>(ox, i, vx); bins_store_f32<VEC>(oy, i, vy); bins_store_f32<VEC>(lat, j, vl);
+                if (up_lc) bins_store_f32<VEC>(upc, j, c1);
+                if (lat_lc) bins_store_f32<VEC>(latc, j, c2);
+                if (slat) bins_store_f32<VEC>(slat, j, sl);
+            } else if constexpr (VEC == 4) {
+                typedef float pk4 __attribute__((ext_vector_type(4)));
+                auto st4 = [](float* p, size_t j, const float (&v)[VEC]) {
+                    __builtin_nontemporal_store(pk4{v[0], v[1], v[2], v[3]}, reinterpret_cast<pk4*>(p) + j);
+                };
+                st4(ox, i, vx); st4(oy, i, vy); st4(lat + (size_t)b * N, i, vl);
+                if (up_lc) st4(upc + (size_t)b * N, i, c1);
+                if (lat_lc) st4(latc + (size_t)b * N, i, c2);
+                if (slat) st4(slat + (size_t)b * N, i, sl);
+            } else {
+                ox[i] = vx[0]; oy[i] = vy[0]; lat[(size_t)b * N + i] = vl[0];
+                if (up_lc) upc[(size_t)b * N + i] = c1[0];
+                if (lat_lc) latc[(size_t)b * N + i] = c2[0];
+                if (slat) slat[(size_t)b * N + i] = sl[0];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- the epilogue's backward (gclm_pack_fields_backward)
+// The gradients of the four outputs above, g_*, taken back to the raw planes in ONE pass that reads the raws again and
+// recomputes in float32 what it needs of the forward: no forward output is read, none has to be kept.  d_* are written in
+// the raws' type, rounded to nearest even.  A group (up, latitude, either confidence) runs where its d_* is given -- wave-
+// uniform branches, as the forward's; the entry has checked that such a group has its raw plane and its g_*.
+//   up          n = |r|.  n >= 1e-12: with u = r / n and u' = (-u.y, u.x), d_r = u' (u' . g) / n -- in two dimensions this IS
+//               g - u (u . g), without its cancellation where g is nearly parallel to u, and d_r . r = 0 to the rounding
+//               of two products.  n < 1e-12 (the clamped branch of F.normalize): d_r = g / 1e-12.
+//   latitude    asin(tanh x) has the derivative sech x = 2 e / (1 + e^2), e = exp(-|x|) (no cancellation; sqrt(1 - t^2) has
+//               lost three digits at |x| = 6); exactly 0 where the forward's tanhf(x) left [-1 + 1e-5, 1 - 1e-5] -- the same
+//               comparison on the same float, so forward and backward agree on every pixel about what was clamped.
+//   confidence  s (1 - s) = e / (1 + e)^2, e = exp(-|x|): finite and >= 0 for every finite x.
+// A NaN raw makes e (or n) NaN and with it the gradients of its own group only.
+// The raws and the incoming gradients are read once: non-temporal loads.  The raw gradients are read by autograd's next
+// kernel, so their stores were decided by a measurement with such a reader behind the pass: plain -- non-temporal
+// stores win 6 % at B = 1024 and lose as much at B = 64, a training batch (GCLM_PACK_BWD_NT_STORES builds that variant).
+template <int DT>
+__device__ __forceinline__ bins_elem<DT> pack_narrow(float v) {      // round to nearest even, as torch's .to(dtype)
+    if constexpr (DT == GCLM_LOGITS_F32) return v;
+    else if constexpr (DT == GCLM_LOGITS_F16) return __builtin_bit_cast(uint16_t, (_Float16)v);
+    else {
+        const uint32_t u = __builtin_bit_cast(uint32_t, v);
+        return v != v ? (uint16_t)0x7fc0u : (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+    }
+}
+template <int DT, int VEC>
+__device__ __forceinline__ void pack_store_grad(bins_elem<DT>* p, size_t i, const float (&v)[VEC]) {
+    if constexpr (VEC == 1) p[i] = pack_narrow<DT>(v[0]);
+    else {
+        bins_u4 q;
+        if constexpr (DT == GCLM_LOGITS_F32) {
+            q = bins_u4{__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]), __builtin_bit_cast(uint32_t, v[2]),
+                        __builtin_bit_cast(uint32_t, v[3])};
+        } else {
+            uint32_t w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w[k] = (uint32_t)pack_narrow<DT>(v[2 * k]) | ((uint32_t)pack_narrow<DT>(v[2 * k + 1]) << 16);
+            q = bins_u4{w[0], w[1], w[2], w[3]};
+        }
+#ifdef GCLM_PACK_BWD_NT_STORES
+        __builtin_nontemporal_store(q, reinterpret_cast<bins_u4*>(p) + i);
+#else
+        reinterpret_cast<bins_u4*>(p)[i] = q;
+#endif
+    }
+}
+template <int DT, int VEC>
+__global__ __launch_bounds__(256) void pack_fields_backward_kernel(
+    const bins_elem<DT>* __restrict__ up_raw, const bins_elem<DT>* __restrict__ up_lc, const bins_elem<DT>* __restrict__ lat_raw,
+    const bins_elem<DT>* __restrict__ lat_lc, int B, size_t N, const float* __restrict__ g_up, const float* __restrict__ g_upc,
+    const float* __restrict__ g_lat, const float* __restrict__ g_latc, bins_elem<DT>* __restrict__ d_up,
+    bins_elem<DT>* __restrict__ d_upc, bins_elem<DT>* __restrict__ d_lat, bins_elem<DT>* __restrict__ d_latc) {
+    const size_t units = N / VEC;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const size_t up0 = (size_t)b * 2 * units, px0 = (size_t)b * units;      // in units: N is a multiple of VEC
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < units; i += (size_t)gridDim.x * blockDim.x) {
+            float vx[VEC], vy[VEC], gx[VEC], gy[VEC], vl[VEC], gl[VEC], c1[VEC], g1[VEC], c2[VEC], g2[VEC];
+            if (d_up) {
+                bins_load<DT, VEC>(up_raw, up0 + i, vx); bins_load<DT, VEC>(up_raw, up0 + units + i, vy);
+                bins_load_f32<VEC>(g_up, up0 + i, gx); bins_load_f32<VEC>(g_up, up0 + units + i, gy);
+            }
+            if (d_lat) { bins_load<DT, VEC>(lat_raw, px0 + i, vl); bins_load_f32<VEC>(g_lat, px0 + i, gl); }
+            if (d_upc) { bins_load<DT, VEC>(up_lc, px0 + i, c1); bins_load_f32<VEC>(g_upc, px0 + i, g1); }
+            if (d_latc) { bins_load<DT, VEC>(lat_lc, px0 + i, c2); bins_load_f32<VEC>(g_latc, px0 + i, g2); }
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                if (d_up) {
+                    const float n = sqrtf(vx[k] * vx[k] + vy[k] * vy[k]);      // the forward's expression
+                    const float ux = vx[k] / n, uy = vy[k] / n;
+                    const float c = (ux * gy[k] - uy * gx[k]) / n;
+                    const bool clamped = n < 1e-12f;
+                    vx[k] = clamped ? gx[k] / 1e-12f : -uy * c;
+                    vy[k] = clamped ? gy[k] / 1e-12f : ux * c;
+                }
+                if (d_lat) {
+                    const float t = tanhf(vl[k]), e = expf(-fabsf(vl[k]));
+                    vl[k] = (t < -1.0f + 1e-5f || t > 1.0f - 1e-5f) ? 0.0f : gl[k] * (2.0f * e / (1.0f + e * e));
+                }
+                if (d_upc) { const float e = expf(-fabsf(c1[k])); c1[k] = g1[k] * (e / ((1.0f + e) * (1.0f + e))); }
+                if (d_latc) { const float e = expf(-fabsf(c2[k])); c2[k] = g2[k] * (e / ((1.0f + e) * (1.0f + e))); }
+            }
+            if (d_up) { pack_store_grad<DT, VEC>(d_up, up0 + i, vx); pack_store_grad<DT, VEC>(d_up, up0 + units + i, vy); }
+            if (d_lat) pack_store_grad<DT, VEC>(d_lat, px0 + i, vl);
+            if (d_upc) pack_store_grad<DT, VEC>(d_upc, px0 + i, c1);
+            if (d_latc) pack_store_grad<DT, VEC>(d_latc, px0 + i, c2);
+        }
+    }
+}
+
+// ---------------------------------------------------------------- classification heads (the same step, the other format)
+// UpDecoder / LatitudeDecoder with loss_type == "classification" (the original PerspectiveFields weights): the heads emit
+// Ku and Kl logits per pixel, the fields are the decodes of the per-pixel argmax.  ONE pass reads the Ku + Kl logit planes
+// once and writes the planes the sweep reads; a decode has one value per bin, so it is a gather from the caller's tables
+// (include/gclm.h: gclm_pack_fields_bins), staged in LDS once per workgroup -- no device cos or sin, the reference's bits.
+// Lanes run along pixels and the channel loop runs inside the lane: every channel read is a row of consecutive pixels, the
+// running maximum and its index never leave registers.  DT = the logits' type (gclm_logit_dtype); VEC = pixels per lane:
+// one 16-byte load per channel (4 floats, 8 halves) where the planes allow it, else 1.
+// slat: sin of the latitude just written, by the sweep's polynomial, as in pack_fields_kernel; a bin centre lies strictly
+// inside +-pi/2, so no range fold here either.
 // torch.argmax's rule over the K planes of one image: the first index of the greatest value; a NaN is greater than everything
 // and the first NaN wins; all -inf gives 0.  A later x replaces the best only if the best is no NaN and x <= best is false.
 template <int DT, int VEC>
@@ -138,27 +267,6 @@ __device__ __forceinline__ void bins_argmax(const bins_elem<DT>* __restrict__ lo
     for (; c < K; ++c) {
         bins_load<DT, VEC>(logits + (size_t)c * N, i, v[0]);
         take(v[0], c);
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void bins_load_f32(const float* p, size_t i, float (&v)[VEC]) {
-    if constexpr (VEC == 1) v[0] = p[i];
-    else {
-#pragma unroll
-        for (int q = 0; q < VEC / 4; ++q) {
-            const bins_f4 t = __builtin_nontemporal_load(reinterpret_cast<const bins_f4*>(p) + i * (VEC / 4) + q);
-            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-        }
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void bins_store_f32(float* p, size_t i, const float (&v)[VEC]) {
-    if constexpr (VEC == 1) p[i] = v[0];
-    else {
-#pragma unroll
-        for (int q = 0; q < VEC / 4; ++q)
-            __builtin_nontemporal_store(bins_f4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]},
-                                        reinterpret_cast<bins_f4*>(p) + i * (VEC / 4) + q);
     }
 }
 // (the log-confidences may be their own outputs, lane by lane: no __restrict__ on those four)
@@ -601,6 +709,55 @@ hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const flo
     const dim3 grid(bx, B < 4096 ? B : 4096), block(256);
     if (vec4) hipLaunchKernelGGL(pack_fields_kernel<4>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc, slat);
     else hipLaunchKernelGGL(pack_fields_kernel<1>, grid, block, 0, s, up_raw, up_lc, lat_raw, lat_lc, B, N, up, upc, lat, latc, slat);
+    return hipGetLastError();
+}
+
+// The grid of the two typed epilogue passes: pack_fields' own.
+static dim3 pack_grid(size_t units, int B) {
+    const int bx = (int)((units + 255) / 256 < 2048 ? (units + 255) / 256 : 2048);
+    return dim3(bx, B < 4096 ? B : 4096);
+}
+// 16-bit raws (float32 raws are launch_pack_fields').  `vec`: as below.
+hipError_t launch_pack_fields_typed(int dtype, const void* up_raw, const void* up_lc, const void* lat_raw, const void* lat_lc, int B,
+                                    int H, int W, bool vec, float* up, float* upc, float* lat, float* latc, float* slat, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    const size_t N = (size_t)H * W;
+    auto go = [&](auto dt, auto v) {
+        constexpr int DT = decltype(dt)::value, VEC = decltype(v)::value;
+        using E = bins_elem<DT>;
+        hipLaunchKernelGGL((pack_fields_kernel<VEC, DT>), pack_grid(N / VEC, B), dim3(256), 0, s, static_cast<const E*>(up_raw),
+                           static_cast<const E*>(up_lc), static_cast<const E*>(lat_raw), static_cast<const E*>(lat_lc), B, N, up, upc, lat,
+                           latc, slat);
+    };
+    auto width = [&](auto dt) {
+        if (vec) go(dt, std::integral_constant<int, 8>{});
+        else go(dt, std::integral_constant<int, 1>{});
+    };
+    if (dtype == GCLM_LOGITS_F16) width(std::integral_constant<int, GCLM_LOGITS_F16>{});
+    else if (dtype == GCLM_LOGITS_BF16) width(std::integral_constant<int, GCLM_LOGITS_BF16>{});
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_pack_fields_backward(int dtype, const void* up_raw, const void* up_lc, const void* lat_raw, const void* lat_lc, int B,
+                                       int H, int W, bool vec, const float* g_up, const float* g_upc, const float* g_lat,
+                                       const float* g_latc, void* d_up, void* d_upc, void* d_lat, void* d_latc, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    const size_t N = (size_t)H * W;
+    auto go = [&](auto dt, auto v) {
+        constexpr int DT = decltype(dt)::value, VEC = decltype(v)::value;
+        using E = bins_elem<DT>;
+        hipLaunchKernelGGL((pack_fields_backward_kernel<DT, VEC>), pack_grid(N / VEC, B), dim3(256), 0, s, static_cast<const E*>(up_raw),
+                           static_cast<const E*>(up_lc), static_cast<const E*>(lat_raw), static_cast<const E*>(lat_lc), B, N, g_up, g_upc,
+                           g_lat, g_latc, static_cast<E*>(d_up), static_cast<E*>(d_upc), static_cast<E*>(d_lat), static_cast<E*>(d_latc));
+    };
+    auto width = [&](auto dt) {
+        if (vec) go(dt, std::integral_constant<int, bins_vec(decltype(dt)::value)>{});
+        else go(dt, std::integral_constant<int, 1>{});
+    };
+    if (dtype == GCLM_LOGITS_F32) width(std::integral_constant<int, GCLM_LOGITS_F32>{});
+    else if (dtype == GCLM_LOGITS_F16) width(std::integral_constant<int, GCLM_LOGITS_F16>{});
+    else if (dtype == GCLM_LOGITS_BF16) width(std::integral_constant<int, GCLM_LOGITS_BF16>{});
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

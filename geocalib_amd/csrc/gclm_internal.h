@@ -221,6 +221,15 @@ hipError_t launch_upsample_multi(const UpsampleMulti& m, int h, int w, int H, in
 hipError_t launch_pack_fields(const float* up_raw, const float* up_lc, const float* lat_raw, const float* lat_lc,
                               int B, int H, int W, bool vec4, float* up, float* upc, float* lat, float* latc,
                               float* slat /* or nullptr */, hipStream_t s);
+// ... for float16 / bfloat16 raws (dtype: gclm_logit_dtype; vec: 16-byte planes and H * W a multiple of 8)
+hipError_t launch_pack_fields_typed(int dtype, const void* up_raw, const void* up_lc, const void* lat_raw, const void* lat_lc, int B,
+                                    int H, int W, bool vec, float* up, float* upc, float* lat, float* latc, float* slat /* or nullptr */,
+                                    hipStream_t s);
+// the gradients g_* of pack_fields' outputs back to the raw planes d_*, in the raws' dtype; a group runs where its d_* is given
+// (vec: 16-byte planes and H * W a multiple of 4 for float32, of 8 for the 16-bit types)
+hipError_t launch_pack_fields_backward(int dtype, const void* up_raw, const void* up_lc, const void* lat_raw, const void* lat_lc, int B,
+                                       int H, int W, bool vec, const float* g_up, const float* g_upc, const float* g_lat,
+                                       const float* g_latc, void* d_up, void* d_upc, void* d_lat, void* d_latc, hipStream_t s);
 hipError_t launch_pack_fields_bins(const void* up_logits, int Ku, const void* lat_logits, int Kl, int dtype, const float* up_table,
                                    const float* lat_table, const float* up_lc, const float* lat_lc, int B, int H, int W, bool vec,
                                    float* up, float* upc, float* lat, float* latc, float* slat /* or nullptr */, hipStream_t s);

@@ -9,40 +9,123 @@ Replaces the tail of the reference's UpDecoder / LatitudeDecoder (geocalib/geoca
 
 and writes the five planes in the layout LMOptimizer reads (eager PyTorch: 8 kernels, ~18 plane passes) -- and, on request,
 a sixth: sin(latitude_field), which the LM solve reads in place of the radians (gclm_pack_fields_ex).  `pack_fields_from_logits`
-is the same step for classification heads (gclm_pack_fields_bins)."""
+is the same step for classification heads (gclm_pack_fields_bins).  `pack_fields` reads float16 / bfloat16 raws as they are
+(gclm_pack_fields_typed) and, for raws that require grad, carries a graph whose backward is one more HIP pass
+(gclm_pack_fields_backward): with losses.perspective_field_loss and the differentiable LMOptimizer, everything after the
+network's last convolution is this package's, forward and backward."""
 import ctypes
 from typing import Dict, Optional
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _call, _lib
+
+
+_LOGIT_DTYPES = {torch.float32: _lib.LOGIT_DTYPE_IDS["float32"], torch.float16: _lib.LOGIT_DTYPE_IDS["float16"],
+                 torch.bfloat16: _lib.LOGIT_DTYPE_IDS["bfloat16"]}
+_HALF_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _pack_call(up_raw, lat_raw, ulc, llc, inplace: bool, sin_latitude: bool):
+    """The forward launch of pack_fields on raws as the kernels read them -- contiguous, detached, all float32 or all of one
+    16-bit type: (up, lat, up_conf, lat_conf, sin_lat), None for a plane not asked for."""
+    B, _, H, W = lat_raw.shape
+    assert up_raw.shape == (B, 2, H, W), up_raw.shape
+    for c in (ulc, llc):
+        assert c is None or c.numel() == B * H * W, c.shape
+    if lat_raw.dtype is torch.float32:
+        out_like = (lambda t: t) if inplace else torch.empty_like
+        entry, dtype = "gclm_pack_fields_ex", ()
+    else:
+        out_like = lambda t: torch.empty_like(t, dtype=torch.float32)      # noqa: E731
+        entry, dtype = "gclm_pack_fields_typed", (_LOGIT_DTYPES[lat_raw.dtype],)
+    up, lat = out_like(up_raw), out_like(lat_raw)
+    upc = None if ulc is None else out_like(ulc).view(B, H, W)
+    latc = None if llc is None else out_like(llc).view(B, H, W)
+    slat = torch.empty_like(lat) if sin_latitude else None       # (never in place: a plane of its own)
+    p = _call.ptr
+    _call.call(entry, *dtype, p(up_raw), p(ulc), p(lat_raw), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc), p(slat),
+               _call.raw_stream(lat_raw.device), device=lat_raw.device)
+    return up, lat, upc, latc, slat
+
+
+class _PackFieldsFunction(torch.autograd.Function):
+    """(up_raw, lat_raw, up_log_confidence, lat_log_confidence) -> (up, lat, up_conf, lat_conf, sin_lat) with a graph: the
+    forward is _pack_call, the backward one pass of gclm_pack_fields_backward that reads the raws again -- nothing but the
+    inputs is kept.  The raws come contiguous, all float32 or all of one 16-bit type; an absent confidence is None."""
+
+    @staticmethod
+    def forward(ctx, up_raw, lat_raw, ulc, llc, sin_latitude):
+        out = _pack_call(up_raw, lat_raw, ulc, llc, False, sin_latitude)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*(t for t in (up_raw, lat_raw, ulc, llc) if t is not None))
+        ctx.given = [t is not None for t in (up_raw, lat_raw, ulc, llc)]
+        if out[4] is not None:
+            ctx.mark_non_differentiable(out[4])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_up, g_lat, g_upc, g_latc, g_slat):
+        saved = list(ctx.saved_tensors)
+        up_raw, lat_raw, ulc, llc = (saved.pop(0) if g else None for g in ctx.given)
+        B, _, H, W = lat_raw.shape
+        # a raw gets a gradient where it asks for one and its output got one; every other group is left out of the pass
+        raws, grads, out = [], [], []
+        for i, (raw, g) in enumerate(((up_raw, g_up), (lat_raw, g_lat), (ulc, g_upc), (llc, g_latc))):
+            want = raw is not None and g is not None and ctx.needs_input_grad[i]
+            raws.append(raw if want else None)
+            grads.append(g.to(torch.float32).contiguous() if want else None)
+            out.append(torch.empty_like(raw) if want else None)
+        if any(o is not None for o in out) and B > 0:
+            p, dev = _call.ptr, lat_raw.device
+            _call.call("gclm_pack_fields_backward", _LOGIT_DTYPES[lat_raw.dtype], p(raws[0]), p(raws[2]), p(raws[1]), p(raws[3]),
+                       B, H, W, p(grads[0]), p(grads[2]), p(grads[1]), p(grads[3]), p(out[0]), p(out[2]), p(out[1]), p(out[3]),
+                       _call.raw_stream(dev), device=dev)
+        return (*out, None)
 
 
 def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: Optional[torch.Tensor] = None,
                 lat_log_confidence: Optional[torch.Tensor] = None, inplace: bool = False,
                 sin_latitude: bool = False) -> Dict[str, torch.Tensor]:
     """up_raw (B,2,H,W), lat_raw (B,1,H,W), log-confidences (B,H,W) or (B,1,H,W): raw head outputs on a HIP device.
-    Returns the dict `LMOptimizer.forward` consumes.
+    Returns the dict `LMOptimizer.forward` consumes, float32.
 
     `sin_latitude`: the dict also holds "sin_latitude" (B,1,H,W), sin of "latitude_field" written by the same launch with
     the solve's own polynomial.  LMOptimizer reads it in place of the radians where its sweeps can (include/gclm.h:
     gclm_solve_ex) -- same results bit for bit, no per-sweep sin and no library-owned scratch plane.  The key names no
-    field / confidence / uncertainty, so GeoCalib._post_process neither resizes nor returns it."""
-    up_raw, lat_raw = _call.dev_f32(up_raw, "up_raw"), _call.dev_f32(lat_raw, "lat_raw")
-    B, _, H, W = lat_raw.shape
-    assert up_raw.shape == (B, 2, H, W), up_raw.shape
-    ulc = None if up_log_confidence is None else _call.dev_f32(up_log_confidence, "up_log_confidence")
-    llc = None if lat_log_confidence is None else _call.dev_f32(lat_log_confidence, "lat_log_confidence")
-    for c in (ulc, llc):
-        assert c is None or c.numel() == B * H * W, c.shape
-    out_like = (lambda t: t) if inplace else torch.empty_like
-    up, lat = out_like(up_raw), out_like(lat_raw)
-    upc = None if ulc is None else out_like(ulc).view(B, H, W)
-    latc = None if llc is None else out_like(llc).view(B, H, W)
-    slat = torch.empty_like(lat_raw) if sin_latitude else None       # (never in place: a plane of its own)
-    p = _call.ptr
-    _call.call("gclm_pack_fields_ex", p(up_raw), p(ulc), p(lat_raw), p(llc), B, H, W, p(up), p(upc), p(lat), p(latc), p(slat),
-               _call.raw_stream(lat_raw.device), device=lat_raw.device)
+    field / confidence / uncertainty, so GeoCalib._post_process neither resizes nor returns it.
+
+    Raws that are all float16 or all bfloat16 (what the heads emit under autocast) and contiguous are read as they are
+    (gclm_pack_fields_typed): no conversion pass, the bits of the call on `.float()` of them.  Mixed dtypes and strided raws
+    are brought to contiguous float32 by torch first.
+
+    In grad mode, with a raw that requires grad and `inplace` False, the outputs carry a graph: same values bit for bit, and
+    backward is one HIP pass on torch's current stream (gclm_pack_fields_backward) that reads the raws again and keeps nothing
+    else; gradients come back in each raw's dtype and shape, once (no double backward), none for "sin_latitude".
+    `inplace=True` overwrites float32 raws as it always did and attaches NO graph, whatever requires grad."""
+    names = ("up_raw", "lat_raw", "up_log_confidence", "lat_log_confidence")
+    given = [t for t in (up_raw, lat_raw, up_log_confidence, lat_log_confidence) if t is not None]
+    half = (not inplace and lat_raw.dtype in _HALF_DTYPES and all(t.dtype is lat_raw.dtype and t.is_contiguous() for t in given))
+    graph = torch.is_grad_enabled() and not inplace and any(t.requires_grad for t in given)
+    if graph or half:
+        for t, name in zip((up_raw, lat_raw, up_log_confidence, lat_log_confidence), names):
+            if t is not None:
+                _call.require_device(t, name)
+    if graph:
+        if not half:      # differentiable torch ops, outside the Function: mixed or strided raws still get their gradients
+            up_raw, lat_raw, up_log_confidence, lat_log_confidence = (
+                None if t is None else t.float().contiguous() for t in (up_raw, lat_raw, up_log_confidence, lat_log_confidence))
+        up, lat, upc, latc, slat = _PackFieldsFunction.apply(up_raw, lat_raw, up_log_confidence, lat_log_confidence, sin_latitude)
+    elif half:
+        up, lat, upc, latc, slat = _pack_call(*(None if t is None else t.detach() for t in
+                                                 (up_raw, lat_raw, up_log_confidence, lat_log_confidence)), False, sin_latitude)
+    else:
+        up_raw, lat_raw = _call.dev_f32(up_raw, "up_raw"), _call.dev_f32(lat_raw, "lat_raw")
+        ulc = None if up_log_confidence is None else _call.dev_f32(up_log_confidence, "up_log_confidence")
+        llc = None if lat_log_confidence is None else _call.dev_f32(lat_log_confidence, "lat_log_confidence")
+        up, lat, upc, latc, slat = _pack_call(up_raw, lat_raw, ulc, llc, inplace, sin_latitude)
     out = {"up_field": up, "latitude_field": lat}
     if upc is not None:
         out["up_confidence"] = upc
@@ -51,10 +134,6 @@ def pack_fields(up_raw: torch.Tensor, lat_raw: torch.Tensor, up_log_confidence: 
     if slat is not None:
         out["sin_latitude"] = slat
     return out
-
-
-_LOGIT_DTYPES = {torch.float32: _lib.LOGIT_DTYPE_IDS["float32"], torch.float16: _lib.LOGIT_DTYPE_IDS["float16"],
-                 torch.bfloat16: _lib.LOGIT_DTYPE_IDS["bfloat16"]}
 
 
 def pack_fields_from_logits(up_logits: torch.Tensor, lat_logits: torch.Tensor, up_log_confidence: Optional[torch.Tensor] = None,

@@ -60,7 +60,10 @@ extern "C" {
  * against a calibration and their gradients with respect to the predicted fields;
  * gclm_solve_recorded, gclm_calibrate_recorded, gclm_lm_backward and gclm_lm_backward_workspace added, also within 610: the
  * solve with a step record, and the adjoint of its LM steps -- the gradients of the optimised camera and gravity with respect
- * to the fields and the confidences).  gclm_create refuses a gclm_config whose first two fields do not
+ * to the fields and the confidences;
+ * gclm_pack_fields_typed and gclm_pack_fields_backward added, also within 610: the head epilogue for float16 / bfloat16 raw
+ * planes, and its backward -- the gradients of the fields and confidences taken back to the raw head outputs in one pass).
+ * gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
 
@@ -346,6 +349,42 @@ int gclm_pack_fields(const float* d_up_raw, const float* d_up_logconf, const flo
 int gclm_pack_fields_ex(const float* d_up_raw, const float* d_up_logconf, const float* d_lat_raw,
                         const float* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
                         float* d_lat_conf, float* d_sin_lat /* (B,1,H,W) or NULL */, void* stream);
+
+/*
+ * gclm_pack_fields_ex for raw planes of raw_dtype (enum gclm_logit_dtype below: float32, float16, bfloat16; all raw planes of
+ * a call share it); the outputs are float32.  Each element widens exactly and the arithmetic is gclm_pack_fields_ex's, in
+ * float32: GCLM_LOGITS_F32 gives its bits (and is that call), a 16-bit type the bits of gclm_pack_fields_ex on the widened
+ * planes.  In-place operation stays legal for float32 only.  For the 16-bit types, -3: a NULL d_up_raw, d_lat_raw, d_up or
+ * d_lat; B < 0, H or W <= 0; a log-confidence without its output; a raw plane off a 2-byte, an output off a 4-byte boundary;
+ * an output that overlaps any other plane of the call.  -3 for an unknown raw_dtype.  B = 0 succeeds and launches nothing.
+ * Where H * W is a multiple of 8 and every plane is 16-byte aligned a lane reads eight pixels with one 16-byte load per
+ * plane; any other call takes one pixel per lane, same results.
+ */
+int gclm_pack_fields_typed(int raw_dtype, const void* d_up_raw, const void* d_up_logconf, const void* d_lat_raw,
+                           const void* d_lat_logconf, int B, int H, int W, float* d_up, float* d_up_conf, float* d_lat,
+                           float* d_lat_conf, float* d_sin_lat /* (B,1,H,W) or NULL */, void* stream);
+/*
+ * The BACKWARD of that pass: the float32 gradients d_g_* of its four outputs (d_g_up (B,2,H,W), the others (B,H,W)) taken
+ * back to the raw planes, d_d_*, written in raw_dtype (rounded to nearest even from the float32 value).  One pass; it reads
+ * the raw planes again and recomputes in float32 what it needs -- no forward output is read, none has to be kept.  There is
+ * no gradient for the sin(latitude) plane.  Per pixel:
+ *   up          n = |r|;  n >= 1e-12: d_r = (g - u (u . g)) / n with u = r / n, evaluated as u' (u' . g) / n, u' = (-u.y, u.x)
+ *               (the same vector in two dimensions, without the cancellation);  n < 1e-12: d_r = g / 1e-12
+ *   latitude    d_x = g sech(x) = g 2 e / (1 + e^2), e = exp(-|x|), where tanhf(x) lies within [-1 + 1e-5, 1 - 1e-5], bounds
+ *               included; exactly 0 outside -- the forward's own comparison, so both agree on every pixel
+ *   confidence  d_x = g s (1 - s) = g e / (1 + e)^2, e = exp(-|x|): finite for every finite x
+ * A NaN raw value gives NaN gradients in its own group (up, latitude, either confidence) only.
+ * Any d_g_* may be NULL (that output got no gradient) and any d_d_* may be NULL (that gradient is not wanted); a d_d_* that is
+ * given needs its d_g_* and its raw plane, and a group whose d_d_* is NULL is not read.
+ * -3: an unknown raw_dtype; B < 0, H or W <= 0; no d_d_* at all; a d_d_* without its d_g_* or its raw plane; a pointer off its
+ * element's alignment (raw_dtype's for raws and d_d_*, 4 bytes for d_g_*); a d_d_* that overlaps any other plane of the call.
+ * B = 0 succeeds and launches nothing.  16-byte accesses (four floats; eight 16-bit elements against two float4 of gradient)
+ * where H * W is a multiple of the pixels per lane and every plane read or written is 16-byte aligned; else one pixel per lane.
+ */
+int gclm_pack_fields_backward(int raw_dtype, const void* d_up_raw, const void* d_up_logconf, const void* d_lat_raw,
+                              const void* d_lat_logconf, int B, int H, int W, const float* d_g_up, const float* d_g_up_conf,
+                              const float* d_g_lat, const float* d_g_lat_conf, void* d_d_up_raw, void* d_d_up_logconf,
+                              void* d_d_lat_raw, void* d_d_lat_logconf, void* stream);
 
 /*
  * The same step for CLASSIFICATION heads (siclib's UpDecoder / LatitudeDecoder with loss_type == "classification", the format
