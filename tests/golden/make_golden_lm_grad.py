@@ -11,6 +11,8 @@ Cases (noise 0.03 on both fields, 5 % latitude outliers of 0.4 rad, confidences 
     c1  B = 3, 12 x 20,  5 steps                         c2  B = 2, 13 x 19, 10 steps (lambda reaches its 1e-6 floor)
 each for {pinhole, simple_radial} x {huber at scale 1e-2, squared (scale 2^20)}; and at 12 x 20, pinhole, huber, 5 steps:
     prior_focal, prior_gravity, lat_only (no up field, with the latitude confidence), noconf (no confidences).
+(`make` also takes prior_focal_gravity, both priors: make_golden_lm_grad_frozen.py writes the simple_radial cases of the
+three prior plans into a file of its own with this script's `make`, `run` and `record_case`.)
 
 Asserted here (a case that misses one is replaced by the same case with fewer steps, down to 3, then by
 the next seed, from 11 on; both are recorded): the damping decisions agree between float32 and float64 at every step; no Cholesky failure; the focal and
@@ -75,9 +77,9 @@ def make(ns, model, B, H, W, extra=None, seed=SEED, **_):
     data = dict(up_field=up, latitude_field=lat, up_confidence=upc, latitude_confidence=latc)
     data = {k: v.float() for k, v in data.items()}
     priors = {}
-    if extra == "prior_focal":
+    if extra in ("prior_focal", "prior_focal_gravity"):
         priors["prior_focal"] = (cam.f[:, 1] * 1.05).float()
-    if extra == "prior_gravity":
+    if extra in ("prior_gravity", "prior_focal_gravity"):
         priors["prior_gravity"] = ns.gravity.Gravity.from_rp(roll + 0.02, pitch - 0.02).vec3d.float()
     if extra == "lat_only":
         del data["up_field"], data["up_confidence"]
@@ -154,49 +156,54 @@ def siclib_loss():
     return mod.LMOptimizer
 
 
+def record_case(ns, rec, name, cfg):
+    """One case into `rec`, under the replacement rule of the module's text; returns (float32 result, ground truth)."""
+    # a case that misses a condition is replaced: by the same case with fewer steps (never fewer than 3;
+    # a converged float32 solve compares costs that differ by rounding alone), then by
+    # the next seed
+    tries = [(seed, steps) for seed in range(SEED, SEED + 4) for steps in range(cfg["steps"], min(cfg["steps"], 3) - 1, -1)]
+    for seed, steps in tries:
+        try:
+            cfg = dict(cfg, steps=steps)
+            data, priors, gt_cam, gt_grav = make(ns, seed=seed, **cfg)
+            args = (cfg["model"], data, priors)
+            g64, d64, c64, gr64, l64, _ = run(ns, name, *args, torch.float64, cfg["steps"], cfg["scale"])
+            g32, d32, c32, gr32, l32, res32 = run(ns, name, *args, torch.float32, cfg["steps"], cfg["scale"])
+            assert bool((d64 == d32).all()), f"{name}: damping decisions differ between float32 and float64"
+            break
+        except AssertionError as e:
+            print(f"seed {seed}, {steps} steps replaced: {e}")
+    else:
+        raise SystemExit(f"{name}: no seed met the conditions")
+    rec[f"{name}/seed"] = np.array(seed)
+    for k, v in {**data, **priors}.items():
+        rec[f"{name}/in/{k}"] = v.numpy()
+    wc, wg = weights(cfg["B"], torch.float64)
+    rec[f"{name}/w_cam"], rec[f"{name}/w_grav"] = wc.numpy(), wg.numpy()
+    rec[f"{name}/cfg"] = np.array([cfg["steps"], cfg["scale"]], np.float64)
+    for k in g64:
+        rec[f"{name}/grad64/{k}"] = g64[k].numpy()
+        rec[f"{name}/grad32/{k}"] = g32[k].numpy()
+        a, b = g64[k], g32[k].double()
+        dims = tuple(range(1, a.dim()))
+        err = (a - b).abs().amax(dim=dims) / a.abs().amax(dim=dims)
+        print(f"{name:32s} {k:20s} |g64|max {a.abs().amax(dim=dims).min():.2e}..{a.abs().amax(dim=dims).max():.2e} "
+              f"f32 rel err {err.min():.2e}..{err.max():.2e}")
+    rec[f"{name}/decisions"] = d64.numpy()
+    rec[f"{name}/camera64"], rec[f"{name}/gravity64"] = c64.numpy(), gr64.numpy()
+    rec[f"{name}/camera32"], rec[f"{name}/gravity32"] = c32.numpy(), gr32.numpy()
+    rec[f"{name}/L64"] = l64.numpy()
+    rec[f"{name}/gt_camera"] = torch.cat([gt_cam._data, gt_cam._data.new_zeros(cfg["B"], 8 - gt_cam._data.shape[-1])], -1).numpy()
+    rec[f"{name}/gt_gravity"] = gt_grav._data.numpy()
+    return res32, gt_cam, gt_grav
+
+
 def main():
     ns = ref_import.load()
     rec = {}
     kept = {}
     for name, cfg in cases():
-        # a case that misses a condition is replaced: by the same case with fewer steps (never fewer than 3;
-        # a converged float32 solve compares costs that differ by rounding alone), then by
-        # the next seed
-        tries = [(seed, steps) for seed in range(SEED, SEED + 4) for steps in range(cfg["steps"], min(cfg["steps"], 3) - 1, -1)]
-        for seed, steps in tries:
-            try:
-                cfg = dict(cfg, steps=steps)
-                data, priors, gt_cam, gt_grav = make(ns, seed=seed, **cfg)
-                args = (cfg["model"], data, priors)
-                g64, d64, c64, gr64, l64, _ = run(ns, name, *args, torch.float64, cfg["steps"], cfg["scale"])
-                g32, d32, c32, gr32, l32, res32 = run(ns, name, *args, torch.float32, cfg["steps"], cfg["scale"])
-                assert bool((d64 == d32).all()), f"{name}: damping decisions differ between float32 and float64"
-                break
-            except AssertionError as e:
-                print(f"seed {seed}, {steps} steps replaced: {e}")
-        else:
-            raise SystemExit(f"{name}: no seed met the conditions")
-        rec[f"{name}/seed"] = np.array(seed)
-        for k, v in {**data, **priors}.items():
-            rec[f"{name}/in/{k}"] = v.numpy()
-        wc, wg = weights(cfg["B"], torch.float64)
-        rec[f"{name}/w_cam"], rec[f"{name}/w_grav"] = wc.numpy(), wg.numpy()
-        rec[f"{name}/cfg"] = np.array([cfg["steps"], cfg["scale"]], np.float64)
-        for k in g64:
-            rec[f"{name}/grad64/{k}"] = g64[k].numpy()
-            rec[f"{name}/grad32/{k}"] = g32[k].numpy()
-            a, b = g64[k], g32[k].double()
-            dims = tuple(range(1, a.dim()))
-            err = (a - b).abs().amax(dim=dims) / a.abs().amax(dim=dims)
-            print(f"{name:32s} {k:20s} |g64|max {a.abs().amax(dim=dims).min():.2e}..{a.abs().amax(dim=dims).max():.2e} "
-                  f"f32 rel err {err.min():.2e}..{err.max():.2e}")
-        rec[f"{name}/decisions"] = d64.numpy()
-        rec[f"{name}/camera64"], rec[f"{name}/gravity64"] = c64.numpy(), gr64.numpy()
-        rec[f"{name}/camera32"], rec[f"{name}/gravity32"] = c32.numpy(), gr32.numpy()
-        rec[f"{name}/L64"] = l64.numpy()
-        rec[f"{name}/gt_camera"] = torch.cat([gt_cam._data, gt_cam._data.new_zeros(cfg["B"], 8 - gt_cam._data.shape[-1])], -1).numpy()
-        rec[f"{name}/gt_gravity"] = gt_grav._data.numpy()
-        kept[name] = (res32, gt_cam, gt_grav)
+        kept[name] = record_case(ns, rec, name, cfg)
     # siclib's loss / metrics of the float32 results of the two c1 huber cases
     LM = siclib_loss()
     for name in ("c1/pinhole/huber", "c1/simple_radial/huber"):

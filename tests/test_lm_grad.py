@@ -36,20 +36,22 @@ def dev():
     return torch.device("cuda:0")
 
 
-def run_grad(ref, name, conf=None, wanted=INPUTS, images=None):
-    """(out, {input: gradient of the fixture's L}) of the differentiable HIP solve on a fixture case."""
+def run_grad(ref, name, conf=None, wanted=INPUTS, images=None, batch=None):
+    """(out, {input: gradient of the fixture's L}) of the differentiable HIP solve on a fixture case.  `batch`: a function
+    (data, w_cam, w_grav) -> the same three for another batch made of the case's images; `images` then selects from that."""
     data = case_data(ref, name, torch.float32, dev(), requires_grad=False)
+    wc, wg = (torch.from_numpy(ref[f"{name}/{k}"]).float().to(dev()) for k in ("w_cam", "w_grav"))
+    if batch is not None:
+        data, wc, wg = batch(data, wc, wg)
     if images is not None:
         data = {k: v[images].contiguous() for k, v in data.items()}
+        wc, wg = wc[images], wg[images]
     for k in wanted:
         if k in data:
             data[k].requires_grad_(True)
     opt = LMOptimizer({**case_conf(ref, name), "differentiable": True, **(conf or {})}).train()
     out = opt(dict(data))
     cam, grav = out["camera"], out["gravity"]
-    wc, wg = (torch.from_numpy(ref[f"{name}/{k}"]).to(cam._data) for k in ("w_cam", "w_grav"))
-    if images is not None:
-        wc, wg = wc[images], wg[images]
     loss = (cam._data[:, 2:4] / cam._data[:, 1:2] * wc[:, 2:4]).sum() + (grav._data * wg).sum()
     if hasattr(cam, "dist"):
         loss = loss + (cam._data[:, 6] * wc[:, 6]).sum()
@@ -65,6 +67,10 @@ def per_image_err(got, want):
 
 @pytest.mark.parametrize("name", ALL_CASES)
 def test_recorded_solve_equals_plain_solve(ref, name):
+    recorded_solve_equals_plain_solve(ref, name)
+
+
+def recorded_solve_equals_plain_solve(ref, name):
     data = case_data(ref, name, torch.float32, dev(), requires_grad=False)
     conf = case_conf(ref, name)
     plain = LMOptimizer(conf).train()(dict(data))
@@ -91,6 +97,10 @@ def test_recorded_solve_equals_plain_solve(ref, name):
 
 @pytest.mark.parametrize("name", ALL_CASES)
 def test_gradients_against_reference_float64(ref, name):
+    gradients_against_reference_float64(ref, name)
+
+
+def gradients_against_reference_float64(ref, name):
     out, grads = run_grad(ref, name)
     plain = LMOptimizer(case_conf(ref, name)).train()(case_data(ref, name, torch.float32, dev(), requires_grad=False))
     assert torch.equal(out["camera"]._data, plain["camera"]._data) and torch.equal(out["gravity"]._data, plain["gravity"]._data)

@@ -159,9 +159,10 @@ def stage_state(ref, model, image, kind):
 
 def oracle_step(model, inputs, cam, grav, lam, dtype, adj_cam, adj_grav):
     """One LM step of lm_unrolled_torch from (cam, grav) with damping `lam`, in `dtype`, and autograd of
-    <adj_cam, camera+> + <adj_grav, gravity+>: ({input: gradient}, (gradient of the camera row, of the gravity), out)."""
+    <adj_cam, camera+> + <adj_grav, gravity+>: ({input: gradient}, (gradient of the camera row, of the gravity), out).
+    Keys of `inputs` other than the four fields (priors) are passed on as they are: they fix columns and take no gradient."""
     from geocalib_amd.lm_optimizer import _unit_gravity
-    data = {k: v.to(dtype).requires_grad_(True) for k, v in inputs.items()}
+    data = {k: (v.to(dtype).requires_grad_(True) if k in INPUTS else v) for k, v in inputs.items()}
     c, g = cam.to(dtype).requires_grad_(True), grav.to(dtype).requires_grad_(True)
     out = lm_grad.lm_unrolled_torch(data, step_conf(model, lam), dtype=dtype, init=(camera_models[model](c), _unit_gravity(g)),
                                     detach_init=False)
@@ -186,7 +187,8 @@ def state_facts(model, inputs, cam, grav, lam):
     H = out["hessians"][0, 0]
     A = H + torch.diag((H.diagonal() * lam).clamp(min=1e-6))
     from geocalib_amd.lm_optimizer import _unit_gravity
-    model_f, _ = lm_grad.fields_and_jacobian(camera_models[model](cam.double()), _unit_gravity(grav.double()), (13, 19))
+    model_f, _ = lm_grad.fields_and_jacobian(camera_models[model](cam.double()), _unit_gravity(grav.double()),
+                                             tuple(inputs["latitude_field"].shape[-2:]))
     up = inputs["up_field"].double().permute(0, 2, 3, 1).reshape(1, -1, 2)
     sl = torch.sin(inputs["latitude_field"].double()).reshape(1, -1)
     x_up = ((up - model_f[..., :2]) ** 2).sum(-1) / HUBER ** 2

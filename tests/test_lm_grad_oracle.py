@@ -5,7 +5,11 @@ state, the damping decisions -- and its forward-mode Jacobian against the refere
 Both sides are float64 evaluations of the same formulas, so they agree to summation order: the largest deviation measured
 over all cases is 8.6e-10 for the gradients (per image: max-norm of the difference over max-norm of the reference's
 gradient), 4.5e-12 for the final state and 3.3e-14 for the Jacobian.  The gates are 100 x those: summation
-order cannot fail them, a formula error does (a wrong Huber branch moves a gradient by 1e-2)."""
+order cannot fail them, a formula error does (a wrong Huber branch moves a gradient by 1e-2).
+
+The frozen-column plans with a distortion model (tests/golden/lm_grad_frozen_reference.npz, written by
+tests/golden/make_golden_lm_grad_frozen.py: simple_radial with prior_focal, prior_gravity and both) run at the same gates:
+measured 2.7e-9, 7.7e-11 and 4.8e-11 for the gradients, 5.7e-12 for the final state."""
 import os
 
 import numpy as np
@@ -74,8 +78,37 @@ def test_fixture_holds_every_case(ref):
     assert case_names(ref) == sorted(ALL_CASES)
 
 
+# the frozen-column plans with a distortion model (tests/golden/make_golden_lm_grad_frozen.py): prior_focal is the reference's
+# overlap quirk -- without a free focal length the distortion takes the first gravity step
+FROZEN_CASES = ["prior_focal/simple_radial/huber", "prior_gravity/simple_radial/huber", "prior_focal_gravity/simple_radial/huber"]
+
+
+@pytest.fixture(scope="module")
+def ref_frozen():
+    return np.load(os.path.join(GOLDEN, "lm_grad_frozen_reference.npz"))
+
+
+def test_frozen_fixture_holds_every_case(ref_frozen):
+    assert case_names(ref_frozen) == sorted(FROZEN_CASES)
+    for name in FROZEN_CASES:
+        extra = name.split("/")[0]
+        priors = sorted(k.rsplit("/", 1)[1] for k in ref_frozen.files if k.startswith(f"{name}/in/prior_"))
+        assert priors == {"prior_focal": ["prior_focal"], "prior_gravity": ["prior_gravity"],
+                          "prior_focal_gravity": ["prior_focal", "prior_gravity"]}[extra], (name, priors)
+        assert ref_frozen[f"{name}/in/latitude_field"].shape == (3, 1, 12, 20) and int(ref_frozen[f"{name}/cfg"][0]) == 5
+
+
 @pytest.mark.parametrize("name", ALL_CASES)
 def test_unrolled_matches_reference_float64(ref, name):
+    unrolled_matches_reference_float64(ref, name)
+
+
+@pytest.mark.parametrize("name", FROZEN_CASES)
+def test_unrolled_matches_reference_float64_frozen_columns(ref_frozen, name):
+    unrolled_matches_reference_float64(ref_frozen, name)
+
+
+def unrolled_matches_reference_float64(ref, name):
     data = case_data(ref, name)
     out = lm_grad.lm_unrolled_torch(data, case_conf(ref, name), dtype=torch.float64)
     # the damping decisions: lambda went up exactly where the reference's new cost exceeded the previous one
