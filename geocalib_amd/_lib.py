@@ -154,6 +154,11 @@ _SIGNATURES = {
     "gclm_field_loss": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P,
                                   _P]),
     "gclm_field_loss_grad": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gclm_field_param_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gclm_field_loss_param_grad": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P,
+                                             C.c_size_t, _P, _P, _P]),
+    "gclm_perspective_fields_backward": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P, _P,
+                                                   _P]),
     "gclm_hypothesis_scores_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "gclm_hypothesis_scores": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_float,
                                          C.c_float, C.c_float, _P, C.c_size_t, _P, _P, _P]),

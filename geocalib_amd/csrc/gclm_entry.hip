@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the five render kernels, the field errors, the field losses and their gradients, the adjoint of the LM steps, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the five render kernels, the field errors, the field losses and their gradients (to the fields, and to the camera and gravity), the adjoint of the LM steps, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -433,6 +433,55 @@ int gclm_field_loss_grad(int camera_model, const float* d_cam, const float* d_gr
     if (!a.pass()) return -3;
     return launched(launch_field_loss_grad(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss,
                                            d_scale, d_grad_up, d_grad_lat, static_cast<hipStream_t>(stream)));
+}
+
+size_t gclm_field_param_grad_workspace(int B, int H, int W) { return field_param_grad_workspace(B, H, W); }
+
+int gclm_field_loss_param_grad(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                               const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
+                               const float* d_scale, void* d_workspace, size_t workspace_bytes, float* d_grad_cam,
+                               float* d_grad_grav, void* stream) {
+    if (!d_scale || !d_workspace || (!d_grad_cam && !d_grad_grav)) return -3;
+    if (!field_loss_plain_ok(camera_model, d_cam, d_grav, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss)) return -3;
+    const size_t ws_bytes = field_param_grad_workspace(B, H, W);                 // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_grad_cam, floats(B, 8), 4);
+    a.writes(d_grad_grav, floats(B, 3), 4);
+    a.writes(d_workspace, ws_bytes, 8);
+    a.reads(d_cam, floats(B, 8), 4);
+    a.reads(d_grav, floats(B, 3), 4);
+    a.reads(d_up, mul_sat(px, 2), 4);
+    a.reads(d_lat, px, 4);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    a.reads(d_scale, floats(B, 2), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_field_loss_param_grad(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, up_loss,
+                                                 lat_loss, d_scale, d_workspace, d_grad_cam, d_grad_grav,
+                                                 static_cast<hipStream_t>(stream)));
+}
+
+int gclm_perspective_fields_backward(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,
+                                     const float* d_grad_up, const float* d_grad_lat, void* d_workspace, size_t workspace_bytes,
+                                     float* d_grad_cam, float* d_grad_grav, void* stream) {
+    if (!d_cam || !d_grav || (!d_grad_up && !d_grad_lat) || !d_workspace || (!d_grad_cam && !d_grad_grav)) return -3;
+    if (!known_model(camera_model) || (normalize_up != 0 && normalize_up != 1)) return -3;
+    const size_t ws_bytes = field_param_grad_workspace(B, H, W);                 // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    ArgCheck a;
+    const size_t px = floats(B, H, W);
+    a.writes(d_grad_cam, floats(B, 8), 4);
+    a.writes(d_grad_grav, floats(B, 3), 4);
+    a.writes(d_workspace, ws_bytes, 8);
+    a.reads(d_cam, floats(B, 8), 4);
+    a.reads(d_grav, floats(B, 3), 4);
+    a.reads(d_grad_up, mul_sat(px, 2), 8);                                       // (pairs, as gclm_perspective_fields writes them)
+    a.reads(d_grad_lat, px, 4);
+    if (!a.pass()) return -3;
+    return launched(launch_perspective_fields_backward(camera_model, d_cam, d_grav, B, H, W, normalize_up, d_grad_up, d_grad_lat,
+                                                       d_workspace, d_grad_cam, d_grad_grav, static_cast<hipStream_t>(stream)));
 }
 
 size_t gclm_lm_backward_workspace(int B, int H, int W) { return lm_backward_workspace(B, H, W); }

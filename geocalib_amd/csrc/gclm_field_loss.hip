@@ -21,15 +21,14 @@
 // Gradient: the same walk with no reduction, no LDS, no barrier; plain stores (the planes are read next, by autograd).
 // The loss type is a kernel argument taken by a branch every lane of the grid takes alike, not a template parameter:
 // camera model x PX instantiations per kernel.  Pixels per lane by gclm_render.h's pixels_per_lane.  64-bit offsets.  No scratch.
-#include "gclm_render.h"
+// pixel_loss, pixel_grad and lane_row are gclm_field_loss.h's, shared with gclm_field_param_grad.hip.
+#include "gclm_field_loss.h"
 
 namespace gclm {
 namespace {
 
 constexpr int kLossWords = 4;                // float sums per record
 constexpr int kLossChains = 8;               // summation chains per image of the second launch
-constexpr float kCauchyC2 = 0.007f * 0.007f;
-constexpr float kHuberDelta = 0.017453292519943295f;          // deg2rad(1)
 
 struct FieldLossArgs {
     const float *cam, *grav, *up, *lat, *upc, *latc;
@@ -43,66 +42,6 @@ struct FieldLossGradArgs {
     int H, W, tiles_x, up_loss, lat_loss;
 };
 
-__device__ __forceinline__ float huber(float r) {
-    const float a = fabsf(r);
-    return a < kHuberDelta ? 0.5f * r * r : kHuberDelta * (a - 0.5f * kHuberDelta);      // (a NaN takes the second arm: NaN)
-}
-
-// l of one pixel: r and t hold its C components
-template <int C>
-__device__ __forceinline__ float pixel_loss(int type, const float (&r)[C], const float (&t)[C]) {
-    float s = 0.f;
-    switch (type) {
-        case GCLM_FIELD_LOSS_L1:
-#pragma unroll
-            for (int c = 0; c < C; ++c) s += fabsf(r[c]);
-            return s;
-        case GCLM_FIELD_LOSS_DOT:
-#pragma unroll
-            for (int c = 0; c < C; ++c) s += r[c] * t[c];
-            return 1.f - s;
-        case GCLM_FIELD_LOSS_HUBER:
-#pragma unroll
-            for (int c = 0; c < C; ++c) s += huber(r[c]);
-            return s;
-        default:
-#pragma unroll
-            for (int c = 0; c < C; ++c) s += r[c] * r[c];
-            return type == GCLM_FIELD_LOSS_L2 ? s : (0.5f * kCauchyC2) * log1pf(s / kCauchyC2);
-    }
-}
-
-// dl/dp_c of one pixel, into g
-template <int C>
-__device__ __forceinline__ void pixel_grad(int type, const float (&r)[C], const float (&t)[C], float (&g)[C]) {
-    switch (type) {
-        case GCLM_FIELD_LOSS_L1:
-#pragma unroll
-            for (int c = 0; c < C; ++c) g[c] = r[c] > 0.f ? 1.f : (r[c] < 0.f ? -1.f : (r[c] == 0.f ? 0.f : r[c]));
-            return;
-        case GCLM_FIELD_LOSS_L2:
-#pragma unroll
-            for (int c = 0; c < C; ++c) g[c] = 2.f * r[c];
-            return;
-        case GCLM_FIELD_LOSS_DOT:
-#pragma unroll
-            for (int c = 0; c < C; ++c) g[c] = -t[c];
-            return;
-        case GCLM_FIELD_LOSS_HUBER:
-#pragma unroll
-            for (int c = 0; c < C; ++c) g[c] = r[c] < -kHuberDelta ? -kHuberDelta : (r[c] > kHuberDelta ? kHuberDelta : r[c]);
-            return;
-        default: {
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) s += r[c] * r[c];
-            const float w = 1.f / (1.f + s / kCauchyC2);
-#pragma unroll
-            for (int c = 0; c < C; ++c) g[c] = r[c] * w;
-        }
-    }
-}
-
 // The gradient planes' stores: plain, since autograd reads the planes next.  A build with -DGCLM_FIELD_LOSS_NT_STORES=1 is the
 // measured alternative (scripts/field_loss_bench.py --variant-lib times such a build against this one).
 #ifndef GCLM_FIELD_LOSS_NT_STORES
@@ -110,18 +49,6 @@ __device__ __forceinline__ void pixel_grad(int type, const float (&r)[C], const 
 #endif
 
 constexpr bool kGradNT = GCLM_FIELD_LOSS_NT_STORES != 0;
-
-// The row's terms of this lane's pixels (x, y), and u, r2 of each of them.
-template <int PX>
-__device__ __forceinline__ PerspRow lane_row(const float* cam, const float* grav, int b, int x, int y, float (&u)[PX], float (&r2)[PX]) {
-    const PerspRow r = persp_row(cam + (size_t)b * 8, grav + (size_t)b * 3, y);
-#pragma unroll
-    for (int j = 0; j < PX; ++j) {
-        u[j] = ((float)(x + j) - r.cx) * r.ifx;
-        r2[j] = u[j] * u[j] + r.v2;
-    }
-    return r;
-}
 
 template <int MODEL, int PX>
 __global__ __launch_bounds__(kBlock) void field_loss_kernel(const FieldLossArgs a) {

@@ -280,6 +280,17 @@ hipError_t launch_field_loss_grad(int camera_model, const float* cam, const floa
                                   const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss, const float* scale,
                                   float* grad_up /* or nullptr */, float* grad_lat /* or nullptr */, hipStream_t s);
 
+// gclm_field_param_grad.hip
+size_t field_param_grad_workspace(int B, int H, int W);                   // bytes of one call's tile records; 0: sizes out of range
+hipError_t launch_field_loss_param_grad(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,
+                                        const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss,
+                                        const float* scale, void* workspace, float* grad_cam /* or nullptr */,
+                                        float* grad_grav /* or nullptr */, hipStream_t s);
+hipError_t launch_perspective_fields_backward(int camera_model, const float* cam, const float* grav, int B, int H, int W, int normalize,
+                                              const float* grad_up /* or nullptr */, const float* grad_lat /* or nullptr */,
+                                              void* workspace, float* grad_cam /* or nullptr */, float* grad_grav /* or nullptr */,
+                                              hipStream_t s);
+
 // gclm_lm_grad.hip
 size_t lm_backward_workspace(int B, int H, int W);                        // bytes of one call's workspace; 0: sizes out of range
 hipError_t launch_lm_backward(int camera_model, const float* up, const float* lat, const float* upc, const float* latc, int B, int H,

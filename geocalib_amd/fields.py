@@ -384,7 +384,7 @@ def perspective_fields(camera_model: str, cam: torch.Tensor, grav: torch.Tensor,
     """gclm_perspective_fields: the up field (B, H, W, 2) and the latitude field (B, H, W, 1) of `size` = (H, W) for cameras
     `cam` (B, 8) and gravities `grav` (B, 3), float32 on one HIP device, in one launch per 65 535 images on torch's current
     stream.  A field not asked for is returned as None.  get_perspective_field and friends are the public entries; not
-    differentiable.  simple_divisional's distort scale and its derivative take the forms that do not cancel in float32
+    differentiable here (their calibration_grad=True wraps this call and perspective_fields_backward in a Function).  simple_divisional's distort scale and its derivative take the forms that do not cancel in float32
     (include/gclm.h), where the torch composition keeps the reference's."""
     assert up or latitude, "at least one of up or latitude must be True"
     if not (cam.dtype == grav.dtype == torch.float32 and grav.device == cam.device):
@@ -514,6 +514,73 @@ def field_loss_grad(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, sc
                    *(_call.ptr_at(t, b0) for t in planes.values()), *ids, scale[b0].data_ptr(), _call.ptr_at(g_up, b0),
                    _call.ptr_at(g_lat, b0), _call.raw_stream(dev), device=dev)
     return g_up, g_lat
+
+
+def _param_grad_outputs(cam: torch.Tensor, B: int, want_cam: bool, want_grav: bool):
+    if not (want_cam or want_grav):
+        raise ValueError("at least one of the camera and gravity gradients must be asked for")
+    return (cam.new_empty((B, 8)) if want_cam else None), (cam.new_empty((B, 3)) if want_grav else None)
+
+
+def _param_grad_workspace(B: int, H: int, W: int, dev):
+    ws_bytes = int(_lib.load().gclm_field_param_grad_workspace(min(B, _call.MAX_CALL), H, W))
+    return torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev), ws_bytes
+
+
+def field_loss_param_grad(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, scale: torch.Tensor,
+                          up: Optional[torch.Tensor] = None, lat: Optional[torch.Tensor] = None,
+                          up_conf: Optional[torch.Tensor] = None, lat_conf: Optional[torch.Tensor] = None, up_loss: str = "l1",
+                          lat_loss: str = "l1", want_cam: bool = True, want_grav: bool = True):
+    """gclm_field_loss_param_grad: the gradients of field_loss's two losses with respect to the calibration, (grad_cam (B, 8),
+    grad_grav (B, 3)), None for the one not asked for: the inputs and `scale` (B, 2) of field_loss_grad, the target evaluated
+    again in registers and its cotangent pulled back to the camera row (columns w, h zero) and the gravity as stored; two
+    launches per 65 535 images on torch's current stream.  An image's gradients do not depend on which of the two is asked for."""
+    cam, grav, planes, B, H, W, ids = _loss_call("field_loss_param_grad", cam, grav, up, lat, up_conf, lat_conf, up_loss, lat_loss)
+    dev = cam.device
+    scale = _call.dev_f32(scale, "scale")
+    if scale.shape != (B, 2) or scale.device != dev:
+        raise ValueError(f"`scale` {tuple(scale.shape)} on {scale.device} must be ({B}, 2) on {dev}")
+    g_cam, g_grav = _param_grad_outputs(cam, B, want_cam, want_grav)
+    if B * H * W == 0:
+        return (None if g_cam is None else g_cam.zero_()), (None if g_grav is None else g_grav.zero_())
+    ws, ws_bytes = _param_grad_workspace(B, H, W, dev)
+    for b0, n in _call.slices(B):
+        _call.call("gclm_field_loss_param_grad", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, H, W,
+                   *(_call.ptr_at(t, b0) for t in planes.values()), *ids, scale[b0].data_ptr(), ws.data_ptr(), ws_bytes,
+                   _call.ptr_at(g_cam, b0), _call.ptr_at(g_grav, b0), _call.raw_stream(dev), device=dev)
+    return g_cam, g_grav
+
+
+def perspective_fields_backward(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, grad_up: Optional[torch.Tensor] = None,
+                                grad_lat: Optional[torch.Tensor] = None, normalize: bool = True, want_cam: bool = True,
+                                want_grav: bool = True):
+    """gclm_perspective_fields_backward: the cotangents of perspective_fields' outputs, `grad_up` (B, H, W, 2) / `grad_lat`
+    (B, H, W, 1) or (B, H, W) (one may be None), pulled back to the cameras `cam` (B, 8) and gravities `grav` (B, 3) they were
+    rendered at: (grad_cam (B, 8), grad_grav (B, 3)), None for the one not asked for.  float32 on one HIP device; two launches
+    per 65 535 images on torch's current stream."""
+    if grad_up is None and grad_lat is None:
+        raise ValueError("at least one of the up and latitude cotangents is needed")
+    cam, grav = _call.dev_f32(cam, "cam").reshape(-1, 8), _call.dev_f32(grav, "grav").reshape(-1, 3)
+    dev, B = cam.device, cam.shape[0]
+    if grav.shape[0] != B or grav.device != dev:
+        raise ValueError(f"camera batch {B} and gravity batch {grav.shape[0]} must be equal and on one device")
+    grad_up = None if grad_up is None else _call.dev_f32(grad_up, "grad_up")
+    grad_lat = None if grad_lat is None else _call.dev_f32(grad_lat, "grad_lat")
+    if grad_up is not None and (grad_up.dim() != 4 or grad_up.shape[0] != B or grad_up.shape[3] != 2 or grad_up.device != dev):
+        raise ValueError(f"`grad_up` {tuple(grad_up.shape)} on {grad_up.device} must be ({B}, H, W, 2) on {dev}")
+    H, W = (grad_up.shape[1:3] if grad_up is not None else grad_lat.shape[1:3])
+    if grad_lat is not None and (grad_lat.dim() not in (3, 4) or grad_lat.numel() != B * H * W or grad_lat.shape[:3] != (B, H, W)
+                                 or grad_lat.device != dev):
+        raise ValueError(f"`grad_lat` {tuple(grad_lat.shape)} on {grad_lat.device} must be ({B}, {H}, {W}[, 1]) on {dev}")
+    g_cam, g_grav = _param_grad_outputs(cam, B, want_cam, want_grav)
+    if B * H * W == 0:
+        return (None if g_cam is None else g_cam.zero_()), (None if g_grav is None else g_grav.zero_())
+    ws, ws_bytes = _param_grad_workspace(B, H, W, dev)
+    for b0, n in _call.slices(B):
+        _call.call("gclm_perspective_fields_backward", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n,
+                   H, W, int(normalize), _call.ptr_at(grad_up, b0), _call.ptr_at(grad_lat, b0), ws.data_ptr(), ws_bytes,
+                   _call.ptr_at(g_cam, b0), _call.ptr_at(g_grav, b0), _call.raw_stream(dev), device=dev)
+    return g_cam, g_grav
 
 
 HYPOTHESIS_CHUNK = _lib.HYPOTHESIS_CHUNK     # K: hypotheses scored per read of an image's planes (GCLM_HYPOTHESIS_CHUNK)

@@ -11,6 +11,10 @@ grad a torch.autograd.Function hands autograd the gradient of a second such pass
 is rendered, nothing but the inputs is kept for backward.  That path is differentiable with respect to the predicted fields
 only, once; the confidences are detached, as in the reference.  Anything else (CPU, float64, half-precision predictions, a
 camera or gravity that requires grad) renders the target with get_perspective_field and runs `field_loss`.
+`calibration_grad=True` keeps a float32 HIP camera or gravity that requires grad on the HIP path: backward then also returns
+the gradients to `camera._data` (B, 8) and `gravity._data` (B, 3), from one pass that evaluates the target again and pulls
+its cotangent back to the calibration (gclm_field_loss_param_grad), once differentiable.  Off by default: every default
+route is as it was.
 
 The two paths differ where arithmetic leaves no choice: the l1 gradient of a NaN residual is NaN on the HIP path and 0 in
 torch (torch's sgn), and the HIP path takes the cauchy loss as log1p, which keeps small residuals the float32 log(1 + x)
@@ -85,21 +89,25 @@ class _FieldLossFunction(torch.autograd.Function):
         up, lat, up_conf, lat_conf = (saved.pop(0) if g else None for g in ctx.given)
         cam, grav, den = saved
         model, up_loss, lat_loss, up_weight, lat_weight = ctx.call
-        if not ctx.needs_input_grad[0]:              # a field that asks for no gradient is left out of the pass
-            up = up_conf = None
-        if not ctx.needs_input_grad[1]:
-            lat = lat_conf = None
+        want_up, want_lat, want_cam, want_grav = (ctx.needs_input_grad[i] for i in (0, 1, 3, 4))
         # grad_output x weight / denominator, on the device; an absent field's column is never read
         scale = grad_out.to(torch.float32) / den
         scale[:, 0] *= up_weight
         scale[:, 1] *= lat_weight
-        g_up, g_lat = fields.field_loss_grad(model, cam, grav, scale, up, lat, up_conf, lat_conf, up_loss, lat_loss)
-        return (g_up, g_lat) + (None,) * 9
+        g_up = g_lat = g_cam = g_grav = None
+        f_up, f_upc = (up, up_conf) if want_up else (None, None)      # a field that asks for no gradient is left out of the pass
+        f_lat, f_latc = (lat, lat_conf) if want_lat else (None, None)
+        if f_up is not None or f_lat is not None:
+            g_up, g_lat = fields.field_loss_grad(model, cam, grav, scale, f_up, f_lat, f_upc, f_latc, up_loss, lat_loss)
+        if want_cam or want_grav:                    # (calibration_grad: the same targets' cotangent pulled back to the calibration)
+            g_cam, g_grav = fields.field_loss_param_grad(model, cam, grav, scale, up, lat, up_conf, lat_conf, up_loss, lat_loss,
+                                                         want_cam=want_cam, want_grav=want_grav)
+        return (g_up, g_lat, None, g_cam, g_grav) + (None,) * 6
 
 
 def _hip_path(tensors, cam: torch.Tensor, grav: torch.Tensor) -> bool:
     """Whether these inputs take gclm_field_loss: all float32 on one HIP device, matching batches, camera and gravity without
-    grad (the fields may require it)."""
+    grad (the fields may require it; `calibration_grad` asks with the detached camera and gravity)."""
     dev = cam.device
     return (all(t.is_cuda and t.dtype == torch.float32 and t.device == dev for t in list(tensors) + [cam, grav])
             and not (cam.requires_grad or grav.requires_grad) and cam.dim() == grav.dim() == 2 and cam.shape[0] == grav.shape[0]
@@ -118,7 +126,7 @@ def _field_loss_torch(pred, camera, gravity, types, use_uncertainty_loss):
 
 def perspective_field_loss(pred: Dict[str, torch.Tensor], camera: BaseCamera, gravity: Gravity, up_loss: str = "l1",
                            latitude_loss: str = "l1", use_uncertainty_loss: bool = True, up_loss_weight: float = 1.0,
-                           latitude_loss_weight: float = 1.0) -> Dict[str, torch.Tensor]:
+                           latitude_loss_weight: float = 1.0, calibration_grad: bool = False) -> Dict[str, torch.Tensor]:
     """The decoders' losses of the fields in `pred` against the calibration (camera, gravity), per image.
 
     `pred` is the dict LMOptimizer and metrics.perspective_field_metrics take: "up_field" (B, 2, H, W), "latitude_field"
@@ -129,8 +137,11 @@ def perspective_field_loss(pred: Dict[str, torch.Tensor], camera: BaseCamera, gr
     `use_uncertainty_loss`; sum conf = 0 gives NaN.
 
     float32 HIP fields with a camera and gravity that do not require grad take the HIP path (module docstring), also when a
-    field requires grad; anything else the torch composition.  Raises ValueError for an unknown loss type and for 'dot' on
-    the latitude, on both paths."""
+    field requires grad; anything else the torch composition.  `calibration_grad=True` keeps float32 HIP inputs on the HIP path
+    also when `camera._data` or `gravity._data` require grad: the forward is the same pass, bit for bit, and backward hands
+    autograd their gradients from one more pass (gclm_field_loss_param_grad) -- the loss of an optimised calibration, e.g. the
+    differentiable LMOptimizer's out["camera"], out["gravity"], stays on the HIP path.  Raises ValueError for an unknown loss
+    type and for 'dot' on the latitude, on both paths."""
     if "up_field" not in pred and "latitude_field" not in pred:
         raise ValueError("`pred` holds neither up_field nor latitude_field")
     types = {"up": up_loss, "latitude": latitude_loss}
@@ -147,7 +158,8 @@ def perspective_field_loss(pred: Dict[str, torch.Tensor], camera: BaseCamera, gr
             pred[f"{name}_confidence"] = conf.reshape(conf.shape[0], *conf.shape[-2:])
     given = [pred[k] for f in ("up", "latitude") for k in (f"{f}_field", f"{f}_confidence") if k in pred]
     cam, grav = camera._data, gravity._data
-    if _hip_path(given, cam, grav):
+    # (calibration_grad: the question is put for the detached calibration, so that one that requires grad stays on the HIP path)
+    if _hip_path(given, *((cam.detach(), grav.detach()) if calibration_grad else (cam, grav))):
         confs = [pred.get(f"{f}_confidence") if use_uncertainty_loss else None for f in ("up", "latitude")]
         both = _FieldLossFunction.apply(pred.get("up_field"), pred.get("latitude_field"), camera.name(), cam, grav,
                                         *(None if c is None else c.detach() for c in confs), up_loss, latitude_loss,

@@ -7,7 +7,10 @@ call this module -- residuals and Jacobians are evaluated per pixel in csrc/gclm
 
 float32 cameras and gravities on one HIP device that do not require grad render through the HIP extension
 (gclm_perspective_fields: both fields in one launch); anything else (CPU, float64, autograd) runs the torch composition,
-which stays the differentiable path.  The one deliberate difference: the HIP path evaluates simple_divisional's distort
+which stays the default differentiable path.  `calibration_grad=True` keeps a float32 HIP calibration that requires grad on
+the HIP path: the forward is the same launch inside a torch.autograd.Function that saves only the camera and gravity data,
+the backward one pass that pulls the fields' cotangents back to them (gclm_perspective_fields_backward), once
+differentiable.  The one deliberate difference: the HIP path evaluates simple_divisional's distort
 scale and its derivative in forms that do not cancel in float32 (held to float64), the torch path keeps the reference's
 float32 forms, which do (1.3 % off at |k1 r2| = 1e-6).
 
@@ -18,6 +21,8 @@ from typing import Tuple
 
 import torch
 from torch.nn import functional as F
+
+from torch.autograd.function import once_differentiable
 
 from . import _call, _lib, fields
 from .camera import BaseCamera
@@ -44,16 +49,49 @@ def get_horizon_line(camera: BaseCamera, gravity: Gravity, relative: bool = True
     return ends / camera.size[0, 1] if relative else ends
 
 
-def _on_hip(camera: BaseCamera, gravity: Gravity) -> bool:
+def _on_hip(camera: BaseCamera, gravity: Gravity, calibration_grad: bool = False) -> bool:
     """Whether these batched inputs take gclm_perspective_fields: float32 (B, 8) / (B, 3) data on one HIP device, the
-    batches equal, no grad."""
+    batches equal, no grad -- or with it, where `calibration_grad` asks for the HIP backward."""
     cam, grav = camera._data, gravity._data
     return (cam.is_cuda and cam.dtype == grav.dtype == torch.float32 and grav.device == cam.device and
-            not (cam.requires_grad or grav.requires_grad) and cam.dim() == grav.dim() == 2 and cam.shape[0] == grav.shape[0])
+            (calibration_grad or not (cam.requires_grad or grav.requires_grad)) and cam.dim() == grav.dim() == 2 and
+            cam.shape[0] == grav.shape[0])
+
+
+class _PerspectiveFieldsFunction(torch.autograd.Function):
+    """(cam (B, 8), grav (B, 3)) -> the fields of fields.perspective_fields asked for, gradients by
+    fields.perspective_fields_backward."""
+
+    @staticmethod
+    def forward(ctx, cam, grav, model, size, up, latitude, normalize):
+        out = fields.perspective_fields(model, cam, grav, size, up, latitude, normalize)
+        ctx.set_materialize_grads(False)         # a field nobody used gets no cotangent plane: the pass leaves it out
+        ctx.save_for_backward(cam, grav)
+        ctx.call = (model, up, latitude, normalize)
+        return tuple(t for t in out if t is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        cam, grav = ctx.saved_tensors
+        model, up, latitude, normalize = ctx.call
+        grads = list(grads)
+        g_up = grads.pop(0) if up else None
+        g_lat = grads.pop(0) if latitude else None
+        want_cam, want_grav = ctx.needs_input_grad[:2]
+        if (g_up is None and g_lat is None) or not (want_cam or want_grav):
+            return (None,) * 7
+        # cotangents as the renderer lays its outputs out: contiguous (B, H, W, 2) and (B, H, W, 1)
+        g_cam, g_grav = fields.perspective_fields_backward(model, cam, grav, g_up, g_lat, normalize, want_cam, want_grav)
+        return (g_cam, g_grav) + (None,) * 5
 
 
 def _hip_fields(camera: BaseCamera, gravity: Gravity, h: int, w: int, up: bool, latitude: bool, normalize: bool = True):
-    return fields.perspective_fields(camera.name(), camera._data, gravity._data, (h, w), up, latitude, normalize)
+    cam, grav = camera._data, gravity._data
+    if torch.is_grad_enabled() and (cam.requires_grad or grav.requires_grad):     # (only with calibration_grad: _on_hip)
+        out = list(_PerspectiveFieldsFunction.apply(cam, grav, camera.name(), (h, w), up, latitude, normalize))
+        return (out.pop(0) if up else None), (out.pop(0) if latitude else None)
+    return fields.perspective_fields(camera.name(), cam, grav, (h, w), up, latitude, normalize)
 
 
 def _up_field_torch(camera: BaseCamera, gravity: Gravity, h: int, w: int, normalize: bool) -> torch.Tensor:
@@ -76,33 +114,37 @@ def _latitude_field_torch(camera: BaseCamera, gravity: Gravity, h: int, w: int) 
     return torch.asin(s.clamp(min=-1 + eps, max=1 - eps)).reshape(camera.shape[0], h, w, 1)
 
 
-def get_up_field(camera: BaseCamera, gravity: Gravity, normalize: bool = True) -> torch.Tensor:
+def get_up_field(camera: BaseCamera, gravity: Gravity, normalize: bool = True, calibration_grad: bool = False) -> torch.Tensor:
     """Projected up direction per pixel, (..., h, w, 2): p = (a, b) - c (u, v), pushed through the
     distortion differential  s p + (ds/duv . ... ) i.e. q = s p + (off . uv-weighted p).
-    float32 device inputs without grad: one HIP launch, contiguous (B, h, w, 2) (module docstring)."""
+    float32 device inputs without grad: one HIP launch, contiguous (B, h, w, 2) (module docstring); with grad too where
+    `calibration_grad` is set, the gradient then from one HIP pass."""
     camera, gravity, h, w = _batched(camera, gravity)
-    if _on_hip(camera, gravity):
+    if _on_hip(camera, gravity, calibration_grad):
         return _hip_fields(camera, gravity, h, w, True, False, normalize)[0]
     return _up_field_torch(camera, gravity, h, w, normalize)
 
 
-def get_latitude_field(camera: BaseCamera, gravity: Gravity) -> torch.Tensor:
+def get_latitude_field(camera: BaseCamera, gravity: Gravity, calibration_grad: bool = False) -> torch.Tensor:
     """Latitude (radians) of every pixel's viewing ray wrt the gravity direction, (..., h, w, 1).
-    float32 device inputs without grad: one HIP launch, contiguous (B, h, w, 1) (module docstring)."""
+    float32 device inputs without grad: one HIP launch, contiguous (B, h, w, 1) (module docstring); with grad too where
+    `calibration_grad` is set, the gradient then from one HIP pass."""
     camera, gravity, h, w = _batched(camera, gravity)
-    if _on_hip(camera, gravity):
+    if _on_hip(camera, gravity, calibration_grad):
         return _hip_fields(camera, gravity, h, w, False, True)[1]
     return _latitude_field_torch(camera, gravity, h, w)
 
 
-def get_perspective_field(camera: BaseCamera, gravity: Gravity, use_up: bool = True,
-                          use_latitude: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+def get_perspective_field(camera: BaseCamera, gravity: Gravity, use_up: bool = True, use_latitude: bool = True,
+                          calibration_grad: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(up (..., 2, h, w), latitude (..., 1, h, w)); a disabled field is returned as zeros.
-    float32 device inputs without grad: both fields from ONE HIP launch, the same views as the torch path's."""
+    float32 device inputs without grad: both fields from ONE HIP launch, the same views as the torch path's.
+    `calibration_grad=True`: a float32 HIP calibration that requires grad takes the same launch, and backward is one HIP pass
+    (gclm_perspective_fields_backward) whose gradients land on `camera._data` and `gravity._data`."""
     assert use_up or use_latitude, "At least one of use_up or use_latitude must be True."
     camera, gravity, h, w = _batched(camera, gravity)
     B = camera.shape[0]
-    if _on_hip(camera, gravity):
+    if _on_hip(camera, gravity, calibration_grad):
         up, lat = _hip_fields(camera, gravity, h, w, use_up, use_latitude)
     else:
         up = _up_field_torch(camera, gravity, h, w, True) if use_up else None

@@ -62,7 +62,9 @@ extern "C" {
  * solve with a step record, and the adjoint of its LM steps -- the gradients of the optimised camera and gravity with respect
  * to the fields and the confidences;
  * gclm_pack_fields_typed and gclm_pack_fields_backward added, also within 610: the head epilogue for float16 / bfloat16 raw
- * planes, and its backward -- the gradients of the fields and confidences taken back to the raw head outputs in one pass).
+ * planes, and its backward -- the gradients of the fields and confidences taken back to the raw head outputs in one pass;
+ * gclm_field_loss_param_grad, gclm_perspective_fields_backward and gclm_field_param_grad_workspace added, also within 610: the
+ * gradients of the field losses, and of the rendered fields, with respect to the camera and the gravity).
  * gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
@@ -669,7 +671,8 @@ int gclm_field_errors(int camera_model, const float* d_cam, const float* d_grav,
  *   grad = d_scale[b, field] * dl/dp_c * (conf where that confidence is given),
  * d_scale (B, 2) = [up, latitude] in device memory, which the caller forms as grad_output * weight / denominator from d_out.
  * A NaN residual gives a NaN gradient at that pixel only (dot: -t_c does not depend on p); a NaN or zero-denominator scale
- * reaches every pixel of its image and field.  There is no gradient to the confidences, the camera or the gravity.
+ * reaches every pixel of its image and field.  There is no gradient to the confidences; gclm_field_loss_param_grad, below, has
+ * the gradients to the camera and the gravity.
  * Both return -3 (before any HIP call) for whatever gclm_field_errors refuses among the arguments they share (NULL d_cam or
  * d_grav, both fields NULL, a confidence given for a NULL field, B outside 1..65535, H or W < 1, H * W > 2^31 - 1 or a tile
  * grid over 2^32 threads, a camera_model outside 0..3), a loss id outside 0..4, GCLM_FIELD_LOSS_DOT for the latitude, a
@@ -692,6 +695,63 @@ int gclm_field_loss(int camera_model, const float* d_cam, const float* d_grav, i
 int gclm_field_loss_grad(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
                          const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
                          const float* d_scale, float* d_grad_up, float* d_grad_lat, void* stream);
+
+/*
+ * The gradients of the same losses -- or of any function of the fields gclm_perspective_fields renders -- with respect to
+ * the camera and the gravity the target fields are taken at, per image, in one pass over the planes and one small launch:
+ * what the reference gets from autograd through get_perspective_field, with both fields rendered to memory and a dozen
+ * eager kernels replayed backwards.  Per pixel the target t = (t_ux, t_uy, t_lat) is evaluated in registers by the renderer's
+ * formulas in float64 from the float32 camera and gravity (a float32 target's rounding is 1e-5 of a typical residual and
+ * would be the gradient's largest error), its cotangent g = (g_ux, g_uy, g_lat) is
+ * formed, and g is pulled back in float64 to the entries the formulas of gclm_perspective_fields read -- gravity (a, b, c)
+ * and camera fx, fy, cx, cy, k1, k2:
+ *   up:   normalize: q-bar = (g - t (t . g)) / |q|  (|q| < 1e-12: q-bar = g / 1e-12, F.normalize's constant norm);  else q-bar = g
+ *         q = s p + o (u, v), o = 2 s' D, D = u p_x + v p_y:   s-bar = q-bar . p,  o-bar = q-bar . (u, v),  s'-bar = 2 D o-bar,
+ *         D-bar = 2 s' o-bar,  p-bar = s q-bar + D-bar (u, v),  (u, v)-bar = o q-bar + D-bar p
+ *         p = (a - c u, b - c v):   a-bar += p-bar_x,  b-bar += p-bar_y,  c-bar -= p-bar . (u, v),  (u, v)-bar -= c p-bar
+ *   lat:  inside the clamp  sl-bar = g_lat / sqrt(1 - sl^2),  beyond it 0;   sl = (X a + Y b + c) / N, N = |(X, Y, 1)|:
+ *         a-bar += sl-bar X / N,  b-bar += sl-bar Y / N,  c-bar += sl-bar / N,  (X, Y)-bar = sl-bar ((a, b) - sl (X, Y) / N) / N
+ *         (X, Y) = t (u, v):   (u, v)-bar += t (X, Y)-bar,  t-bar = (X, Y)-bar . (u, v)
+ *   scales:  r2-bar = s-bar ds/dr2 + s'-bar ds'/dr2 + t-bar dt/dr2,  k-bar = s-bar ds/dk + s'-bar ds'/dk + t-bar dt/dk, with the
+ *         partial derivatives of the forms above (simple_divisional, E = sqrt(tau) (1 + sqrt(tau))^2:  ds/dk1 = 4 r2 / E,
+ *         ds'/dk1 = 4 / E + 16 k1 r2 E_tau / E^2,  ds'/dr2 = 16 k1^2 E_tau / E^2,  E_tau = (1 + sqrt(tau)) (1 + 3 sqrt(tau)) /
+ *         (2 sqrt(tau));  dt/dk1 = -r2 t^2,  dt/dr2 = -k1 t^2;  at k1 r2 = 0: s = 1, s' = 0 are constants)
+ *         r2 = u^2 + v^2:   (u, v)-bar += 2 r2-bar (u, v)
+ *   u = (x - cx) / fx:   fx-bar = -u-bar u / fx,  cx-bar = -u-bar / fx,  and likewise fy, cy from v-bar.
+ * The derivative is that of the branch the renderer takes, its conditions constants.  The conditions of the distort and
+ * undistort scales (tau, k1 r2 = 0, a zero denominator) are evaluated on the renderer's own float32 u, r2; every other one --
+ * the latitude's clamp, the 1e-12 norm floor, huber's delta, l1's sign -- on the float64 values, while gclm_field_loss decides
+ * them on its float32 target: for a value within about 1e-7 of a branch point the gradient's branch can differ from the
+ * forward's.  A lane sums its pixels in float64 (the
+ * terms of a parameter cancel across the image); every workgroup leaves one record of nine float64 sums in d_workspace, of
+ * at least gclm_field_param_grad_workspace(B, H, W) bytes (0 for sizes the calls refuse), 8-byte aligned; the second launch
+ * sums each image's records in a fixed order.  No atomics, no memset: results are bit-identical from call to call, do not
+ * depend on the other images of the batch nor on which of the two outputs is asked for (they depend on the image, H, W and
+ * the pixels per lane: two where W is even and every plane is 8-byte aligned, the interleaved up cotangent 16-byte; one
+ * otherwise).
+ * Outputs: d_grad_cam (B, 8) in the layout of d_cam -- columns w, h are written as 0, k2's column is 0 for the
+ * one-parameter models and both distortion columns for pinhole -- and d_grad_grav (B, 3); either may be NULL, not both.
+ * gclm_field_loss_param_grad: the cotangent comes from the loss,  g_c = d_scale[b, field] * conf * dl/dt_c  with the planes,
+ *   loss ids and d_scale of gclm_field_loss_grad (normalize_up = 1);  dl/dt_c = -dl/dp_c for l1, l2, cauchy and huber;  for dot,
+ *   l = 1 - sum_c (p_c - t_c) t_c, so dl/dt_c = 2 t_c - p_c.  The confidence normalisation is detached, as in the forward.
+ * gclm_perspective_fields_backward: the cotangent is read from planes in the layout gclm_perspective_fields writes, d_grad_up
+ *   (B, H, W, 2) interleaved and d_grad_lat (B, H, W); either may be NULL, not both.
+ * Both return -3 (before any HIP call) for a NULL d_cam, d_grav or d_workspace, both outputs NULL, B outside 1..65535, H or
+ * W < 1, H * W > 2^31 - 1 or a tile grid over 2^32 threads, a camera_model outside 0..3, a workspace that is too small or not
+ * 8-byte aligned, a pointer that is not 4-byte aligned, and an output or the workspace overlapping an input or each other;
+ * gclm_field_loss_param_grad also for whatever gclm_field_loss_grad refuses among the arguments they share (both fields NULL,
+ * a confidence given for a NULL field, a loss id outside 0..4, GCLM_FIELD_LOSS_DOT for the latitude, a NULL d_scale);
+ * gclm_perspective_fields_backward also for both cotangent planes NULL, normalize_up not 0 or 1 and a d_grad_up that is not
+ * 8-byte aligned.  -10 if a launch fails.  Asynchronous on `stream`; no allocation.
+ */
+size_t gclm_field_param_grad_workspace(int B, int H, int W);
+int gclm_field_loss_param_grad(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
+                               const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
+                               const float* d_scale, void* d_workspace, size_t workspace_bytes, float* d_grad_cam,
+                               float* d_grad_grav, void* stream);
+int gclm_perspective_fields_backward(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, int normalize_up,
+                                     const float* d_grad_up, const float* d_grad_lat, void* d_workspace, size_t workspace_bytes,
+                                     float* d_grad_cam, float* d_grad_grav, void* stream);
 
 /*
  * Which of N candidate calibrations per image fits the image's predicted perspective fields best, in one pass over the
