@@ -522,6 +522,7 @@ int run_solve(gclm_handle* h, const Fields& f, int B, int H, int W, const InitAr
     if (d_record && h->cfg.shared_intrinsics) return fail(h, -3, "the step record is kept for per-image solves only");
     if (B > 0 && (!d_cam_out || !d_grav_out || !d_info_out)) return fail(h, -3, "null output pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
+    h->sh.active = false;       // any solve ends a split session, also the empty one, which plans nothing (make_plan does it for the others)
     if (B == 0) return solve_empty_shard(h, H, W, ia, s);
     DeviceGuard guard(h->device);
     GCLM_HIP(h, guard.status);
@@ -940,6 +941,7 @@ int gclm_system(gclm_handle* h, const float* d_up, const float* d_lat, const flo
     if (!h) return -1;
     if (int rc = check_shapes(h, d_lat, B, H, W)) return rc;
     if (!d_cam || !d_grav || !d_cost || !d_grad || !d_hess) return fail(h, -3, "gclm_system: null pointer");
+    h->sh.active = false;       // (as run_solve: also the empty call ends a split session)
     if (B == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard guard(h->device);

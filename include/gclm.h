@@ -156,7 +156,9 @@ int gclm_default_config(gclm_config* cfg);
 int gclm_create(gclm_handle** out, const gclm_config* cfg);
 
 /* Re-configure (set_camera_model :173, .shared_intrinsics, priors) without dropping the workspace.  The device of a
- * handle cannot change. */
+ * handle cannot change.  A call after gclm_configure returns what the same call returns on a handle freshly created with
+ * that configuration and the same knobs, bit for bit, whatever the handle did before (tests/test_handle_reuse.py); a split
+ * session that was open is over. */
 int gclm_configure(gclm_handle* h, const gclm_config* cfg);
 
 int gclm_destroy(gclm_handle* h);

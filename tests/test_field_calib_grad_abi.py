@@ -376,3 +376,22 @@ def test_refused_calls_leave_their_outputs_untouched(dev):
         assert torch.all(buf == canary), k
     assert _loss_call(a) == 0 and _planes_call(a) == 0          # ... and the unchanged arguments are accepted
     torch.cuda.synchronize()
+
+
+def _wrapper_call(which, H, W, dev):
+    t = gate.inputs("simple_radial", H, W, device=dev)
+    if which == "loss":
+        scale = torch.tensor([[0.25, -1.5]], device=dev).repeat(gate.B, 1)
+        return lambda: fields.field_loss_param_grad("simple_radial", t["cam"], t["grav"], scale, t["up"], t["lat"], t["upc"], t["latc"],
+                                                    "l1", "huber")
+    return lambda: fields.perspective_fields_backward("simple_radial", t["cam"], t["grav"], t["gup"], t["glat"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["loss", "planes"])
+def test_results_do_not_depend_on_what_the_workspace_held(monkeypatch, dev, which):
+    """gclm_field_loss_param_grad / gclm_perspective_fields_backward on the fixture's 6 x 260 set (five tile columns, the last
+    four pixels wide; two tile rows, the last of two rows) with the wrapper's torch.empty workspace holding 0x00 bytes, 0xFF
+    bytes, and the records of a call at 67 x 65: the same bits."""
+    from workspace_fill import same_bits_whatever_the_memory_held
+    same_bits_whatever_the_memory_held(monkeypatch, dev, _wrapper_call(which, 6, 260, dev), _wrapper_call(which, 67, 65, dev))

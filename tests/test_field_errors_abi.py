@@ -284,3 +284,20 @@ def test_field_error_kernels_carry_no_scratch(tmp_path):
     print({n: v for n, v in k.items()})
     assert all(v["scratch"] == 0 for v in k.values()), k
     assert all(v["vgpr"] <= 64 and v["lds"] <= 2048 for v in k.values()), k
+
+
+# ------------------------------------------------------------------ the caller's workspace
+def _device_call(case, dev):
+    cams, gravs, data = fg.make_case(case)
+    args = [t.to(dev) for t in (cams, gravs, *(data[k] for k in ("up_field", "latitude_field", "up_confidence", "latitude_confidence")))]
+    return lambda: fields.field_errors(case[0], *args, thresholds=fg.THRESHOLDS, return_errors=True)
+
+
+@pytest.mark.gpu
+def test_results_do_not_depend_on_what_the_workspace_held(monkeypatch):
+    """gclm_field_errors at 30 x 200 (tile columns and rows both ragged) with the wrapper's torch.empty workspace holding 0x00
+    bytes, 0xFF bytes, and the records of a call at 3 x 37 x 53: the same bits."""
+    from workspace_fill import same_bits_whatever_the_memory_held
+    dev = torch.device("cuda:0")
+    same_bits_whatever_the_memory_held(monkeypatch, dev, _device_call(("simple_radial", 2, 30, 200, "random", False), dev),
+                                       _device_call(("simple_radial", 3, 37, 53, "random", False), dev))

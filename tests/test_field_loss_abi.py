@@ -378,3 +378,26 @@ def test_field_loss_kernels_carry_no_scratch(tmp_path):
     print({n: v for n, v in k.items()})
     assert all(v["scratch"] == 0 for v in k.values()), k
     assert all(v["vgpr"] <= 64 and v["lds"] <= 2048 for v in k.values()), k
+
+
+# ------------------------------------------------------------------ the caller's memory
+def _device_call(which, case, dev):
+    cams, gravs, data = fg.make_case(case)
+    cam, grav = cams.to(dev), gravs.to(dev)
+    planes = [data[k].to(dev) for k in ("up_field", "latitude_field", "up_confidence", "latitude_confidence")]
+    if which == "loss":
+        return lambda: [fields.field_loss(case[0], cam, grav, *planes, "l1", "huber")]
+    scale = torch.tensor([[0.25, -1.5]], device=dev).repeat(case[1], 1)
+    return lambda: fields.field_loss_grad(case[0], cam, grav, scale, *planes, "l1", "huber")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["loss", "grad"])
+def test_results_do_not_depend_on_what_the_handed_memory_held(monkeypatch, which):
+    """gclm_field_loss / gclm_field_loss_grad at 30 x 200 (tile columns and rows both ragged) with the wrapper's torch.empty
+    memory -- the workspace of the loss; the gradient takes none: its two output planes -- holding 0x00 bytes, 0xFF bytes, and
+    what a call at 3 x 37 x 53 left: the same bits."""
+    from workspace_fill import same_bits_whatever_the_memory_held
+    dev = torch.device("cuda:0")
+    same_bits_whatever_the_memory_held(monkeypatch, dev, _device_call(which, ("simple_radial", 2, 30, 200, "random", False), dev),
+                                       _device_call(which, ("simple_radial", 3, 37, 53, "random", False), dev))

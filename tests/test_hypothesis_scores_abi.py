@@ -294,3 +294,20 @@ def test_hypothesis_kernels_carry_no_scratch(tmp_path):
     assert all(v["scratch"] == 0 for v in k.values()), k
     assert all(v["vgpr"] <= VGPR_MAX and v["lds"] <= LDS_MAX for n, v in k.items() if "finish" not in n), k
     assert finish[0]["vgpr"] <= FINISH_VGPR_MAX and finish[0]["lds"] <= FINISH_LDS_MAX, finish
+
+
+# ------------------------------------------------------------------ the caller's workspace
+def _device_call(case, dev):
+    cams, gravs, data = fg.make_case(case)
+    hc, hgv = (t.to(dev) for t in hg.hypotheses(cams, gravs, 7))
+    planes = [data[k].to(dev) for k in ("up_field", "latitude_field", "up_confidence", "latitude_confidence")]
+    return lambda: fields.hypothesis_scores(case[0], hc, hgv, *planes, up_weight=WEIGHTS[0], lat_weight=WEIGHTS[1])
+
+
+@pytest.mark.gpu
+def test_results_do_not_depend_on_what_the_workspace_held(monkeypatch):
+    """gclm_hypothesis_scores at 30 x 200, seven hypotheses (tile columns and rows both ragged) with the wrapper's torch.empty
+    workspace holding 0x00 bytes, 0xFF bytes, and the records of a call at 3 x 37 x 53: the same scores and the same winner."""
+    from workspace_fill import same_bits_whatever_the_memory_held
+    dev = torch.device("cuda:0")
+    same_bits_whatever_the_memory_held(monkeypatch, dev, _device_call(SELF[2], dev), _device_call(SELF[0], dev))

@@ -396,3 +396,32 @@ def test_absent_planes_and_the_workspace_tail_are_never_written(ref):
         assert sorted(part) == sorted(wanted)
         for k in wanted:
             assert torch.equal(part[k].view(torch.int32), full[k].view(torch.int32)), (wanted, k)
+
+
+@pytest.mark.gpu
+def test_results_do_not_depend_on_what_the_workspace_held(ref):
+    """gclm_lm_backward on the fixture's 13 x 19 case (ragged tiles both ways, ten recorded steps) with the caller's workspace
+    holding 0x00 bytes, 0xFF bytes (NaN patterns), and the records of a call at 3 x 12 x 20: the same bits in all four planes."""
+    from test_lm_grad_oracle import case_conf
+
+    def prepared(name):
+        data = case_data(ref, name, torch.float32, dev(), requires_grad=False)
+        opt = LMOptimizer(case_conf(ref, name)).train()
+        record = lm_grad.recorded_solve(opt, dict(data))[3]
+        adj = [torch.from_numpy(ref[f"{name}/{k}"]).float().to(dev()) for k in ("w_cam", "w_grav")]
+        B, _, H, W = data["latitude_field"].shape
+        return (opt, name.split("/")[1], data, record, *adj), int(_lib.load().gclm_lm_backward_workspace(B, H, W))
+
+    (case, need), (other, other_need) = prepared("c2/simple_radial/huber"), prepared("c1/simple_radial/huber")
+    ws = torch.empty(max(need, other_need), dtype=torch.uint8, device=dev())
+    runs = []
+    for fill in (0x00, 0xFF, None):
+        if fill is None:
+            hip_backward(*other, workspace=ws)
+        else:
+            ws.fill_(fill)
+        runs.append({k: v.clone() for k, v in hip_backward(*case, workspace=ws).items()})
+    assert sorted(runs[0]) == sorted(INPUTS)
+    for what, run in zip(("0xFF bytes", "another call's records"), runs[1:]):
+        for k in INPUTS:
+            assert torch.equal(run[k].view(torch.int32), runs[0][k].view(torch.int32)), (what, k)

@@ -487,3 +487,25 @@ def test_initial_interval_holds_the_estimate_and_the_edges_take_their_branches(p
         assert est[2] == pytest.approx(float(np.float32(math.radians(20))), abs=1e-12)
     if pose[2] == 150:
         assert est[2] == pytest.approx(float(np.float32(math.radians(120))), abs=1e-12)
+
+
+# ------------------------------------------------------------------ the caller's workspace
+def _device_call(name, dev):
+    up, lat, state = pg.ragged_case(name)
+    data = {"up_field": torch.from_numpy(up.copy())[None].to(dev), "latitude_field": torch.from_numpy(lat.copy())[None].to(dev)}
+    init = torch.from_numpy(np.asarray(state, np.float32))[None].to(dev)
+    opt = perspective_opt.PerspectiveParamOpt({"max_steps": 12})
+
+    def run():
+        out = opt(data, init=init)
+        return [out[k] for k in ("rpv", "steps", "converged", "final_cost", "final_up_cost", "final_latitude_cost", "lr")]
+    return run
+
+
+@pytest.mark.gpu
+def test_results_do_not_depend_on_what_the_workspace_held(monkeypatch):
+    """gclm_param_opt on the ragged 6 x 260 case (two tile columns, two tile rows) with the wrapper's torch.empty workspace
+    holding 0x00 bytes, 0xFF bytes, and the state and records of a call at 50 x 516: the same bits after twelve steps."""
+    from workspace_fill import same_bits_whatever_the_memory_held
+    dev = torch.device("cuda:0")
+    same_bits_whatever_the_memory_held(monkeypatch, dev, _device_call("6x260", dev), _device_call("50x516", dev))
