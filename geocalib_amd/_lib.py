@@ -116,6 +116,8 @@ _SIGNATURES = {
     "gclm_solve_recorded": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "gclm_calibrate_recorded": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P,
                                           _P]),
+    "gclm_calibrate_soft": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P,
+                                      _P, _P, _P]),
     "gclm_lm_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "gclm_lm_backward": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_float, C.c_float,
                                    C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),

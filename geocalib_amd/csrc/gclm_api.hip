@@ -75,6 +75,7 @@ struct gclm_handle {
     // carved views
     SolveCtx ctx{};
     float* group_partials = nullptr;
+    float* prior_cost = nullptr;    // (B,2) the soft priors' costs of a gclm_calibrate_soft call that hands no d_prior_cost_out
     // split shared-intrinsics session
     struct {
         bool active = false;
@@ -187,6 +188,7 @@ int ensure_workspace(gclm_handle* h, int B, int nchunks, int G) {
     const size_t o_gp = take(sizeof(float) * GCLM_SHARED_PARTIAL_STRIDE * (size_t)(G > 0 ? G : 1));
     const size_t o_ctrl = take(sizeof(Ctrl));
     const size_t o_cpf = take(sizeof(unsigned) * B);
+    const size_t o_pc = take(sizeof(float) * 2 * B);
     if (off > h->ws_bytes) {
         if (h->ws) GCLM_HIP(h, hipFree(h->ws));
         h->ws = nullptr;
@@ -209,6 +211,7 @@ int ensure_workspace(gclm_handle* h, int B, int nchunks, int G) {
     c.ctrl = reinterpret_cast<Ctrl*>(base + o_ctrl);
     c.cpack_flags = reinterpret_cast<unsigned*>(base + o_cpf);
     h->group_partials = reinterpret_cast<float*>(base + o_gp);
+    h->prior_cost = reinterpret_cast<float*>(base + o_pc);
     return 0;
 }
 
@@ -493,14 +496,14 @@ int solve_one_launch_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, float
 
 // init | { sweep(theta_i) ; update_i } x num_steps | prep_final ; sweep(theta_final, rpf) ; finalize
 int solve_two_launches_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, float* d_cam_out, float* d_grav_out,
-                                float* d_info_out, hipStream_t s, float* d_record = nullptr) {
+                                float* d_info_out, hipStream_t s, float* d_record = nullptr, const SoftPrior& sp = SoftPrior{}) {
     const SolveCtx& c = h->ctx;
     const bool es = h->cfg.early_stop != 0;
     GCLM_HIP(h, launch_init(c, ia, s));
     for (int step = 0; step < h->cfg.num_steps; ++step) {
         if (int rc = timed_sweep(h, p.next_sweep(h, c.pb[step & 1], true, es ? step : 0), s)) return rc;
         if (!h->cfg.shared_intrinsics) {
-            GCLM_HIP(h, launch_update(c, step, s, d_record));
+            GCLM_HIP(h, launch_update(c, step, s, d_record, sp));
         } else {
             GCLM_HIP(h, launch_shared_step(c, step, s));     // reduce + Schur solve + update: one launch
         }
@@ -512,14 +515,19 @@ int solve_two_launches_per_step(gclm_handle* h, Plan& p, const InitArgs& ia, flo
     }
     GCLM_HIP(h, launch_prep_final(c, s));
     if (int rc = timed_sweep(h, p.next_sweep(h, c.pb_final, false, 0), s)) return rc;
-    GCLM_HIP(h, launch_finalize(c, d_cam_out, d_grav_out, d_info_out, s));
+    GCLM_HIP(h, launch_finalize(c, d_cam_out, d_grav_out, d_info_out, s, sp));
     return 0;
 }
 
+// `soft`: the soft priors of gclm_calibrate_soft (all null elsewhere); soft.cost null: the handle's own (B,2) floats
 int run_solve(gclm_handle* h, const Fields& f, int B, int H, int W, const InitArgs& ia, float* d_cam_out,
-              float* d_grav_out, float* d_info_out, const float* d_sin_lat, void* stream, float* d_record = nullptr) {
+              float* d_grav_out, float* d_info_out, const float* d_sin_lat, void* stream, float* d_record = nullptr,
+              SoftPrior soft = SoftPrior{}) {
     if (int rc = check_shapes(h, f.lat, B, H, W)) return rc;
     if (d_record && h->cfg.shared_intrinsics) return fail(h, -3, "the step record is kept for per-image solves only");
+    if (soft.on() && h->cfg.shared_intrinsics) return fail(h, -3, "soft priors are for per-image solves only");
+    if (soft.on() && !(h->cfg.use_spherical_manifold && h->cfg.use_log_focal))
+        return fail(h, -3, "soft priors need use_spherical_manifold and use_log_focal");
     if (B > 0 && (!d_cam_out || !d_grav_out || !d_info_out)) return fail(h, -3, "null output pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     h->sh.active = false;       // any solve ends a split session, also the empty one, which plans nothing (make_plan does it for the others)
@@ -532,12 +540,16 @@ int run_solve(gclm_handle* h, const Fields& f, int B, int H, int W, const InitAr
     h->ctx.iso_final = (ia.cam == nullptr && ia.scales == nullptr && GCLM_ISO_FINAL) ? 1 : 0;
     Plan p;
     if (int rc = make_plan(h, p, f, B, H, W, d_sin_lat, h->cfg.num_steps + 1)) return rc;
-    if (d_record) {
-        // the record is written by the per-image update kernel: a call planned as one launch per step takes its two-launch
-        // twin (same geometry, no plane of its own: the plan above stands), which computes the same bits
+    if (soft.on() && !soft.cost) soft.cost = h->prior_cost;
+    if (d_record || soft.on()) {
+        // the record is written, and the soft priors are added, by the per-image update kernel: a call planned as one launch
+        // per step takes its two-launch twin (same geometry, no plane of its own: the plan above stands), which computes the
+        // same bits
         p.one_launch = false;
-        GCLM_HIP(h, hipMemsetAsync(d_record, 0, sizeof(float) * GCLM_LM_RECORD_STRIDE * (size_t)B * h->cfg.num_steps, s));
-        return solve_two_launches_per_step(h, p, ia, d_cam_out, d_grav_out, d_info_out, s, d_record);
+        if (d_record) GCLM_HIP(h, hipMemsetAsync(d_record, 0, sizeof(float) * GCLM_LM_RECORD_STRIDE * (size_t)B * h->cfg.num_steps, s));
+        // (num_steps = 0: no update writes the initial prior cost, which is then the final one's slot neighbour: zero it)
+        if (soft.on() && h->cfg.num_steps == 0) GCLM_HIP(h, hipMemsetAsync(soft.cost, 0, sizeof(float) * 2 * (size_t)B, s));
+        return solve_two_launches_per_step(h, p, ia, d_cam_out, d_grav_out, d_info_out, s, d_record, soft);
     }
     if (p.one_launch) return solve_one_launch_per_step(h, p, ia, d_cam_out, d_grav_out, d_info_out, s);
     return solve_two_launches_per_step(h, p, ia, d_cam_out, d_grav_out, d_info_out, s);
@@ -889,12 +901,15 @@ static int calibrate_entry(gclm_handle* h, const float* d_up, const float* d_lat
                            const float* d_lat_conf, int B, int H, int W, const float* d_scales,
                            const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
                            int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
-                           const float* d_sin_lat, float* d_record, void* stream) {
+                           const float* d_sin_lat, float* d_record, void* stream, const float* d_prior_focal_sigma = nullptr,
+                           const float* d_prior_gravity_sigma = nullptr, float* d_prior_cost_out = nullptr) {
     if (!h) return -1;
     if (d_prior_dist && (prior_dist_cols < 1 || prior_dist_cols > 2)) return fail(h, -3, "gclm_calibrate: prior_dist_cols must be 1 or 2");
     // the free-parameter flags must agree with the priors (setup_optimization_and_priors, :204-221); an empty batch has
     // no prior rows either (NULL), and only takes part in the stop collectives
-    if (B != 0 && ((d_prior_focal != nullptr) == (h->cfg.estimate_focal != 0) || (d_prior_gravity != nullptr) == (h->cfg.estimate_gravity != 0)))
+    // (a prior given with its standard deviation -- gclm_calibrate_soft -- keeps its column free)
+    const bool hard_focal = d_prior_focal && !d_prior_focal_sigma, hard_gravity = d_prior_gravity && !d_prior_gravity_sigma;
+    if (B != 0 && (hard_focal == (h->cfg.estimate_focal != 0) || hard_gravity == (h->cfg.estimate_gravity != 0)))
         return fail(h, -2, "gclm_calibrate: estimate_focal / estimate_gravity disagree with the priors passed");
     InitArgs ia{};
     ia.scales = d_scales;
@@ -906,7 +921,57 @@ static int calibrate_entry(gclm_handle* h, const float* d_up, const float* d_lat
     ia.lat = d_lat;
     if (h->cfg.heuristic_init && !d_up && B != 0) return fail(h, -3, "gclm_calibrate: heuristic_init needs the up field");
     // (the initial estimate -- the heuristic one reads `lat` -- always reads the radians: ia.lat)
-    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, d_sin_lat, stream, d_record);
+    SoftPrior soft{};
+    if (d_prior_focal_sigma || d_prior_gravity_sigma) {
+        soft.focal = d_prior_focal;
+        soft.focal_sigma = d_prior_focal_sigma;
+        soft.gravity = d_prior_gravity;
+        soft.gravity_sigma = d_prior_gravity_sigma;
+        soft.cost = d_prior_cost_out;
+    }
+    return run_solve(h, Fields{d_up, d_lat, d_up_conf, d_lat_conf}, B, H, W, ia, d_cam_out, d_grav_out, d_info_out, d_sin_lat, stream, d_record,
+                     soft);
+}
+
+int gclm_calibrate_soft(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                        const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                        const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                        int prior_dist_cols, const float* d_prior_focal_sigma, const float* d_prior_gravity_sigma,
+                        float* d_cam_out, float* d_grav_out, float* d_info_out, float* d_prior_cost_out,
+                        const float* d_sin_lat, void* stream) {
+    if (!d_prior_focal_sigma && !d_prior_gravity_sigma)         // gclm_calibrate_ex exactly; d_prior_cost_out is not written
+        return calibrate_entry(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_scales, d_prior_focal, d_prior_gravity, d_prior_dist,
+                               prior_dist_cols, d_cam_out, d_grav_out, d_info_out, d_sin_lat, nullptr, stream);
+    // Everything that can be refused from the arguments alone comes first, before the handle is looked at and before any
+    // HIP call (h == NULL: the message goes where gclm_create's does).
+    if ((d_prior_focal_sigma && !d_prior_focal) || (d_prior_gravity_sigma && !d_prior_gravity))
+        return fail(h, -3, "gclm_calibrate_soft: a standard deviation without its prior");
+    if (B <= 0 || B > kMaxCallImages || H <= 0 || W <= 0) return fail(h, -3, "gclm_calibrate_soft: bad shape B=%d H=%d W=%d", B, H, W);
+    if (!d_lat || !d_cam_out || !d_grav_out || !d_info_out) return fail(h, -3, "gclm_calibrate_soft: null field or output pointer");
+    if (d_prior_dist && (prior_dist_cols < 1 || prior_dist_cols > 2)) return fail(h, -3, "gclm_calibrate_soft: prior_dist_cols must be 1 or 2");
+    ArgCheck a;
+    a.writes(d_cam_out, floats(B, GCLM_CAM_STRIDE), 4);
+    a.writes(d_grav_out, floats(B, GCLM_GRAV_STRIDE), 4);
+    a.writes(d_info_out, floats(B, GCLM_INFO_STRIDE), 4);
+    a.writes(d_prior_cost_out, floats(B, 2), 4);
+    a.reads(d_up, floats(B, 2, H, W), 4);
+    a.reads(d_lat, floats(B, H, W), 4);
+    a.reads(d_up_conf, floats(B, H, W), 4);
+    a.reads(d_lat_conf, floats(B, H, W), 4);
+    a.reads(d_sin_lat, floats(B, H, W), 4);
+    a.reads(d_scales, floats(2), 4);
+    a.reads(d_prior_focal, floats(B), 4);
+    a.reads(d_prior_gravity, floats(B, 3), 4);
+    a.reads(d_prior_dist, floats(B, prior_dist_cols > 0 ? prior_dist_cols : 1), 4);
+    a.reads(d_prior_focal_sigma, floats(B), 4);
+    a.reads(d_prior_gravity_sigma, floats(B), 4);
+    if (!a.pass()) return fail(h, -3, "gclm_calibrate_soft: a misaligned pointer, or an output that overlaps another range of the call");
+    if (!h) return -1;
+    if (h->cfg.shared_intrinsics || !(h->cfg.use_spherical_manifold && h->cfg.use_log_focal))
+        return fail(h, -3, "gclm_calibrate_soft: per-image solves on the spherical manifold and the log focal length only");
+    return calibrate_entry(h, d_up, d_lat, d_up_conf, d_lat_conf, B, H, W, d_scales, d_prior_focal, d_prior_gravity, d_prior_dist,
+                           prior_dist_cols, d_cam_out, d_grav_out, d_info_out, d_sin_lat, nullptr, stream, d_prior_focal_sigma,
+                           d_prior_gravity_sigma, d_prior_cost_out);
 }
 
 int gclm_calibrate_ex(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,

@@ -325,13 +325,15 @@ struct StepDelta {
     float dg0, dg1, df, dk1, dk2;
 };
 // (`d`: the full-size solution over the columns (d1, d2, f, k1[, k2]), zero in fixed columns and after a failed step --
-//  what the step record of gclm_solve_recorded keeps)
+//  what the step record of gclm_solve_recorded keeps;
+//  `prior_mean_cost`: null, or the soft priors' cost / N at this state (add_soft_priors), which joins the compared cost)
 template <int PM>
 __device__ inline bool lm_solve(const gclm_config& cfg, int H, int W, int step, State& s, const float (&acc)[kNAccMax],
-                                StepDelta& dl, float (&d)[PM]) {
+                                StepDelta& dl, float (&d)[PM], const float* prior_mean_cost = nullptr) {
     const float invN = 1.0f / (float)((size_t)H * W);
     float cu, cl;
-    const float total = total_cost(acc, invN, true, cu, cl);   // A_CU is 0 without an up field
+    float total = total_cost(acc, invN, true, cu, cl);   // A_CU is 0 without an up field
+    if (prior_mean_cost) total = total + *prior_mean_cost;
     if (step == 0) { s.init_cu = cu; s.init_cl = cl; }     // infos["initial_*"] (:585-588)
     const bool moved = cost_rules(cfg, step, total, s, !cfg.fix_lambda);
 
@@ -376,9 +378,9 @@ __device__ inline void lm_apply_dist(const gclm_config& cfg, State& s, const Ste
 }
 template <int PM>
 __device__ inline bool lm_step(const gclm_config& cfg, int H, int W, int step, State& s, const float (&acc)[kNAccMax],
-                               float (&d)[PM]) {
+                               float (&d)[PM], const float* prior_mean_cost = nullptr) {
     StepDelta dl;
-    const bool moved = lm_solve<PM>(cfg, H, W, step, s, acc, dl, d);
+    const bool moved = lm_solve<PM>(cfg, H, W, step, s, acc, dl, d, prior_mean_cost);
     lm_apply_gravity(cfg, s, dl);
     lm_apply_focal(cfg, s, dl);
     lm_apply_dist(cfg, s, dl);
@@ -389,6 +391,72 @@ __device__ inline bool lm_step(const gclm_config& cfg, int H, int W, int step, S
     float d[PM];
     return lm_step<PM>(cfg, H, W, step, s, acc, d);
 }
+
+// Soft priors (gclm_calibrate_soft): a prior given with its standard deviation is one more observation of image b, in the
+// sum convention of the sweep's record (cost sum rho, H = sum w J^T J, G = sum w J^T r, r = target - model), at state s:
+//   focal    on the log-focal column 2: w = (f0 / sigma_f)^2, r = log f0 - log fy;  G[2] += w r, H[2][2] += w, cost w r^2
+//            (r as log(f0 / fy): the difference of two float32 logarithms of ~3 would carry 1e-5 of a residual of 0.03)
+//   gravity  g0 = normalize(prior), w = 1 / sigma_g^2, r = g0 - g, T the 3x2 tangent basis of columns 0 and 1 (the sweep's:
+//            pblock_tangent);  G[0:2] += w T^T r, H[0:2,0:2] += w T^T T, cost w |r|^2
+// added to the image's REDUCED record `acc`; the cost is returned (to be divided by N like the data costs) and not folded
+// into A_CU / A_CL, which stay the data's.  `final_form`: the record is the uncertainty sweep's, over (roll, pitch, plain
+// focal): only the information is added, T = tangent_rp and 1 / sigma_f^2 on the focal diagonal -- times fy^2 where the sweep
+// ran the log-focal form that finalize_kernel rescales by 1 / fy (`iso_final`).  The cost is that of the LM form either way.
+// A sigma that is not finite and positive (or a prior that cannot be used: non-positive focal, NaN) leaves its term out and
+// sets `bad`; the caller counts a failed step.  Weights that underflow add exact zeros: sigma = 1e30 is the free solve's bits.
+struct PriorTerms {
+    float cost;
+    bool bad;
+};
+__device__ inline bool finite_positive(float v) { return v > 0.f && v <= 3.0e38f; }
+template <int PM>
+__device__ inline PriorTerms add_soft_priors(const gclm_config& cfg, const SoftPrior& sp, int b, const State& s, bool final_form,
+                                             bool iso_final, float (&acc)[kNAccMax]) {
+    PriorTerms out{0.f, false};
+    if (sp.focal_sigma) {
+        const float f0 = sp.focal[b], sg = sp.focal_sigma[b];
+        if (finite_positive(sg) && finite_positive(f0)) {
+            const float q = f0 / sg, w = q * q, r = logf(f0 / s.fy);
+            out.cost += w * r * r;
+            if (!final_form) {
+                acc[A_G0 + 2] += w * r;
+                acc[acc_h(PM, 2, 2)] += w;
+            } else {
+                const float qf = (iso_final ? s.fy : 1.0f) / sg;
+                acc[acc_h(PM, 2, 2)] += qf * qf;
+            }
+        } else {
+            out.bad = true;
+        }
+    }
+    if (sp.gravity_sigma) {
+        const float sg = sp.gravity_sigma[b];
+        const V3 g0 = normalize3({sp.gravity[b * 3], sp.gravity[b * 3 + 1], sp.gravity[b * 3 + 2]});
+        const float n0 = g0.x * g0.x + g0.y * g0.y + g0.z * g0.z;
+        if (finite_positive(sg) && n0 > 0.5f && n0 < 2.0f) {        // (a zero or NaN prior vector does not normalise)
+            const float is = 1.0f / sg, w = is * is;
+            const float r[3] = {g0.x - s.gx, g0.y - s.gy, g0.z - s.gz};
+            float T[3][2];
+            if (final_form) tangent_rp({s.gx, s.gy, s.gz}, T);
+            else pblock_tangent({s.gx, s.gy, s.gz}, cfg.use_spherical_manifold != 0, T);
+            out.cost += w * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+            if (!final_form) {
+                acc[A_G0 + 0] += w * (T[0][0] * r[0] + T[1][0] * r[1] + T[2][0] * r[2]);
+                acc[A_G0 + 1] += w * (T[0][1] * r[0] + T[1][1] * r[1] + T[2][1] * r[2]);
+            }
+            acc[acc_h(PM, 0, 0)] += w * (T[0][0] * T[0][0] + T[1][0] * T[1][0] + T[2][0] * T[2][0]);
+            acc[acc_h(PM, 0, 1)] += w * (T[0][0] * T[0][1] + T[1][0] * T[1][1] + T[2][0] * T[2][1]);
+            acc[acc_h(PM, 1, 1)] += w * (T[0][1] * T[0][1] + T[1][1] * T[1][1] + T[2][1] * T[2][1]);
+        } else {
+            out.bad = true;
+        }
+    }
+    return out;
+}
+// The cost the damping rule and the early stop compare, with soft priors: (up + latitude) + prior / N, each operation
+// rounded to float32 (here, where nothing contracts), so that infos["final_cost"] is that float32 sum of its three infos.
+__device__ inline float prior_mean(float prior_cost, float invN) { return prior_cost * invN; }
+__device__ inline float add_prior_mean(float data_total, float prior_cost_mean) { return data_total + prior_cost_mean; }
 
 // The state after update `step` and its parameter block go into the OTHER half of the double buffers, for the next sweep.
 __device__ inline void commit_state(const SolveCtx& c, int step, int b, const State& s) {

@@ -151,6 +151,17 @@ struct InitArgs {              // initial estimate: explicit (cam, grav) or triv
     const float* up;            // heuristic initialisation reads three pixels of the fields
     const float* lat;
 };
+// Soft priors of a per-image solve (gclm_calibrate_soft): a prior with its standard deviation is a pseudo-observation of
+// every LM step and of the uncertainty pass (gclm_device.h: add_soft_priors).  A kernel argument of its own, handed to
+// update_kernel and finalize_kernel only; every pointer may be null (all null: the solve without soft priors).
+struct SoftPrior {
+    const float* focal;          // (B,) prior fy, with ...
+    const float* focal_sigma;    // (B,) its standard deviation in pixels, or nullptr: no soft focal prior
+    const float* gravity;        // (B,3) prior gravity (normalised on use), with ...
+    const float* gravity_sigma;  // (B,) its isotropic standard deviation in radians, or nullptr: no soft gravity prior
+    float* cost;                 // (B,2) prior cost / N at the initial and at the final state; never null when a sigma is given
+    __host__ __device__ bool on() const { return focal_sigma != nullptr || gravity_sigma != nullptr; }
+};
 // One-launch-per-step variant of the sweep for small batches (gclm_pass.hip: fused_step_kernel)
 struct FusedArgs {
     SolveCtx c;
@@ -201,9 +212,11 @@ hipError_t launch_jacobian_fields(int camera_model, const float* d_cam, const fl
 
 // gclm_update.hip
 hipError_t launch_init(const SolveCtx& c, const InitArgs& ia, hipStream_t s);
-hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s, float* d_record = nullptr);   // d_record: gclm_solve_recorded
+hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s, float* d_record = nullptr,     // d_record: gclm_solve_recorded
+                         const SoftPrior& sp = SoftPrior{});
 hipError_t launch_prep_final(const SolveCtx& c, hipStream_t s);
-hipError_t launch_finalize(const SolveCtx& c, float* d_cam, float* d_grav, float* d_info, hipStream_t s);
+hipError_t launch_finalize(const SolveCtx& c, float* d_cam, float* d_grav, float* d_info, hipStream_t s,
+                           const SoftPrior& sp = SoftPrior{});
 hipError_t launch_merge_stop(const MergeStopArgs& a, hipStream_t s);
 hipError_t launch_shared_reduce(const SolveCtx& c, int step, float* d_group_partials, hipStream_t s);
 hipError_t launch_shared_apply(const SolveCtx& c, int step, const float* d_group_partials, hipStream_t s);

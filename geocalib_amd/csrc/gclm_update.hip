@@ -72,8 +72,10 @@ __global__ void init_kernel(SolveCtx c, InitArgs ia) {
 // `record` (gclm_solve_recorded): null, or (B, num_steps, GCLM_LM_RECORD_STRIDE) floats; the image's leader leaves row `step`
 // there -- the state the step started from, the damping used, the full-size step, "failed", "executed" and the reduced
 // accumulator record (include/gclm.h has the layout).  Plain vector stores of values the step computes anyway.
+// `sp` (gclm_calibrate_soft): the soft priors' terms join the reduced record before the step (a uniform branch: one
+// pointer test per kernel), so the step, the compared cost and the recorded system are the posterior's.
 template <int PM>
-__global__ __launch_bounds__(kGroups * kSlots) void update_kernel(SolveCtx c, int step, float* record) {
+__global__ __launch_bounds__(kGroups * kSlots) void update_kernel(SolveCtx c, int step, float* record, SoftPrior sp) {
     if (c.cfg.early_stop && stop_fired_before(c.ctrl, step)) return;          // block-uniform
     // the leader of an image fetches its state BEFORE the reduction: the load overlaps the partial records' round trip
     // instead of heading the serial chain behind it
@@ -84,7 +86,17 @@ __global__ __launch_bounds__(kGroups * kSlots) void update_kernel(SolveCtx c, in
     if (!coop_reduce_partials(c, r, acc)) return;
     const State s0 = s;
     float d[PM];
-    if (lm_step<PM>(c.cfg, c.H, c.W, step, s, acc, d)) atomicAdd(&c.ctrl->notclose[step], 1);
+    bool moved;
+    if (sp.on()) {
+        const PriorTerms pt = add_soft_priors<PM>(c.cfg, sp, r.b, s, false, false, acc);
+        const float pcn = prior_mean(pt.cost, 1.0f / (float)((size_t)c.H * c.W));
+        if (step == 0) sp.cost[r.b * 2] = pcn;              // infos["initial_prior_cost"]
+        moved = lm_step<PM>(c.cfg, c.H, c.W, step, s, acc, d, &pcn);
+        if (pt.bad) s.fails += 1.f;                         // an unusable sigma or prior: its term was left out
+    } else {
+        moved = lm_step<PM>(c.cfg, c.H, c.W, step, s, acc, d);
+    }
+    if (moved) atomicAdd(&c.ctrl->notclose[step], 1);
     commit_state(c, step, r.b, s);
     if (record) {
         float* o = record + ((size_t)r.b * c.cfg.num_steps + step) * GCLM_LM_RECORD_STRIDE;
@@ -157,8 +169,10 @@ __device__ inline void spd_inverse(const float (&A)[N][N], double (&inv)[N][N]) 
 }
 
 // Final costs + estimate_uncertainty (lm_optimizer.py:632-642, 463-516) from the final sweep.
+// `sp`: the soft priors join the final record too -- their cost at the final state the compared cost, their information
+// (in the uncertainty sweep's parametrisation) the Hessian before its inverse: the covariance is the posterior's.
 template <int PM>
-__global__ __launch_bounds__(kGroups * kSlots) void finalize_kernel(SolveCtx c, float* cam, float* grav, float* info) {
+__global__ __launch_bounds__(kGroups * kSlots) void finalize_kernel(SolveCtx c, float* cam, float* grav, float* info, SoftPrior sp) {
     const CoopRole r = coop_role(c.B, c.nchunks);
     const int b = r.b;
     float acc[kNAccMax];
@@ -168,7 +182,15 @@ __global__ __launch_bounds__(kGroups * kSlots) void finalize_kernel(SolveCtx c, 
     State s = c.state[sel][b];
     const float invN = 1.0f / (float)((size_t)c.H * c.W);
     float cu, cl;
-    const float total = total_cost(acc, invN, true, cu, cl);
+    float total = total_cost(acc, invN, true, cu, cl);
+    float pcn0 = 0.f;
+    if (sp.on()) {
+        const PriorTerms pt = add_soft_priors<PM>(cfg, sp, b, s, true, c.iso_final != 0, acc);
+        const float pcn = prior_mean(pt.cost, invN);
+        total = add_prior_mean(total, pcn);
+        pcn0 = sp.cost[b * 2];
+        sp.cost[b * 2 + 1] = pcn;                           // infos["final_prior_cost"]
+    }
     // the final sweep is also the "new cost" evaluation of the last executed step
     const bool update_lambda = !cfg.fix_lambda && !cfg.shared_intrinsics;
     if (!c.ctrl->stopped)
@@ -184,7 +206,7 @@ __global__ __launch_bounds__(kGroups * kSlots) void finalize_kernel(SolveCtx c, 
     o[GCLM_INFO_STOP_AT] = (float)first_quiet_step(c.ctrl, cfg.num_steps);      // (nothing of this launch is needed for it)
     o[GCLM_INFO_INITIAL_UP_COST] = s.init_cu;
     o[GCLM_INFO_INITIAL_LAT_COST] = s.init_cl;
-    o[GCLM_INFO_INITIAL_COST] = s.init_cu + s.init_cl;
+    o[GCLM_INFO_INITIAL_COST] = sp.on() ? add_prior_mean(s.init_cu + s.init_cl, pcn0) : s.init_cu + s.init_cl;
     o[GCLM_INFO_FINAL_UP_COST] = cu;
     o[GCLM_INFO_FINAL_LAT_COST] = cl;
     o[GCLM_INFO_FINAL_COST] = total;
@@ -573,15 +595,15 @@ hipError_t launch_init(const SolveCtx& c, const InitArgs& ia, hipStream_t s) {
     GCLM_L(init_kernel, c.B > 0 ? c.B : 1, s, c, ia);     // B = 0 (an empty shard of the split protocol): thread 0 still resets Ctrl
     return hipGetLastError();
 }
-hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s, float* d_record) {
-    return with_system_size(c.cfg.camera_model, [&](auto pm, auto) { GCLM_LR(update_kernel<pm>, c.B, s, c, step, d_record); });
+hipError_t launch_update(const SolveCtx& c, int step, hipStream_t s, float* d_record, const SoftPrior& sp) {
+    return with_system_size(c.cfg.camera_model, [&](auto pm, auto) { GCLM_LR(update_kernel<pm>, c.B, s, c, step, d_record, sp); });
 }
 hipError_t launch_prep_final(const SolveCtx& c, hipStream_t s) {
     GCLM_L(prep_final_kernel, c.B, s, c);
     return hipGetLastError();
 }
-hipError_t launch_finalize(const SolveCtx& c, float* d_cam, float* d_grav, float* d_info, hipStream_t s) {
-    return with_system_size(c.cfg.camera_model, [&](auto pm, auto) { GCLM_LR(finalize_kernel<pm>, c.B, s, c, d_cam, d_grav, d_info); });
+hipError_t launch_finalize(const SolveCtx& c, float* d_cam, float* d_grav, float* d_info, hipStream_t s, const SoftPrior& sp) {
+    return with_system_size(c.cfg.camera_model, [&](auto pm, auto) { GCLM_LR(finalize_kernel<pm>, c.B, s, c, d_cam, d_grav, d_info, sp); });
 }
 // Parts of ONE batch solved by separate handles (LMOptimizer.overlap_streams): infos["stop_at"] is a property of the
 // whole batch, so it is re-derived from the SUM of the parts' per-step counters and written into every row of every part.

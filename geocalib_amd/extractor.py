@@ -110,7 +110,13 @@ class GeoCalib(nn.Module):
     def calibrate(self, img: torch.Tensor, camera_model: str = "pinhole",
                   priors: Optional[Dict[str, torch.Tensor]] = None,
                   shared_intrinsics: bool = False) -> Dict[str, torch.Tensor]:
-        """img: (C,H,W) or (B,C,H,W) in [0,1] RGB; B must be 1 unless shared_intrinsics."""
+        """img: (C,H,W) or (B,C,H,W) in [0,1] RGB; B must be 1 unless shared_intrinsics.
+
+        `priors`: "focal" (pixels of the INPUT image) and "gravity", held fixed as in the reference -- or, an extension, each
+        with its standard deviation, "focal_uncertainty" (pixels of the input image, the unit of the returned
+        `focal_uncertainty`) and "gravity_uncertainty" (radians): the prior then stays free and enters the solve as one more
+        observation (LMOptimizer: `prior_focal_uncertainty`, `prior_gravity_uncertainty`).  The focal prior and its
+        uncertainty are scaled to the solve's resolution by `scales[1]`, and the result is scaled back as always."""
         if len(img.shape) == 3:
             img = img[None]
         if not shared_intrinsics:
@@ -121,9 +127,16 @@ class GeoCalib(nn.Module):
         if (pf := priors.get("focal")) is not None:
             pf = pf[None] if len(pf.shape) == 0 else pf
             prior_values["prior_focal"] = pf * img_data["scales"][1]
+        if (pfu := priors.get("focal_uncertainty")) is not None:
+            pfu = torch.as_tensor(pfu, dtype=torch.float32)
+            prior_values["prior_focal_uncertainty"] = \
+                (pfu[None] if len(pfu.shape) == 0 else pfu).to(img_data["scales"].device) * img_data["scales"][1]
         if "gravity" in priors:
             pg = priors["gravity"]
             prior_values["prior_gravity"] = pg[None] if len(pg.shape) == 0 else pg
+        if (pgu := priors.get("gravity_uncertainty")) is not None:
+            pgu = torch.as_tensor(pgu, dtype=torch.float32)
+            prior_values["prior_gravity_uncertainty"] = pgu[None] if len(pgu.shape) == 0 else pgu
         self.optimizer.set_camera_model(camera_model)
         self.optimizer.shared_intrinsics = shared_intrinsics
         out = dict(self.field_model(img_data))
@@ -135,5 +148,5 @@ class GeoCalib(nn.Module):
         if "covariance" in out:
             res["covariance"] = out["covariance"]
         for tag in ("field", "confidence", "uncertainty"):
-            res |= {k: out[k] for k in out if tag in k}
+            res |= {k: out[k] for k in out if tag in k and not k.startswith("prior_")}
         return res

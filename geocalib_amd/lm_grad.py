@@ -55,16 +55,17 @@ def _model_fields(camera: BaseCamera, gravity: Gravity, hw: Tuple[int, int], use
     return torch.cat(rows, -1)
 
 
-def _full_update(camera: BaseCamera, gravity: Gravity, delta: torch.Tensor) -> Tuple[BaseCamera, Gravity]:
-    """theta [+] delta over the full columns (d1, d2, log focal, k...)."""
-    g = gravity.update(delta[..., :2], spherical=True)
-    c = camera.update_focal(delta[..., 2:3], as_log=True)
+def _full_update(camera: BaseCamera, gravity: Gravity, delta: torch.Tensor, rpf: bool = False) -> Tuple[BaseCamera, Gravity]:
+    """theta [+] delta over the full columns (d1, d2, log focal, k...); `rpf`: over (roll, pitch, plain focal, k...), the
+    parametrisation of the uncertainty pass."""
+    g = gravity.update(delta[..., :2], spherical=not rpf)
+    c = camera.update_focal(delta[..., 2:3], as_log=not rpf)
     if hasattr(c, "dist"):
         c = c.update_dist(delta[..., 3:3 + c.num_dist_params()])
     return c, g
 
 
-def fields_and_jacobian(camera: BaseCamera, gravity: Gravity, hw: Tuple[int, int], use_up: bool = True):
+def fields_and_jacobian(camera: BaseCamera, gravity: Gravity, hw: Tuple[int, int], use_up: bool = True, rpf: bool = False):
     """(model (B, N, R), J (B, N, R, P)) with R = 3 rows [up_x, up_y, sin latitude] (1 without the up field) and P = 3 +
     the model's distortion parameters: J[..., j] is the forward-mode derivative of fields(theta [+] delta) along column j
     at delta = 0, on the spherical manifold and the log focal length.  Both carry the autograd graph of (camera, gravity)."""
@@ -76,7 +77,7 @@ def fields_and_jacobian(camera: BaseCamera, gravity: Gravity, hw: Tuple[int, int
         e = torch.zeros_like(zero)
         e[:, j] = 1
         with fwAD.dual_level():
-            c, g = _full_update(camera, gravity, fwAD.make_dual(zero, e))
+            c, g = _full_update(camera, gravity, fwAD.make_dual(zero, e), rpf)
             out = fwAD.unpack_dual(_model_fields(c, g, hw, use_up))
             if model is None:
                 model = out.primal
@@ -92,6 +93,57 @@ def _initial_estimate(opt: LMOptimizer, data: Dict[str, Any], dtype: torch.dtype
     return opt.camera_model(camera._data.detach().to(dtype)), Gravity(gravity._data.detach().to(dtype))
 
 
+def _soft_priors(data: Dict[str, Any], dtype: torch.dtype, B: int, device) -> Dict[str, torch.Tensor]:
+    """The soft priors of `data` in `dtype`: {"f0", "sf"} and / or {"g0", "sg"} -- a prior with its standard deviation
+    (`prior_focal_uncertainty` in pixels of fy, `prior_gravity_uncertainty` in radians); empty without either."""
+    out = {}
+
+    def vec(key, shape):
+        t = data[key]
+        t = t._data if hasattr(t, "_data") else torch.as_tensor(t)
+        return t.detach().to(device=device, dtype=dtype).reshape(shape)
+
+    for key, prior in (("prior_focal_uncertainty", "prior_focal"), ("prior_gravity_uncertainty", "prior_gravity")):
+        if key in data and prior not in data:
+            raise ValueError(f"lm_unrolled_torch: `{key}` needs `{prior}`")
+    if "prior_focal_uncertainty" in data:
+        out["f0"], out["sf"] = vec("prior_focal", (B,)), vec("prior_focal_uncertainty", (B,))
+    if "prior_gravity_uncertainty" in data:
+        g0 = vec("prior_gravity", (B, 3))
+        out["g0"], out["sg"] = g0 / g0.norm(dim=-1, keepdim=True), vec("prior_gravity_uncertainty", (B,))
+    return out
+
+
+def soft_prior_terms(soft: Dict[str, torch.Tensor], camera: BaseCamera, gravity: Gravity, dims, rpf: bool = False):
+    """(cost (B,), G (B, P), H (B, P, P)) of the soft priors at (camera, gravity) over the free columns `dims`, in the
+    sum convention of the data terms (cost sum rho, H = sum w J^T J, G = sum w J^T r, r = target - model):
+      focal    w = (f0 / sigma_f)^2, r = log f0 - log fy on the log-focal column;
+      gravity  w = 1 / sigma_g^2, r = g0 - g, J = T, the tangent basis of the gravity columns (SphericalManifold.J_plus).
+    `rpf`: the information in the uncertainty pass's parametrisation -- T = Gravity.J_rp, 1 / sigma_f^2 on the plain focal --
+    with the same cost; G is then zero (the pass takes no step)."""
+    fy = camera.f[..., 1]
+    B, P = fy.shape[0], len(dims)
+    cost, G, H = fy.new_zeros(B), fy.new_zeros(B, P), fy.new_zeros(B, P, P)
+    if "sf" in soft:
+        j = dims.index(2)
+        w, r = (soft["f0"] / soft["sf"]) ** 2, torch.log(soft["f0"] / fy)
+        cost = cost + w * r * r
+        if rpf:
+            H[:, j, j] = H[:, j, j] + 1 / soft["sf"] ** 2
+        else:
+            G[:, j] = G[:, j] + w * r
+            H[:, j, j] = H[:, j, j] + w
+    if "sg" in soft:
+        assert dims[:2] == [0, 1]
+        w, r = 1 / soft["sg"] ** 2, soft["g0"] - gravity.vec3d
+        T = gravity.J_rp() if rpf else gravity.J_update(spherical=True)
+        cost = cost + w * (r * r).sum(-1)
+        if not rpf:
+            G[:, :2] = G[:, :2] + w[:, None] * torch.einsum("bik,bi->bk", T, r)
+        H[:, :2, :2] = H[:, :2, :2] + w[:, None, None] * torch.einsum("bik,bil->bkl", T, T)
+    return cost, G, H
+
+
 def lm_unrolled_torch(data: Dict[str, Any], conf: Optional[Dict[str, Any]] = None, dtype: torch.dtype = torch.float64,
                       init: Optional[Tuple[BaseCamera, Gravity]] = None, detach_init: bool = True) -> Dict[str, Any]:
     """The unrolled LM loop of LMOptimizer(conf) on `data`, in `dtype`, differentiable by autograd with respect to
@@ -103,7 +155,12 @@ def lm_unrolled_torch(data: Dict[str, Any], conf: Optional[Dict[str, Any]] = Non
     stands, and autograd also reaches the state the loop starts from -- the state adjoint of a step (num_steps=1).
     Returns the dict of LMOptimizer.forward in training mode -- "camera", "gravity", "stop_at", the initial and final costs --
     plus "lambdas" (num executed steps, B), the damping after each step's rule, "deltas", the steps taken, and "hessians", each
-    step's J^T W J over the free columns, before the damping."""
+    step's J^T W J over the free columns, before the damping.
+
+    Soft priors (`prior_focal_uncertainty`, `prior_gravity_uncertainty` in `data`, each with its prior; LMOptimizer documents
+    them): the prior seeds the initial estimate and keeps its column free, `soft_prior_terms` joins every step's system (the
+    "hessians" are then the systems as solved) and prior / N the compared cost; the dict gains "initial_prior_cost" and
+    "final_prior_cost", and "initial_cost" / "final_cost" are the compared sums.  Without those keys nothing changes."""
     opt = LMOptimizer(dict(conf or {}))
     c = opt.conf
     if c.shared_intrinsics or not (c.use_spherical_manifold and c.use_log_focal):
@@ -147,6 +204,8 @@ def lm_unrolled_torch(data: Dict[str, Any], conf: Optional[Dict[str, Any]] = Non
 
     total = lambda costs: sum(v.mean(-1) for v in costs.values())  # noqa: E731
     dims = opt._column_dims()
+    soft = _soft_priors(data, dtype, B, d["latitude_field"].device)
+    prior_mean = lambda cam, grav: soft_prior_terms(soft, cam, grav, dims)[0] / (h * w)  # noqa: E731
     lamb = d["latitude_field"].new_full((B,), float(c.lambda_))
     infos: Dict[str, Any] = {"stop_at": opt.num_steps}
     lambdas, deltas, hessians, prev_cost = [], [], [], None
@@ -156,11 +215,17 @@ def lm_unrolled_torch(data: Dict[str, Any], conf: Optional[Dict[str, Any]] = Non
         if i == 0:
             prev_cost = total(costs)
             infos.update({f"initial_{k}": v.mean(-1) for k, v in costs.items()})
+            if soft:
+                infos["initial_prior_cost"] = prior_mean(camera, gravity)
+                prev_cost = prev_cost + infos["initial_prior_cost"]
             infos["initial_cost"] = prev_cost
         J = J[..., dims]
         wr = wt * r
         G = torch.einsum("bnrk,bnr->bk", J, wr)
         Hm = torch.einsum("bnrk,bnr,bnrl->bkl", J, wt, J)
+        if soft:
+            _, Gp, Hp = soft_prior_terms(soft, camera, gravity, dims)
+            G, Hm = G + Gp, Hm + Hp
         damp = (Hm.diagonal(dim1=-2, dim2=-1) * lamb[:, None]).clamp(min=1e-6)
         A = Hm + torch.diag_embed(damp)
         L, fail = torch.linalg.cholesky_ex(A)
@@ -172,6 +237,8 @@ def lm_unrolled_torch(data: Dict[str, Any], conf: Optional[Dict[str, Any]] = Non
         hessians.append(Hm.detach())
         camera, gravity = opt.update_estimate(camera, gravity, delta)
         new_cost = total(costs_weights(_model_fields(camera, gravity, (h, w), use_up))[0])
+        if soft:
+            new_cost = new_cost + prior_mean(camera, gravity)
         if not c.fix_lambda:
             lamb = update_lambda(lamb, prev_cost.detach(), new_cost.detach())
         lambdas.append(lamb.detach().clone())
@@ -184,6 +251,9 @@ def lm_unrolled_torch(data: Dict[str, Any], conf: Optional[Dict[str, Any]] = Non
     infos["stop_at"] = camera._data.new_ones(B) * infos["stop_at"]
     infos.update({f"final_{k}": v.mean(-1) for k, v in final.items()})
     infos["final_cost"] = total(final)
+    if soft:
+        infos["final_prior_cost"] = prior_mean(camera, gravity)
+        infos["final_cost"] = infos["final_cost"] + infos["final_prior_cost"]
     infos["lambdas"] = torch.stack(lambdas) if lambdas else lamb.new_zeros((0, B))
     infos["deltas"] = torch.stack(deltas) if deltas else lamb.new_zeros((0, B, len(dims)))
     infos["hessians"] = torch.stack(hessians) if hessians else lamb.new_zeros((0, B, len(dims), len(dims)))

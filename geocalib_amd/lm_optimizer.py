@@ -216,10 +216,11 @@ class LMOptimizer(nn.Module):
 
     def setup_optimization_and_priors(self, data: Dict[str, torch.Tensor] = None,
                                       shared_intrinsics: bool = False) -> None:
-        """Which parameters are free given the priors in `data` (reference: lm_optimizer.py:189-246)."""
+        """Which parameters are free given the priors in `data` (reference: lm_optimizer.py:189-246).  A prior given with its
+        uncertainty (`prior_focal_uncertainty`, `prior_gravity_uncertainty`: a soft prior) keeps its column free."""
         data = data or {}
-        estimate_gravity = "prior_gravity" not in data
-        estimate_focal = "prior_focal" not in data
+        estimate_gravity = "prior_gravity" not in data or "prior_gravity_uncertainty" in data
+        estimate_focal = "prior_focal" not in data or "prior_focal_uncertainty" in data
         estimate_dist = self.camera_has_distortion and "prior_dist" not in data
         gravity_delta_dims = (0, 1) if estimate_gravity else (-1,)
         focal_delta_dims = (max(gravity_delta_dims) + 1,) if estimate_focal else (-1,)
@@ -354,6 +355,9 @@ class LMOptimizer(nn.Module):
                  record: torch.Tensor = None) -> Tuple[BaseCamera, Gravity, Dict[str, torch.Tensor]]:
         """All LM steps + final costs + uncertainty on the device (reference: lm_optimizer.py:551-644).  `record`: the step
         record of gclm_solve_recorded, (B, num_steps, _lib.LM_RECORD_STRIDE) float32 (lm_grad.recorded_solve)."""
+        if any(k in data for k, _ in self._SOFT_KEYS):
+            raise ValueError("LMOptimizer soft priors: `optimize` from an explicit initial estimate does not cover them; "
+                             "use `forward` / `calibrate_fields`")
         up, lat, upc, latc, (B, H, W) = self._fields(data)
         slat = self._sin_lat(data, lat)
         device = lat.device
@@ -372,7 +376,39 @@ class LMOptimizer(nn.Module):
         self._last_raw = (cam, grav, info)     # packed device results (parallel.calibrate_sharded)
         return camera_opt.__class__(cam), _unit_gravity(grav), self._unpack_info(info, up is not None)
 
-    def _unpack_info(self, info: torch.Tensor, has_up: bool) -> Dict[str, torch.Tensor]:
+    _SOFT_KEYS = (("prior_focal_uncertainty", "prior_focal"), ("prior_gravity_uncertainty", "prior_gravity"))
+
+    def check_soft_priors(self, data: Dict[str, Any]) -> bool:
+        """Whether `data` holds a soft prior -- `prior_focal_uncertainty` (B,) in pixels of fy at the solve's resolution with
+        `prior_focal`, `prior_gravity_uncertainty` (B,) in radians with `prior_gravity` -- and, if so, that this optimiser
+        covers it: anything else raises a ValueError that names the limit, before the library is touched.  An uncertainty
+        that lives on the CPU is checked for finite, positive values here; one on the device is not read back (no host
+        synchronisation): the kernel leaves the term of such an image out and counts its LM steps into `step_failures`."""
+        soft = [k for k, _ in self._SOFT_KEYS if k in data]
+        if not soft:
+            return False
+        c, who = self.conf, "LMOptimizer soft priors"
+        for key, prior in self._SOFT_KEYS:
+            if key in data and prior not in data:
+                raise ValueError(f"{who}: `{key}` needs `{prior}`: an uncertainty without its prior")
+        if self.shared_intrinsics or c.shared_intrinsics:
+            raise ValueError(f"{who}: per-image solves only (shared_intrinsics=False)")
+        if c.differentiable:
+            raise ValueError(f"{who}: not covered by differentiable=True (the adjoint of the LM steps has no prior terms)")
+        if self._init_name == "ransac":
+            raise ValueError(f"{who}: init_conf trivial or heuristic only, got `ransac` (the minimal solver takes no soft prior)")
+        if not (c.use_spherical_manifold and c.use_log_focal):
+            raise ValueError(f"{who}: use_spherical_manifold and use_log_focal must stay True")
+        B = data["latitude_field"].shape[0]
+        for key in soft:
+            t = torch.as_tensor(data[key])
+            if t.numel() != B:
+                raise ValueError(f"{who}: `{key}` must hold one value per image ({B}), got shape {tuple(t.shape)}")
+            if t.device.type == "cpu" and not bool((torch.isfinite(t) & (t > 0)).all()):
+                raise ValueError(f"{who}: `{key}` must be finite and > 0")
+        return True
+
+    def _unpack_info(self, info: torch.Tensor, has_up: bool, prior_cost: torch.Tensor = None) -> Dict[str, torch.Tensor]:
         I = _lib.INFO
         # column k of the packed rows, for the 15 scalar columns in ONE call (15 separate integer selects were 12 us of a
         # 38 us host path; scripts/probes/host_overhead_probe.py)
@@ -394,10 +430,14 @@ class LMOptimizer(nn.Module):
         out["final_latitude_cost"] = col[I["final_latitude_cost"]]
         out["final_cost"] = col[I["final_cost"]]
         out["step_failures"] = col[I["step_failures"]]
+        if prior_cost is not None:       # soft priors: prior cost / N, part of initial_cost / final_cost
+            out["initial_prior_cost"], out["final_prior_cost"] = prior_cost.unbind(1)
         return out
 
     def forward(self, data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """Run the LM optimisation (reference: lm_optimizer.py:646-664)."""
+        data["latitude_field"]                # KeyError like get_trivial_estimation (lm_optimizer.py:31)
+        self.check_soft_priors(data)
         if self.conf.differentiable:
             from . import lm_grad
             return lm_grad.differentiable_forward(self, data)
@@ -475,7 +515,7 @@ class LMOptimizer(nn.Module):
                            "the batch-global stop is evaluated per slice (pass early_stop=False for slice-independent "
                            "results)", B, self._MAX_CALL)
         per_image = ("up_field", "latitude_field", "up_confidence", "latitude_confidence", "sin_latitude", "prior_focal",
-                     "prior_gravity", "prior_dist")
+                     "prior_gravity", "prior_dist", "prior_focal_uncertainty", "prior_gravity_uncertainty")
         cams, gravs, infos, raws = [], [], [], []
         for lo, n in _call.slices(B):
             part = {k: (v[lo:lo + n] if k in per_image else v) for k, v in data.items()}
@@ -490,6 +530,9 @@ class LMOptimizer(nn.Module):
         """get_trivial_estimation + optimize in ONE C call (gclm_calibrate): the initial estimate is built
         on the device from (H, W) and the priors, so no host-side tensor op precedes the kernels.  `record`: the step
         record of gclm_calibrate_recorded (lm_grad.recorded_solve; one call, never split or overlapped)."""
+        soft = self.check_soft_priors(data)
+        if soft and record is not None:
+            raise ValueError("LMOptimizer soft priors: the recorded solve does not cover them")
         up, lat, upc, latc, (B, H, W) = self._fields(data)
         if B > self._MAX_CALL:
             assert record is None, "the recorded solve is one call"
@@ -511,6 +554,9 @@ class LMOptimizer(nn.Module):
         scales = prior("scales", (2,))
         pf = prior("prior_focal", (B,))
         pg = prior("prior_gravity", (B, 3))
+        sf = prior("prior_focal_uncertainty", (B,))
+        sg = prior("prior_gravity_uncertainty", (B,))
+        pcost = torch.empty((B, 2), dtype=torch.float32, device=device) if soft else None
         nd = self.num_dist
         pd = prior("prior_dist") if nd else None       # (B,) or (B, k): its own width is the number of given parameters
         if pd is not None:
@@ -525,13 +571,16 @@ class LMOptimizer(nn.Module):
             _call.call("gclm_calibrate_recorded", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg), P(pd), nd,
                        cam.data_ptr(), grav.data_ptr(), info.data_ptr(), record.data_ptr(), stream, handle=h.ptr)
         elif n_over > 1:
-            self._calibrate_overlapped(n_over, device, (up, lat, upc, latc, slat), (B, H, W), scales, (pf, pg, pd), nd,
-                                       (cam, grav, info))
+            self._calibrate_overlapped(n_over, device, (up, lat, upc, latc, slat), (B, H, W), scales, (pf, pg, pd, sf, sg), nd,
+                                       (cam, grav, info, pcost))
+        elif soft:
+            _call.call("gclm_calibrate_soft", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg), P(pd), nd,
+                       P(sf), P(sg), cam.data_ptr(), grav.data_ptr(), info.data_ptr(), pcost.data_ptr(), P(slat), stream, handle=h.ptr)
         else:
             _call.call("gclm_calibrate_ex", h.ptr, P(up), P(lat), P(upc), P(latc), B, H, W, P(scales), P(pf), P(pg), P(pd), nd,
                        cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), stream, handle=h.ptr)
         self._last_raw = (cam, grav, info)
-        return self.camera_model(cam), _unit_gravity(grav), self._unpack_info(info, up is not None)
+        return self.camera_model(cam), _unit_gravity(grav), self._unpack_info(info, up is not None, pcost)
 
     # Host-side knob without a reference counterpart.  n > 1: a large batch of INDEPENDENT images with a fixed step count
     # is solved as n contiguous parts on n side streams (forked from / joined to the caller's stream with events), so that
@@ -621,10 +670,15 @@ class LMOptimizer(nn.Module):
             _call.call("gclm_set_conf_pack", h.ptr, int(bool(pack)), handle=h.ptr)
             h.conf_pack = int(bool(pack))                   # (what _Handle.set_conf_pack remembers)
             up, lat, upc, latc, slat = (part(t, lo, hi) for t in fields)
-            pf, pg, pd = (part(t, lo, hi) for t in priors)
-            cam, grav, info = (t[lo:hi] for t in outs)
-            _call.call("gclm_calibrate_ex", h.ptr, P(up), P(lat), P(upc), P(latc), hi - lo, H, W, P(scales), P(pf), P(pg), P(pd),
-                       nd, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), s.cuda_stream, handle=h.ptr)
+            pf, pg, pd, sf, sg = (part(t, lo, hi) for t in priors)
+            cam, grav, info, pcost = (part(t, lo, hi) for t in outs)
+            if pcost is None:
+                _call.call("gclm_calibrate_ex", h.ptr, P(up), P(lat), P(upc), P(latc), hi - lo, H, W, P(scales), P(pf), P(pg), P(pd),
+                           nd, cam.data_ptr(), grav.data_ptr(), info.data_ptr(), P(slat), s.cuda_stream, handle=h.ptr)
+            else:
+                _call.call("gclm_calibrate_soft", h.ptr, P(up), P(lat), P(upc), P(latc), hi - lo, H, W, P(scales), P(pf), P(pg),
+                           P(pd), nd, P(sf), P(sg), cam.data_ptr(), grav.data_ptr(), info.data_ptr(), pcost.data_ptr(), P(slat),
+                           s.cuda_stream, handle=h.ptr)
             handles.append(h)
             cur.wait_event(s.record_event())                # join: whatever follows on the caller's stream sees the results
         # infos["stop_at"] is ONE number for the whole batch (the first step after which every image's cost was close,

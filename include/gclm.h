@@ -64,7 +64,9 @@ extern "C" {
  * gclm_pack_fields_typed and gclm_pack_fields_backward added, also within 610: the head epilogue for float16 / bfloat16 raw
  * planes, and its backward -- the gradients of the fields and confidences taken back to the raw head outputs in one pass;
  * gclm_field_loss_param_grad, gclm_perspective_fields_backward and gclm_field_param_grad_workspace added, also within 610: the
- * gradients of the field losses, and of the rendered fields, with respect to the camera and the gravity).
+ * gradients of the field losses, and of the rendered fields, with respect to the camera and the gravity;
+ * gclm_calibrate_soft added, also within 610: gclm_calibrate_ex with a focal and a gravity prior given with their standard
+ * deviations, as pseudo-observations of every LM step and of the uncertainty pass).
  * gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
@@ -267,6 +269,43 @@ int gclm_calibrate_recorded(gclm_handle* h, const float* d_up, const float* d_la
                             const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
                             int prior_dist_cols, float* d_cam_out, float* d_grav_out, float* d_info_out,
                             float* d_record, void* stream);
+
+/*
+ * gclm_calibrate_ex with SOFT priors: a prior given together with its standard deviation is not frozen but enters every LM
+ * step, the compared cost and the uncertainty pass as one more observation.  An extension (the reference's priors are all
+ * or nothing), in the reference's conventions: cost = sum rho / N, H = sum w J^T J, G = sum w J^T r with r = target - model,
+ * step (H + damp) delta = G, Cov = H^-1.
+ *   d_prior_focal_sigma    (B,) or NULL  standard deviation of d_prior_focal, in pixels of fy; needs d_prior_focal and
+ *                                        cfg.estimate_focal == 1 (the column stays free)
+ *   d_prior_gravity_sigma  (B,) or NULL  isotropic standard deviation of d_prior_gravity, in radians; needs d_prior_gravity
+ *                                        and cfg.estimate_gravity == 1
+ *   d_prior_cost_out       (B,2) or NULL the priors' cost / N at the initial and at the final state
+ * Both in the units of the solve's own covariance (GCLM_INFO_COV: unit residual noise), not of a calibrated physical noise.
+ * A prior without its sigma is the hard prior of gclm_calibrate (its estimate_* flag 0); the two may be mixed.  Either prior
+ * seeds the initial estimate exactly as the hard one does.  At state (g, fy), per LM step, added to the image's reduced system:
+ *   focal    on the log-focal column: w = (f0 / sigma_f)^2, r = log f0 - log fy;  G[2] += w r, H[2][2] += w, cost += w r^2
+ *   gravity  g0 = normalize(prior), w = 1 / sigma_g^2, r = g0 - g, T the 3x2 tangent basis of the gravity columns;
+ *            G[0:2] += w T^T r, H[0:2,0:2] += w T^T T, cost += w |r|^2
+ * The cost that the damping rule and the early stop compare is up + latitude + prior / N, each term at the same state;
+ * GCLM_INFO_INITIAL_COST and GCLM_INFO_FINAL_COST are those sums (final: the float32 sum (up + latitude) + prior / N of the
+ * values reported), the up and latitude slots stay the data's.  The uncertainty pass adds T^T T / sigma_g^2 (T: the roll-pitch
+ * tangent) and 1 / sigma_f^2 on the plain-focal diagonal before the inverse: the covariance is the posterior's.
+ * A sigma that is not finite and > 0 (or a prior focal that is not, or a prior gravity that does not normalise) leaves its term
+ * out for that image and counts one into GCLM_INFO_STEP_FAILURES per LM step.  A sigma so large that its weight underflows
+ * adds exact zeros: the result is the two-launch solve's without the prior, bit for bit.
+ * The LM step of such a call is always two launches (sweep, per-image update): the priors are added by the update kernel.
+ * With both sigma pointers NULL the call is gclm_calibrate_ex exactly (d_prior_cost_out is not written).  Otherwise it returns
+ * -3, before the handle is looked at and before any HIP call, for a sigma without its prior, B <= 0 or beyond 65535, H or W
+ * <= 0, a NULL latitude or output, prior_dist_cols outside 1 .. 2, a pointer that is not 4-byte aligned, or an output that
+ * overlaps another range of the call; then -1 for a NULL handle, -3 for shared_intrinsics or use_spherical_manifold /
+ * use_log_focal off, and -2 where an estimate_* flag disagrees with the priors (a soft prior's flag is 1).
+ */
+int gclm_calibrate_soft(gclm_handle* h, const float* d_up, const float* d_lat, const float* d_up_conf,
+                        const float* d_lat_conf, int B, int H, int W, const float* d_scales,
+                        const float* d_prior_focal, const float* d_prior_gravity, const float* d_prior_dist,
+                        int prior_dist_cols, const float* d_prior_focal_sigma, const float* d_prior_gravity_sigma,
+                        float* d_cam_out, float* d_grav_out, float* d_info_out, float* d_prior_cost_out,
+                        const float* d_sin_lat, void* stream);
 
 /*
  * gclm_lm_backward: the adjoint of the LM steps of a recorded solve (no handle).  Given the gradients of a scalar with respect
