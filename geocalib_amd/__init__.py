@@ -18,7 +18,9 @@ Public surface (mirrors the reference's geocalib package for this path):
                                         fields, batched; perspective_opt.cost_function: its cost and gradient in one pass)
     losses                              siclib/models/decoders/{up,latitude,perspective}_decoder.py: calculate_losses, loss
                                         (perspective_field_loss: the heads' training losses against a calibration,
-                                        differentiable in the predicted fields, one HIP pass each way)
+                                        differentiable in the predicted fields, one HIP pass each way;
+                                        perspective_bin_loss: the classification heads' cross-entropy against a calibration's
+                                        bins, differentiable in the logits, one HIP pass each way)
     pack_fields                         geocalib/geocalib.py:57,73-75  (fields.pack_fields: the heads' epilogue in one HIP pass,
                                         float32 / float16 / bfloat16 raws; with a raw that requires grad the outputs carry a
                                         graph and backward is one more pass -- raw head outputs -> fields -> {losses, LM})
@@ -33,7 +35,7 @@ from . import viz  # noqa: F401,E402
 from . import perspective_encoding  # noqa: F401,E402
 from .perspective_opt import PerspectiveParamOpt  # noqa: F401,E402
 from . import losses  # noqa: F401,E402
-from .losses import perspective_decoder_loss, perspective_field_loss  # noqa: F401,E402
+from .losses import perspective_bin_loss, perspective_decoder_loss, perspective_field_loss  # noqa: F401,E402
 from . import lm_grad  # noqa: F401,E402
 from .fields import pack_fields  # noqa: F401,E402
 

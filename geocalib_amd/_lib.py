@@ -156,6 +156,10 @@ _SIGNATURES = {
     "gclm_field_loss": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P,
                                   _P]),
     "gclm_field_loss_grad": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gclm_bin_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gclm_bin_loss": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t,
+                                _P, _P, _P, _P]),
+    "gclm_bin_loss_grad": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gclm_field_param_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "gclm_field_loss_param_grad": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P,
                                              C.c_size_t, _P, _P, _P]),

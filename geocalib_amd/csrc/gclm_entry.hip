@@ -1,5 +1,5 @@
 // gclm_entry.hip -- the entry points of include/gclm.h that take no handle: the stage kernels, the head epilogue and the
-// upsampler, the five render kernels, the field errors, the field losses and their gradients (to the fields, and to the camera and gravity), the adjoint of the LM steps, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
+// upsampler, the five render kernels, the field errors, the field losses and their gradients (to the fields, and to the camera and gravity), the classification heads' loss and its gradient, the adjoint of the LM steps, the hypothesis scores, the minimal solver, the Adam optimiser on (roll, pitch, vfov), the synthetic fields and the read probe.  Each checks its arguments
 // before the first HIP call -- plain conditions first, then the ranges the call writes and reads over the one checker,
 // gclm_args.h -- and launches on the caller's stream and current device.  Host code only: this unit holds no kernel.
 #include <cfloat>
@@ -112,6 +112,17 @@ bool field_loss_plain_ok(int camera_model, const float* d_cam, const float* d_gr
     if (up_loss < GCLM_FIELD_LOSS_L1 || up_loss > GCLM_FIELD_LOSS_HUBER || lat_loss < GCLM_FIELD_LOSS_L1 || lat_loss > GCLM_FIELD_LOSS_HUBER)
         return false;
     return lat_loss != GCLM_FIELD_LOSS_DOT;
+}
+
+// gclm_bin_loss / gclm_bin_loss_grad: the plain conditions the two share -- at least one head, a head's count in range (an
+// absent head's count is not looked at), a confidence only beside its head, a known logit type, sizes of the right sign
+bool bin_loss_plain_ok(const void* d_up_logits, int up_bins, const void* d_lat_logits, int lat_bins, int logit_dtype,
+                       const float* d_up_conf, const float* d_lat_conf, int B, int H, int W) {
+    if ((!d_up_logits && !d_lat_logits) || (!d_up_logits && d_up_conf) || (!d_lat_logits && d_lat_conf)) return false;
+    if (d_up_logits && (up_bins < 2 || up_bins > GCLM_MAX_BINS)) return false;
+    if (d_lat_logits && (lat_bins < 1 || lat_bins > GCLM_MAX_BINS)) return false;
+    if (logit_dtype != GCLM_LOGITS_F32 && logit_dtype != GCLM_LOGITS_F16 && logit_dtype != GCLM_LOGITS_BF16) return false;
+    return B >= 0 && H >= 1 && W >= 1;
 }
 }  // namespace
 
@@ -433,6 +444,57 @@ int gclm_field_loss_grad(int camera_model, const float* d_cam, const float* d_gr
     if (!a.pass()) return -3;
     return launched(launch_field_loss_grad(camera_model, d_cam, d_grav, B, H, W, d_up, d_lat, d_up_conf, d_lat_conf, up_loss, lat_loss,
                                            d_scale, d_grad_up, d_grad_lat, static_cast<hipStream_t>(stream)));
+}
+
+size_t gclm_bin_loss_workspace(int B, int H, int W) { return bin_loss_workspace(B, H, W); }
+
+int gclm_bin_loss(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const void* d_up_logits, int up_bins,
+                  const void* d_lat_logits, int lat_bins, int logit_dtype, const float* d_up_conf, const float* d_lat_conf,
+                  void* d_workspace, size_t workspace_bytes, float* d_out, float* d_lse, int16_t* d_bins, void* stream) {
+    if (!d_cam || !d_grav || !d_workspace || !d_out || !d_lse || !d_bins || !known_model(camera_model)) return -3;
+    if (!bin_loss_plain_ok(d_up_logits, up_bins, d_lat_logits, lat_bins, logit_dtype, d_up_conf, d_lat_conf, B, H, W)) return -3;
+    if (B == 0) return 0;
+    const size_t ws_bytes = bin_loss_workspace(B, H, W);                         // 0: sizes out of range
+    if (ws_bytes == 0 || workspace_bytes < ws_bytes) return -3;
+    const size_t esize = logit_dtype == GCLM_LOGITS_F32 ? 4 : 2, px = floats(B, H, W);
+    ArgCheck a;
+    a.writes(d_out, floats(B, 6), 4);
+    a.writes(d_lse, mul_sat(px, 2), 4);
+    a.writes(d_bins, elements<int16_t>(B, 2, H, W), 2);
+    a.writes(d_workspace, ws_bytes, 4);
+    a.reads(d_cam, floats(B, 8), 4);
+    a.reads(d_grav, floats(B, 3), 4);
+    a.reads(d_up_logits, mul_sat(elements<char>(B, up_bins, H, W), esize), esize);
+    a.reads(d_lat_logits, mul_sat(elements<char>(B, lat_bins, H, W), esize), esize);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    if (!a.pass()) return -3;
+    return launched(launch_bin_loss(camera_model, d_cam, d_grav, B, H, W, d_up_logits, up_bins, d_lat_logits, lat_bins, logit_dtype,
+                                    d_up_conf, d_lat_conf, d_workspace, d_out, d_lse, d_bins, static_cast<hipStream_t>(stream)));
+}
+
+int gclm_bin_loss_grad(const void* d_up_logits, int up_bins, const void* d_lat_logits, int lat_bins, int logit_dtype,
+                       const float* d_up_conf, const float* d_lat_conf, int B, int H, int W, const float* d_lse, const int16_t* d_bins,
+                       const float* d_scale, void* d_grad_up, void* d_grad_lat, void* stream) {
+    if (!d_lse || !d_bins || !d_scale || (!d_grad_up && !d_grad_lat) || (d_grad_up && !d_up_logits) || (d_grad_lat && !d_lat_logits)) return -3;
+    if (!bin_loss_plain_ok(d_up_logits, up_bins, d_lat_logits, lat_bins, logit_dtype, d_up_conf, d_lat_conf, B, H, W)) return -3;
+    if (B == 0) return 0;
+    if (bin_loss_workspace(B, H, W) == 0) return -3;                             // (the sizes the forward refuses)
+    const size_t esize = logit_dtype == GCLM_LOGITS_F32 ? 4 : 2, px = floats(B, H, W);
+    const size_t up_bytes = mul_sat(elements<char>(B, up_bins, H, W), esize), lat_bytes = mul_sat(elements<char>(B, lat_bins, H, W), esize);
+    ArgCheck a;
+    a.writes(d_grad_up, up_bytes, esize);
+    a.writes(d_grad_lat, lat_bytes, esize);
+    a.reads(d_up_logits, up_bytes, esize);
+    a.reads(d_lat_logits, lat_bytes, esize);
+    a.reads(d_up_conf, px, 4);
+    a.reads(d_lat_conf, px, 4);
+    a.reads(d_lse, mul_sat(px, 2), 4);
+    a.reads(d_bins, elements<int16_t>(B, 2, H, W), 2);
+    a.reads(d_scale, floats(B, 2), 4);
+    if (!a.pass()) return -3;
+    return launched(launch_bin_loss_grad(B, H, W, d_up_logits, up_bins, d_lat_logits, lat_bins, logit_dtype, d_up_conf, d_lat_conf, d_lse,
+                                         d_bins, d_scale, d_grad_up, d_grad_lat, static_cast<hipStream_t>(stream)));
 }
 
 size_t gclm_field_param_grad_workspace(int B, int H, int W) { return field_param_grad_workspace(B, H, W); }

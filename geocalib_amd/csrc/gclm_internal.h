@@ -293,6 +293,15 @@ hipError_t launch_field_loss_grad(int camera_model, const float* cam, const floa
                                   const float* lat, const float* upc, const float* latc, int up_loss, int lat_loss, const float* scale,
                                   float* grad_up /* or nullptr */, float* grad_lat /* or nullptr */, hipStream_t s);
 
+// gclm_bin_loss.hip
+size_t bin_loss_workspace(int B, int H, int W);                           // bytes of one call's tile records; 0: sizes out of range
+hipError_t launch_bin_loss(int camera_model, const float* cam, const float* grav, int B, int H, int W, const void* up_logits /* or nullptr */,
+                           int Ku, const void* lat_logits /* or nullptr */, int Kl, int dtype, const float* upc, const float* latc,
+                           void* workspace, float* out, float* lse, int16_t* bins, hipStream_t s);
+hipError_t launch_bin_loss_grad(int B, int H, int W, const void* up_logits, int Ku, const void* lat_logits, int Kl, int dtype,
+                                const float* upc, const float* latc, const float* lse, const int16_t* bins, const float* scale,
+                                void* grad_up /* or nullptr */, void* grad_lat /* or nullptr */, hipStream_t s);
+
 // gclm_field_param_grad.hip
 size_t field_param_grad_workspace(int B, int H, int W);                   // bytes of one call's tile records; 0: sizes out of range
 hipError_t launch_field_loss_param_grad(int camera_model, const float* cam, const float* grav, int B, int H, int W, const float* up,

@@ -1,7 +1,7 @@
-// gclm_render.h -- the per-pixel core of the one-pass kernels over the tile geometry below.  Included by eleven kernel files --
+// gclm_render.h -- the per-pixel core of the one-pass kernels over the tile geometry below.  Included by twelve kernel files --
 // the renderers gclm_image.hip, gclm_pano.hip, gclm_reproject.hip, gclm_persp.hip and gclm_overlay.hip, and the kernels that
 // score, fit or differentiate predicted fields, gclm_metrics.hip, gclm_hypotheses.hip, gclm_param_opt.hip,
-// gclm_field_loss.hip, gclm_field_param_grad.hip and gclm_lm_grad.hip -- and by gclm_entry.hip, for the bound on the tile grid: the camera models'
+// gclm_field_loss.hip, gclm_bin_loss.hip, gclm_field_param_grad.hip and gclm_lm_grad.hip -- and by gclm_entry.hip, for the bound on the tile grid: the camera models'
 // undistort and distort scales, the zero-padded bilinear sampler (float32 images, and uint8 images planar or interleaved
 // with their rounding store), the nontemporal store, the tile geometry, the perspective fields of one pixel, and the tile
 // walk of the second group ("The tile walk" below: pixels per lane, per-row terms, wave sum, tile record, chain sum).
@@ -274,8 +274,10 @@ __device__ __forceinline__ float persp_lat_slope(const PerspRow& r, float u, flo
 }
 
 // The tile walk of the kernels that reduce an image's pixels to a few numbers per image (gclm_metrics.hip,
-// gclm_hypotheses.hip, gclm_param_opt.hip, gclm_field_loss.hip, gclm_field_param_grad.hip, gclm_lm_grad.hip).  Every rule stands here
+// gclm_hypotheses.hip, gclm_param_opt.hip, gclm_field_loss.hip, gclm_bin_loss.hip, gclm_field_param_grad.hip, gclm_lm_grad.hip).  Every rule stands here
 // once; each kernel keeps its per-pixel body, its record layout and what its finish kernel makes of the sums.
+//   - (gclm_bin_loss.hip walks the same tiles with 8, 4 or 1 pixels per lane by its logits' type, and adds a lane's pixels in
+//     the one-pixel walk's tree so that its records do not depend on the width: see its header)
 //   - grid = (tiles of one image, .., images) over the tile geometry above, PX = 4, 2 or 1 pixels per lane
 //     (pixels_per_lane: by W and the planes' alignment; the planes of every image of a batch share the alignment of the
 //     first, so an image's path does not depend on its place in the batch); load_px / store_px move a lane's pixels.

@@ -12,7 +12,8 @@ a sixth: sin(latitude_field), which the LM solve reads in place of the radians (
 is the same step for classification heads (gclm_pack_fields_bins).  `pack_fields` reads float16 / bfloat16 raws as they are
 (gclm_pack_fields_typed) and, for raws that require grad, carries a graph whose backward is one more HIP pass
 (gclm_pack_fields_backward): with losses.perspective_field_loss and the differentiable LMOptimizer, everything after the
-network's last convolution is this package's, forward and backward."""
+network's last convolution is this package's, forward and backward -- for classification heads too: `bin_loss` /
+`bin_loss_grad` (gclm_bin_loss, gclm_bin_loss_grad) are the host wrappers behind losses.perspective_bin_loss."""
 import ctypes
 from typing import Dict, Optional
 
@@ -514,6 +515,93 @@ def field_loss_grad(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, sc
                    *(_call.ptr_at(t, b0) for t in planes.values()), *ids, scale[b0].data_ptr(), _call.ptr_at(g_up, b0),
                    _call.ptr_at(g_lat, b0), _call.raw_stream(dev), device=dev)
     return g_up, g_lat
+
+
+def _bin_loss_call(who: str, up_logits, lat_logits, up_conf, lat_conf):
+    """What bin_loss and bin_loss_grad share: the checked logits and confidences as their kernels read them -- (logits,
+    confidences, B, H, W, device, gclm_logit_dtype).  The logits are taken as they lie (contiguous, one of the three dtypes, one
+    device); a confidence is float32 (B, H, W)."""
+    given = [t for t in (up_logits, lat_logits) if t is not None]
+    if not given:
+        raise ValueError(f"{who}: at least one of the up and latitude logits is needed")
+    if (up_logits is None and up_conf is not None) or (lat_logits is None and lat_conf is not None):
+        raise ValueError(f"{who}: a confidence needs its logits")
+    first = given[0]
+    for t in given:
+        if t.dim() != 4 or t.dtype not in _LOGIT_DTYPES or t.dtype != first.dtype or t.device != first.device or \
+                t.shape[0] != first.shape[0] or t.shape[-2:] != first.shape[-2:] or not t.is_contiguous():
+            raise ValueError(f"{who}: logits are contiguous (B, bins, H, W) float32, float16 or bfloat16 tensors of one dtype, device, "
+                             f"B, H and W, got {[(tuple(t.shape), t.dtype, str(t.device)) for t in given]}")
+        _call.require_device(t, "logits")
+    B, (H, W), dev = first.shape[0], first.shape[-2:], first.device
+    if up_logits is not None and not 2 <= up_logits.shape[1] <= _lib.MAX_BINS or \
+            lat_logits is not None and not 1 <= lat_logits.shape[1] <= _lib.MAX_BINS:
+        raise ValueError(f"{who}: 2..{_lib.MAX_BINS} up bins and 1..{_lib.MAX_BINS} latitude bins, got "
+                         f"{[t.shape[1] for t in given]}")
+    confs = []
+    for name, c in (("up_conf", up_conf), ("lat_conf", lat_conf)):
+        if c is not None:
+            c = _call.dev_f32(c, name)
+            if c.numel() != B * H * W or c.shape[-2:] != (H, W) or c.device != dev:
+                raise ValueError(f"{who}: `{name}` {tuple(c.shape)} on {c.device} does not fit {B} images of {H} x {W} on {dev}")
+        confs.append(c)
+    logits = [None if t is None else t.detach() for t in (up_logits, lat_logits)]
+    return logits, confs, B, H, W, dev, _LOGIT_DTYPES[first.dtype]
+
+
+def bin_loss(camera_model: str, cam: torch.Tensor, grav: torch.Tensor, up_logits: Optional[torch.Tensor] = None,
+             lat_logits: Optional[torch.Tensor] = None, up_conf: Optional[torch.Tensor] = None,
+             lat_conf: Optional[torch.Tensor] = None):
+    """gclm_bin_loss: the cross-entropy of classification-head logits `up_logits` (B, Ku, H, W) / `lat_logits` (B, Kl, H, W) (one
+    may be None; float32, float16 or bfloat16, contiguous) against the bins of the fields of cameras `cam` (B, 8) and gravities
+    `grav` (B, 3), float32, all on one HIP device, in one pass per 65 535 images on torch's current stream.  A confidence
+    (B, H, W) weights its head's pixels; None is the plain mean.  Returns (out, lse, bins) as include/gclm.h lays them out: out
+    (B, 6) = [numerator, denominator, hits] of up, then of latitude (NaN for an absent head), lse (B, 2, H, W) float32 and bins
+    (B, 2, H, W) int16, which bin_loss_grad takes.  losses.perspective_bin_loss is the public entry."""
+    logits, confs, B, H, W, dev, dtype = _bin_loss_call("bin_loss", up_logits, lat_logits, up_conf, lat_conf)
+    cam, grav = _call.dev_f32(cam, "cam").reshape(-1, 8), _call.dev_f32(grav, "grav").reshape(-1, 3)
+    if cam.shape[0] != B or grav.shape[0] != B or cam.device != dev or grav.device != dev:
+        raise ValueError(f"camera batch {cam.shape[0]} on {cam.device} and gravity batch {grav.shape[0]} on {grav.device} must be {B} "
+                         f"on {dev}")
+    out = cam.new_empty((B, 6))
+    lse = cam.new_empty((B, 2, H, W))
+    bins = torch.empty((B, 2, H, W), dtype=torch.int16, device=dev)
+    if B * H * W == 0:
+        return out.fill_(float("nan")), lse, bins
+    counts = [0 if t is None else t.shape[1] for t in logits]
+    ws_bytes = int(_lib.load().gclm_bin_loss_workspace(min(B, _call.MAX_CALL), H, W))
+    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=dev)
+    for b0, n in _call.slices(B):
+        _call.call("gclm_bin_loss", _lib.CAMERA_MODEL_IDS[camera_model], cam[b0].data_ptr(), grav[b0].data_ptr(), n, H, W,
+                   _call.ptr_at(logits[0], b0), counts[0], _call.ptr_at(logits[1], b0), counts[1], dtype,
+                   _call.ptr_at(confs[0], b0), _call.ptr_at(confs[1], b0), ws.data_ptr(), ws_bytes, out[b0].data_ptr(),
+                   lse[b0].data_ptr(), bins[b0].data_ptr(), _call.raw_stream(dev), device=dev)
+    return out, lse, bins
+
+
+def bin_loss_grad(scale: torch.Tensor, lse: torch.Tensor, bins: torch.Tensor, up_logits: Optional[torch.Tensor] = None,
+                  lat_logits: Optional[torch.Tensor] = None, up_conf: Optional[torch.Tensor] = None,
+                  lat_conf: Optional[torch.Tensor] = None):
+    """gclm_bin_loss_grad: the gradients of bin_loss's two losses with respect to the logits given, (grad_up (B, Ku, H, W),
+    grad_lat (B, Kl, H, W)) in the logits' dtype, None for an absent head: `scale` (B, 2) = [up, latitude] (grad_output x weight
+    / denominator, on the device) times softmax(z) - onehot(bin), times the confidence where given, with `lse` and `bins` as
+    bin_loss returned them.  One launch per 65 535 images on torch's current stream."""
+    logits, confs, B, H, W, dev, dtype = _bin_loss_call("bin_loss_grad", up_logits, lat_logits, up_conf, lat_conf)
+    scale = _call.dev_f32(scale, "scale")
+    if scale.shape != (B, 2) or scale.device != dev:
+        raise ValueError(f"`scale` {tuple(scale.shape)} on {scale.device} must be ({B}, 2) on {dev}")
+    if lse.shape != (B, 2, H, W) or lse.dtype != torch.float32 or bins.shape != (B, 2, H, W) or bins.dtype != torch.int16 or \
+            lse.device != dev or bins.device != dev or not (lse.is_contiguous() and bins.is_contiguous()):
+        raise ValueError(f"`lse` and `bins` are bin_loss's: contiguous ({B}, 2, {H}, {W}) float32 and int16 on {dev}")
+    grads = [None if t is None else torch.empty_like(t) for t in logits]
+    if B * H * W == 0:
+        return tuple(grads)
+    counts = [0 if t is None else t.shape[1] for t in logits]
+    for b0, n in _call.slices(B):
+        _call.call("gclm_bin_loss_grad", _call.ptr_at(logits[0], b0), counts[0], _call.ptr_at(logits[1], b0), counts[1], dtype,
+                   _call.ptr_at(confs[0], b0), _call.ptr_at(confs[1], b0), n, H, W, lse[b0].data_ptr(), bins[b0].data_ptr(),
+                   scale[b0].data_ptr(), _call.ptr_at(grads[0], b0), _call.ptr_at(grads[1], b0), _call.raw_stream(dev), device=dev)
+    return tuple(grads)
 
 
 def _param_grad_outputs(cam: torch.Tensor, B: int, want_cam: bool, want_grav: bool):

@@ -66,7 +66,9 @@ extern "C" {
  * gclm_field_loss_param_grad, gclm_perspective_fields_backward and gclm_field_param_grad_workspace added, also within 610: the
  * gradients of the field losses, and of the rendered fields, with respect to the camera and the gravity;
  * gclm_calibrate_soft added, also within 610: gclm_calibrate_ex with a focal and a gravity prior given with their standard
- * deviations, as pseudo-observations of every LM step and of the uncertainty pass).
+ * deviations, as pseudo-observations of every LM step and of the uncertainty pass;
+ * gclm_bin_loss, gclm_bin_loss_grad and gclm_bin_loss_workspace added, also within 610: the classification heads' training
+ * loss -- per-pixel cross-entropy of the logits against the bins of a calibration's fields -- and its gradient to the logits).
  * gclm_create refuses a gclm_config whose first two fields do not
  * carry the library's own sizeof(gclm_config) and GCLM_VERSION, with a message naming both sides. */
 #define GCLM_VERSION 610
@@ -736,6 +738,56 @@ int gclm_field_loss(int camera_model, const float* d_cam, const float* d_grav, i
 int gclm_field_loss_grad(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const float* d_up,
                          const float* d_lat, const float* d_up_conf, const float* d_lat_conf, int up_loss, int lat_loss,
                          const float* d_scale, float* d_grad_up, float* d_grad_lat, void* stream);
+
+/*
+ * The loss the classification heads are trained with (the heads gclm_pack_fields_bins decodes), per image, and its gradient
+ * with respect to the logits, against the calibration (camera rows, gravities) of each image: what a training step gets from
+ * get_perspective_field + encode_up_bin / encode_bin_latitude + F.cross_entropy, with the target evaluated per pixel in
+ * registers -- no field and no target map is rendered, no log-softmax of the logits' size is written; the logits are read
+ * once forward and once more backward.
+ * Logits as gclm_pack_fields_bins takes them: d_up_logits (B, up_bins, H, W) and d_lat_logits (B, lat_bins, H, W), planar, of
+ * the one type logit_dtype (enum gclm_logit_dtype; 16-bit logits are the floats they widen to); either may be NULL, not both,
+ * and an absent head's count is not looked at.  d_cam (B, 8), d_grav (B, 3) and the target fields as gclm_field_errors takes
+ * and evaluates them (the up field normalised).  Confidences d_up_conf, d_lat_conf (B, H, W) float32, either may be NULL: a
+ * NULL confidence is how a caller expresses use_uncertainty_loss = False.
+ * Target bins, float32: up -- degrees = atan2(t_y, t_x) 180 / pi + 180, bin = rint(degrees / (360 / (up_bins - 1))) (half to
+ * even), a full turn wraps to 0, a target that is exactly (0, 0) is the invalid class up_bins - 1; latitude -- class k holds
+ * the degrees in (-90 + k 180 / lat_bins, -90 + (k + 1) 180 / lat_bins], the first and the last class open-ended.
+ * Per pixel of a head with logits z and target bin t:  lse = log sum_k exp z_k,  ce = lse - z_t,  hit = [argmax_k z_k == t]
+ * with torch.argmax's rule (the first index of the greatest value, a NaN above everything).
+ * gclm_bin_loss writes
+ *   d_out  (B, 6) float32 = [up numerator, up denominator, up hits, latitude numerator, latitude denominator, latitude hits]:
+ *          numerator = sum w ce, denominator = sum w with w the head's confidence (H W, and w = 1, without one), hits = sum hit
+ *          (exact below 2^24 pixels); the loss is numerator / denominator, the accuracy hits / (H W); no loss weight is applied;
+ *          the three entries of a NULL head are NaN.  sum conf = 0 gives 0 / 0.
+ *   d_lse  (B, 2, H, W) float32 and d_bins (B, 2, H, W) int16: lse and the target bin of every pixel, plane 0 the up head's,
+ *          plane 1 the latitude's; the planes of a NULL head are not written.  gclm_bin_loss_grad reads them: the target is
+ *          not evaluated a second time, so both passes agree on every pixel's bin.
+ * Every workgroup leaves records of six float32 sums in d_workspace, of at least gclm_bin_loss_workspace(B, H, W) bytes (0 for
+ * sizes the call refuses); a second small launch sums each image's records in float64 in a fixed order.  No atomics: results
+ * are bit-identical from call to call, do not depend on the other images of the batch, and do not depend on the pixels per
+ * lane (16-byte loads -- 4 float32 or 8 16-bit logits per lane -- where W is a multiple of that and every plane is 16-byte
+ * aligned, else one pixel per lane: the same records either way).
+ * gclm_bin_loss_grad writes d_grad_up (B, up_bins, H, W) and d_grad_lat (B, lat_bins, H, W) in the logits' type, rounded to
+ * nearest even; either may be NULL, not both, and a head without its gradient is not read:
+ *   grad[b, k] = d_scale[b, head] * w * (exp(z_k - lse) - [k == t]),
+ * d_scale (B, 2) = [up, latitude] float32 in device memory, which the caller forms as grad_output * weight / denominator from
+ * d_out.  There is no gradient to the confidences, the camera or the gravity: the targets are discrete.
+ * Both return -3 (before any HIP call) for both logit tensors NULL, a confidence given for a NULL head, up_bins outside
+ * 2..GCLM_MAX_BINS or lat_bins outside 1..GCLM_MAX_BINS (of a head that is given), an unknown logit_dtype, B < 0 or above
+ * 65535, H or W < 1, H * W > 2^31 - 1 or a tile grid over 2^32 threads, a pointer that is not aligned to its element, and an
+ * output that overlaps an input or another output; gclm_bin_loss also for a NULL d_cam, d_grav, d_workspace, d_out, d_lse or
+ * d_bins, a camera_model outside 0..3 and a workspace that is too small; gclm_bin_loss_grad also for a NULL d_lse, d_bins or
+ * d_scale, both gradients NULL and a gradient given for a NULL head.  B = 0 succeeds and launches nothing.  -10 if a launch
+ * fails.  Asynchronous on `stream`; no allocation.
+ */
+size_t gclm_bin_loss_workspace(int B, int H, int W);
+int gclm_bin_loss(int camera_model, const float* d_cam, const float* d_grav, int B, int H, int W, const void* d_up_logits, int up_bins,
+                  const void* d_lat_logits, int lat_bins, int logit_dtype, const float* d_up_conf, const float* d_lat_conf,
+                  void* d_workspace, size_t workspace_bytes, float* d_out, float* d_lse, int16_t* d_bins, void* stream);
+int gclm_bin_loss_grad(const void* d_up_logits, int up_bins, const void* d_lat_logits, int lat_bins, int logit_dtype,
+                       const float* d_up_conf, const float* d_lat_conf, int B, int H, int W, const float* d_lse, const int16_t* d_bins,
+                       const float* d_scale, void* d_grad_up, void* d_grad_lat, void* stream);
 
 /*
  * The gradients of the same losses -- or of any function of the fields gclm_perspective_fields renders -- with respect to
